@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MSM witness path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload msm|lhs] [--logn L] [--curve bn254_g1|grumpkin]
+    python bench.py --gpus N --steps K --warmup W [--workload msm|lhs] [--logn L] [--curve bn254_g1|grumpkin] [--dump-outputs DIR]
 
 One "step" = one full n-point MSM (digits -> bucket sort -> bucket accumulation -> bucket
 reduction -> host Horner) over synthetic inputs that are resident in HBM before the timed
@@ -16,6 +16,11 @@ accumulation) at the ALGORITHMIC 96 B per scalar-point pair against the 8 TB/s H
 HIP-event timings taken on the library's own stream; `cpu_baseline` times the oracle's
 restatement of halo2 best_multiexp on the host cores over a bounded sample of the same inputs
 and checks the GPU result on that sample bit-exactly.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float64; every 256-bit integer as its 32-bit little-endian words, which float64 holds exactly;
+every point in canonical affine form, since its Jacobian representative varies from run to run),
+so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -73,7 +78,7 @@ def gen_scalars(n: int, modulus: int, seed: int) -> np.ndarray:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=["msm", "lhs", "lhs_witness"], default="msm",
                     help="msm: best_multiexp (the headline); lhs: the MSM core of compute_lhs_witness; lhs_witness: compute_lhs_witness in full "
@@ -93,7 +98,11 @@ def main():
                     help="N > 1 partition of the MSM: Pippenger windows (north star, default) or pairs (SURVEY 8e alternative)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="lemsm_set_option tuning knob for A/B runs (repeatable); reported in config.options")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -162,7 +171,7 @@ def main():
     def step():
         if args.workload == "msm":
             if world == 1 and args.batch > 1:
-                return ctx.msm_batch_device(cid, [d_scalars.ptr] * args.batch, d_points.ptr, n)[-1]
+                return ctx.msm_batch_device(cid, [d_scalars.ptr] * args.batch, d_points.ptr, n)
             if world == 1:
                 return ctx.msm_device(cid, d_scalars.ptr, d_points.ptr, n)
             if args.sharding == "points":
@@ -171,10 +180,10 @@ def main():
                 return ctx.msm_sharded_device(cid, d_scalars.ptr, d_points.ptr, n)
             return ldist.sharded_msm(ctx, cid, d_scalars.ptr, d_points.ptr, n, world, rank, coll_dev)
         if world == 1:
-            return ctx.lhs_msm_device(cid, d_scalars.ptr, d_points.ptr, n, args.base, True)[0]
+            return ctx.lhs_msm_device(cid, d_scalars.ptr, d_points.ptr, n, args.base, True)
         if exchange == "rccl-abi":
-            return ctx.lhs_msm_sharded_device(cid, d_scalars.ptr, d_points.ptr, n, args.base, True)[0]
-        return ldist.sharded_lhs_msm(ctx, cid, d_scalars.ptr, d_points.ptr, n, args.base, world, rank, coll_dev)[0]
+            return ctx.lhs_msm_sharded_device(cid, d_scalars.ptr, d_points.ptr, n, args.base, True)
+        return ldist.sharded_lhs_msm(ctx, cid, d_scalars.ptr, d_points.ptr, n, args.base, world, rank, coll_dev)
 
     def sync():
         if world > 1:
@@ -187,7 +196,7 @@ def main():
     t0 = time.perf_counter()
     acc_ms = 0.0; tot_ms = 0.0; launches = 0; clock_sum = 0.0; clock_n = 0
     for _ in range(args.steps):
-        result = step()
+        outputs = step()
         tt, ta, nl = ctx.last_timing()
         acc_ms += ta; tot_ms += tt; launches += nl
         ck = ctx.last_accum_clock_mhz()
@@ -201,8 +210,18 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the timed path's result: msm -> the Jacobian point (a batch: (K, 12), the last call checked); lhs -> (carry, carries)
+    if args.workload == "msm":
+        result = outputs[-1] if outputs.ndim == 2 else outputs
+    else:
+        result = outputs[0]
 
     if rank == 0:
+        if args.dump_outputs:
+            if args.workload == "msm":
+                dump_outputs(args.dump_outputs, cid, {"msm_result": outputs})
+            else:
+                dump_outputs(args.dump_outputs, cid, {"lhs_carry": outputs[0], "lhs_carries": outputs[1]})
         ms_per_step = elapsed / args.steps * 1e3
         batch = args.batch if (args.workload == "msm" and world == 1) else 1
         value = n * batch * args.steps / elapsed
@@ -331,6 +350,10 @@ def bench_lhs_witness(args, ctx, n, logn, world, rank, dist, torch, red_dev):
         elapsed = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:
+        arrays = {"lhs_witness_index": index}
+        arrays.update(sample_coefficients(ctx, out, index))
+        dump_outputs(args.dump_outputs, cid, {"lhs_witness_carry": carry}, arrays)
     ms_per_step = elapsed / args.steps * 1e3
     achieved = ntt_bytes / (ntt_ms * 1e-3) / 1e9 if ntt_ms > 0 else 0.0
     coeffs = int(index[:, 1].sum() + index[:, 3].sum())
@@ -406,6 +429,57 @@ def verify_lhs_witness(ctx, cid, scalars, q, d_points, n, base, carry, index, ou
     if done:
         checks.append("witness vanishes on sampled points of its list (%d digit positions)" % done)
     return checks
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_COEFF_SAMPLE = 1 << 16      # coefficients of the witness functions written by --dump-outputs (fixed seed)
+
+
+def words_f64(a) -> np.ndarray:
+    """u64 limbs -> their 32-bit little-endian words as float64 (exact): (..., k) -> (..., 2k)"""
+    a = np.ascontiguousarray(a, np.uint64)
+    return a.view(np.uint32).astype(np.float64)
+
+
+def dump_outputs(path, cid, points, arrays=None):
+    """--dump-outputs: the outputs of the last timed step as path/<name>.npy in float64.  `points`: raw Montgomery
+    Jacobian points (..., 12) u64, written as the canonical affine x || y of each (..., 16 words): the group element, not
+    its Jacobian representative, which depends on the order of the additions.  `arrays`: values float64 holds exactly."""
+    from oracle import cref
+    out = {}
+    for name, a in points.items():
+        a = np.ascontiguousarray(a, np.uint64)
+        aff = [np.frombuffer(cref.jac_to_canonical(cid, p), np.uint32) for p in a.reshape(-1, 12)]
+        out[name] = np.stack(aff).reshape(a.shape[:-1] + (16,)).astype(np.float64)
+    for name, a in (arrays or {}).items():
+        out[name] = np.asarray(a, np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def sample_coefficients(ctx, buf, index):
+    """A fixed, seeded sample of the coefficients compute_lhs_witness left in HBM: the k-th coefficient over all functions,
+    numbered in index order (function f: its len_a coefficients of a, then its len_b of b), for DUMP_COEFF_SAMPLE values of k
+    drawn with a fixed seed (all of them when there are fewer).  Returns the sampled k (float64) and the coefficients (raw Montgomery, 8 words each)."""
+    segs = []                                       # (element offset, length) in numbering order
+    for oa, la, ob, lb in np.asarray(index, np.int64):
+        segs += [(int(oa), int(la)), (int(ob), int(lb))]
+    lens = np.array([ln for _, ln in segs], np.int64)
+    total = int(lens.sum())
+    rng = np.random.Generator(np.random.PCG64(0x5EED2000))
+    ks = np.sort(rng.choice(total, size=DUMP_COEFF_SAMPLE, replace=False)) if total > DUMP_COEFF_SAMPLE else np.arange(total)
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    which = np.searchsorted(starts, ks, side="right") - 1
+    coeffs = np.zeros((ks.size, 4), np.uint64)
+    for s in np.unique(which):
+        sel = which == s
+        off, ln = segs[s]
+        coeffs[sel] = _download_elems(ctx, buf, off, ln)[ks[sel] - starts[s]]
+    return {"lhs_witness_coeff_sample_k": ks.astype(np.float64), "lhs_witness_coeff_sample": words_f64(coeffs)}
 
 
 def _download_elems(ctx, buf, off_elems, count):

@@ -1,8 +1,8 @@
 """Pins the oracle (oracle/pyref.py and oracle/c) before anything trusts it.
 
 * the reference's only byte-level golden data: the 192 raw-Montgomery bn256::Fr constants of
-  /root/reference/src/precomputed_fft_data.rs, through tests/golden/fr_mont_chains.json (heads +
-  SHA-256 of each table) and, when the reference is mounted, through the file itself;
+  its src/precomputed_fft_data.rs, through tests/golden/fr_mont_chains.json (heads + SHA-256 of
+  each table), and every entry rebuilt from the root of unity against those digests;
 * the public EIP-196 vector 2*(1,2) on BN254 G1;
 * SURVEY.md Appendix A micro-KATs for negbase_decompose and the digit-count table;
 * every property the reference's own tests assert (negbase_test, lhs_test);
@@ -23,8 +23,6 @@ from oracle import cref, pyref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-REF_FILE = "/root/reference/src/precomputed_fft_data.rs"
-
 
 def test_fr_montmul_chains_python():
     chains = load_json("fr_mont_chains.json")
@@ -44,12 +42,29 @@ def test_fr_montmul_chains_c_oracle():
         assert got[name] == chains[name]["sha256"], name
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FILE), reason="reference not mounted (GPU box)")
+OMEGA_2_28 = 0x03DDB9F5166D18B798865EA93DD31F743215CF6DD39329C8D34F1ED960C37C9C   # bn256::Fr ROOT_OF_UNITY (order 2^28)
+
+
+def fr_fft_tables():
+    """The three 64-entry tables of the reference's src/precomputed_fft_data.rs, rebuilt from public constants in
+    Python integers: omega_pow[i] = w^(2^i), omega_pow_inv[i] = w^(-2^i), half_pow[i] = 2^(-i), raw Montgomery, 32 B LE."""
+    r = pyref.R_BN254
+    mont = lambda x: (x * (1 << 256) % r).to_bytes(32, "little")
+    w, wi, h = OMEGA_2_28, pow(OMEGA_2_28, -1, r), pow(2, -1, r)
+    return {"omega_pow": [mont(pow(w, 1 << i, r)) for i in range(64)],
+            "omega_pow_inv": [mont(pow(wi, 1 << i, r)) for i in range(64)],
+            "half_pow": [mont(pow(h, i, r)) for i in range(64)]}
+
+
 def test_fr_constants_against_reference_file():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from make_golden import parse_reference_tables
-    t = parse_reference_tables(REF_FILE)
+    """every entry of the reference's tables: rebuilt from the root of unity, they hash to the digests that
+    tests/golden/fr_mont_chains.json took of the reference file, and they hold the properties the FFT relies on"""
+    import hashlib
+    t = fr_fft_tables()
+    chains = load_json("fr_mont_chains.json")
+    for name, tab in t.items():
+        assert hashlib.sha256(b"".join(tab)).hexdigest() == chains[name]["sha256"], name
+        assert tab[chains[name]["head_index"]].hex() == chains[name]["head"], name
     c = pyref.GRUMPKIN
     r = pyref.R_BN254
     w = [int.from_bytes(b, "little") for b in t["omega_pow"]]
