@@ -335,6 +335,23 @@ class Context:
         self._check(self.lib.lemsm_msm_with_bases(self.h, bases.h, _ptr(s), s.shape[0], _ptr(out)))
         return out
 
+    # ---- fixed-base tables over resident bases ------------------------------------------------
+    def fixed_bases(self, bases: "Bases", window_bits: int = 0, tables: int = 0) -> "FixedBases":
+        """precomputed window tables over resident bases (lemsm_fixed_bases_create); 0 = the plan's choice"""
+        return FixedBases(self, bases, window_bits, tables)
+
+    def msm_fixed(self, fb: "FixedBases", scalars) -> np.ndarray:
+        """sum_i scalars[i] * bases[i] for the first len(scalars) bases of the table (lemsm_msm_fixed)"""
+        s = _scalars(scalars)
+        out = np.zeros(12, np.uint64)
+        self._check(self.lib.lemsm_msm_fixed(self.h, fb.h, _ptr(s), s.shape[0], _ptr(out)))
+        return out
+
+    def msm_fixed_device(self, fb: "FixedBases", d_scalars: int, n: int) -> np.ndarray:
+        out = np.zeros(12, np.uint64)
+        self._check(self.lib.lemsm_msm_fixed_device(self.h, fb.h, d_scalars, n, _ptr(out)))
+        return out
+
     def msm_batch_with_bases(self, bases: "Bases", scalars_list) -> np.ndarray:
         """len(scalars_list) MSMs over the same resident bases, scalar vectors in host memory, uploads pipelined with the
         compute inside the library (lemsm_msm_batch_with_bases); returns (K, 12) Jacobian results"""
@@ -598,6 +615,55 @@ class Bases:
             self.free()
         except Exception:
             pass
+
+
+class FixedBases:
+    """fixed-base window tables of resident bases on one GPU (lemsm_fixed_bases_create)"""
+
+    def __init__(self, ctx: Context, bases: Bases, window_bits: int = 0, tables: int = 0):
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.lemsm_fixed_bases_create(ctx.h, bases.h, window_bits, tables, ctypes.byref(h)))
+        self.ctx, self.h, self.n = ctx, h, bases.n
+
+    def info(self) -> dict:
+        """{"c", "num_windows", "m", "h", "device_bytes"} of the table"""
+        v = [ctypes.c_uint32() for _ in range(4)]
+        b = ctypes.c_size_t()
+        self.ctx._check(self.ctx.lib.lemsm_fixed_bases_info(self.h, *[ctypes.byref(x) for x in v], ctypes.byref(b)))
+        return {"c": v[0].value, "num_windows": v[1].value, "m": v[2].value, "h": v[3].value, "device_bytes": b.value}
+
+    @property
+    def ptr(self) -> int:
+        return self.ctx.lib.lemsm_fixed_bases_device_ptr(self.h)
+
+    def rows(self, first: int, count: int) -> np.ndarray:
+        """table rows [first, first + count) as (count, 8) affine limbs; row i * m + k = 2^(c h k) bases[i]"""
+        out = np.zeros((count, 8), np.uint64)
+        if count:
+            self.ctx._check(self.ctx.lib.lemsm_device_download(self.ctx.h, _ptr(out), self.ptr + first * 64, count * 64))
+        return out
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.lemsm_fixed_bases_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def fixed_plan(curve, n: int, window_bits: int = 0, tables: int = 0) -> dict:
+    """the geometry lemsm_fixed_bases_create would give a table over n bases (pure host: lemsm_fixed_plan)"""
+    lib = _lib.load()
+    v = [ctypes.c_uint32() for _ in range(4)]
+    b = ctypes.c_size_t()
+    rc = lib.lemsm_fixed_plan(_curve_id(curve), n, window_bits, tables, *[ctypes.byref(x) for x in v], ctypes.byref(b))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"c": v[0].value, "num_windows": v[1].value, "m": v[2].value, "h": v[3].value, "device_bytes": b.value}
 
 
 def comm_unique_id() -> bytes:

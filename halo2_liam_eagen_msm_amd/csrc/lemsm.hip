@@ -2482,3 +2482,4 @@ int lemsm_debug_pointop(lemsm_ctx* ctx, int curve, int op, const uint64_t* acc, 
 }  // extern "C"
 
 #include "divisor_abi.inc"
+#include "fixed_base.inc"

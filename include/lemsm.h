@@ -215,6 +215,37 @@ int lemsm_msm_with_bases(lemsm_ctx* ctx, const lemsm_bases* bases, const uint8_t
    call's status is returned. */
 int lemsm_msm_batch_with_bases(lemsm_ctx* ctx, const lemsm_bases* bases, const uint8_t* const* scalars, size_t batch, size_t n, uint64_t* outs);
 
+/* ---- fixed-base MSM: precomputed window tables over resident bases --------------------- */
+/* best_multiexp(&scalars, &pts_aff) (src/argument_witness_calc.rs:144) for a prover that calls it many times over one SRS.
+   A table holds m shifted copies T_k[i] = 2^(c h k) P_i of the bases (k < m, h = ceil(W / m), W signed c-bit windows whose
+   top digit stays below 2^(c-1)), row i * m + k, 64 B each in the ABI's affine form (identity: all-zero row).  A call runs
+   the bucket pipeline over n * m "virtual points" with h windows that all m tables share: one bucket set and one pyramid
+   per folded window, the host's Horner over h windows only (none at h = 1).  Geometry: c in [3, 17], m in [1, W]; 0 = auto
+   (a cost model: n W accumulate additions, 2 h 2^(c-1) pyramid additions, a fixed cost per slab of 2^24 virtual points;
+   an automatic plan keeps its table within 16 GiB).  Out of scope: multi-GPU, batch entries and the negabase path. */
+typedef struct lemsm_fixed_bases lemsm_fixed_bases;
+/* Pure host: the geometry a table over n bases would get (window_bits / tables 0 = auto); device_bytes = m * n * 64.
+   LEMSM_ERR_BAD_ARG for a window width outside [3, 17] or more tables than windows.  (best_multiexp, :144) */
+int lemsm_fixed_plan(int curve, size_t n, uint32_t window_bits, uint32_t tables, uint32_t* c, uint32_t* num_windows, uint32_t* m,
+                     uint32_t* h, size_t* device_bytes);
+/* Builds the table of `bases` on the context's GPU (one doubling chain per base and table, one inversion per base).
+   LEMSM_ERR_NOMEM, before any kernel runs, when the table does not fit in free device memory.  Free the table before its
+   context is destroyed, like lemsm_bases; the bases themselves may be freed once the table exists.  (best_multiexp, :144) */
+int lemsm_fixed_bases_create(lemsm_ctx* ctx, const lemsm_bases* bases, uint32_t window_bits, uint32_t tables,
+                             lemsm_fixed_bases** out);
+/* The table's geometry (as lemsm_fixed_plan).  (best_multiexp, :144) */
+int lemsm_fixed_bases_info(const lemsm_fixed_bases* fb, uint32_t* c, uint32_t* num_windows, uint32_t* m, uint32_t* h,
+                           size_t* device_bytes);
+/* the table on the device: row i * m + k = 2^(c h k) bases[i] (64 B, affine ABI form) */
+const void* lemsm_fixed_bases_device_ptr(const lemsm_fixed_bases* fb);
+void lemsm_fixed_bases_free(lemsm_fixed_bases* fb);
+/* best_multiexp(scalars, bases[0..n]) (:144) for n <= the table's n (halo2 commits to prefixes of the SRS).  Result and status
+   codes are those of lemsm_msm: a non-canonical scalar is LEMSM_ERR_SCALAR_OUT_OF_RANGE with its index in
+   lemsm_last_bad_index, n above the table's n is LEMSM_ERR_LEN_MISMATCH, a table of another context LEMSM_ERR_BAD_ARG. */
+int lemsm_msm_fixed(lemsm_ctx* ctx, const lemsm_fixed_bases* fb, const uint8_t* scalars, size_t n, uint64_t out_jacobian[12]);
+/* the same with the scalars already on the context's GPU (n x 32 B) */
+int lemsm_msm_fixed_device(lemsm_ctx* ctx, const lemsm_fixed_bases* fb, const void* d_scalars, size_t n, uint64_t out_jacobian[12]);
+
 /* ---- negabase decomposition ---------------------------------------------------------- */
 int lemsm_num_digits(int curve, uint8_t base, uint32_t* d);
 /* digits[i*d + k] = k-th negabase digit (LSB first, in [0,base)) of scalar i, zero padded /
