@@ -47,7 +47,7 @@ SYMBOLS = [
     "lemsm_jacobian_to_canonical", "lemsm_jacobian_sum",
     "lemsm_device_alloc", "lemsm_device_free", "lemsm_device_upload", "lemsm_device_download",
     "lemsm_device_gen_walk",
-    "lemsm_debug_montmul", "lemsm_debug_fieldop", "lemsm_debug_pointop",
+    "lemsm_debug_montmul", "lemsm_debug_fieldop", "lemsm_debug_pointop", "lemsm_debug_field29_raw", "lemsm_debug_xyzz29_raw",
     "lemsm_comm_unique_id", "lemsm_comm_init", "lemsm_comm_destroy", "lemsm_comm_info",
     "lemsm_msm_sharded_device", "lemsm_lhs_msm_sharded_device",
     "lemsm_node_create", "lemsm_node_destroy", "lemsm_node_size", "lemsm_node_ctx", "lemsm_node_last_error",
@@ -130,6 +130,8 @@ def load() -> ctypes.CDLL:
         "lemsm_debug_montmul": (i, [vp, i, u64p, u64p, u64p, sz]),
         "lemsm_debug_fieldop": (i, [vp, i, i, u64p, u64p, u64p, sz]),
         "lemsm_debug_pointop": (i, [vp, i, i, u64p, u64p, u64p, sz]),
+        "lemsm_debug_field29_raw": (i, [vp, i, i, vp, vp, vp, vp, vp, sz]),
+        "lemsm_debug_xyzz29_raw": (i, [vp, i, i, vp, vp, vp, sz]),
         "lemsm_comm_unique_id": (i, [u8p]),
         "lemsm_comm_init": (i, [vp, u8p, i, i]),
         "lemsm_comm_destroy": (i, [vp]),

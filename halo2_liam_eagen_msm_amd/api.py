@@ -591,6 +591,35 @@ class Context:
         self._check(self.lib.lemsm_debug_pointop(self.h, _curve_id(curve), op, _ptr(acc), _ptr(q), _ptr(out), acc.shape[0]))
         return out
 
+    # raw-limb hooks of the lazy field and XYZZ29 (lemsm.h LEMSM_F29_* / LEMSM_X29_*): int32 limbs in and out, no conversion
+    F29_OPS = ("mul", "sqr", "mul2", "mul_addhi", "sqr_addhi", "add", "sub", "neg", "cneg", "wnorm", "canon", "reduce_small",
+               "mul32", "from_abi", "div32", "is_zero_mod", "limbs_zero", "hi_term", "pp_is_zero")
+    X29_OPS = ("madd", "madd_abi", "add", "dbl_affine", "dbl", "scale", "unscale", "add4_mem")
+
+    def debug_field29_raw(self, curve, op, a, b=None, c=None, d=None) -> np.ndarray:
+        """(n, 10) int32: the 9 result limbs of `op` (a name of F29_OPS or its number) on (n, 9) int32 operands, then the
+        predicate word"""
+        opi = self.F29_OPS.index(op) if isinstance(op, str) else int(op)
+        a = np.ascontiguousarray(a, np.int32).reshape(-1, 9)
+        ops = [a] + [np.zeros_like(a) if x is None else np.ascontiguousarray(x, np.int32).reshape(-1, 9) for x in (b, c, d)]
+        if any(x.shape != a.shape for x in ops):
+            raise ValueError("field29_raw operands must all be n x 9 int32")
+        out = np.zeros((a.shape[0], 10), np.int32)
+        self._check(self.lib.lemsm_debug_field29_raw(self.h, _curve_id(curve), opi, *[_ptr(x) for x in ops], _ptr(out), a.shape[0]))
+        return out
+
+    def debug_xyzz29_raw(self, curve, op, acc, q=None) -> np.ndarray:
+        """(n, 37) int32: the 36 result limbs of `op` (a name of X29_OPS or its number) and the flag word; acc and q are
+        (n, 37) int32 records (acc's flag: `empty` on entry)"""
+        opi = self.X29_OPS.index(op) if isinstance(op, str) else int(op)
+        acc = np.ascontiguousarray(acc, np.int32).reshape(-1, 37)
+        q = np.zeros_like(acc) if q is None else np.ascontiguousarray(q, np.int32).reshape(-1, 37)
+        if q.shape != acc.shape:
+            raise ValueError("xyzz29_raw records must both be n x 37 int32")
+        out = np.zeros_like(acc)
+        self._check(self.lib.lemsm_debug_xyzz29_raw(self.h, _curve_id(curve), opi, _ptr(acc), _ptr(q), _ptr(out), acc.shape[0]))
+        return out
+
 
 class Bases:
     """affine bases resident on one GPU (lemsm_bases_upload): later MSMs upload only their scalars"""

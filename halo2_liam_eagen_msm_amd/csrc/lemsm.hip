@@ -1520,6 +1520,104 @@ __global__ void k_dbg_pointop29(int op, const char* __restrict__ acc_in, const c
   dbg_out29<F29>(op_, acc.x); dbg_out29<F29>(op_ + 32, acc.y); dbg_out29<F29>(op_ + 64, acc.zz); dbg_out29<F29>(op_ + 96, acc.zzz);
 }
 
+// ---- raw-limb entries: the lazy field and XYZZ29 exactly as the hot kernels call them, no conversion in or out.  A field
+// element is 9 x i32 (its limbs as they sit in registers); a point record is 36 limbs (x, y, zz, zzz) + one flag word.
+template <class F29>
+__device__ __forceinline__ void raw_ld(typename F29::fe& r, const int32_t* p) {
+#pragma unroll
+  for (int k = 0; k < 9; k++) r.l[k] = p[k];
+}
+template <class F29>
+__device__ __forceinline__ void raw_st(int32_t* p, const typename F29::fe& a) {
+#pragma unroll
+  for (int k = 0; k < 9; k++) p[k] = a.l[k];
+}
+// lemsm.h LEMSM_F29_*: out = 9 limbs + a predicate word (1/0 for the boolean ops, 0 otherwise)
+template <class G29>
+__global__ void k_dbg_field29_raw(int op, const int32_t* __restrict__ a, const int32_t* __restrict__ b, const int32_t* __restrict__ c,
+                                  const int32_t* __restrict__ d, int32_t* __restrict__ out, u32 n) {
+  typedef typename G29::F_ F29;
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  typename F29::fe x, y, z, w, r;
+  raw_ld<F29>(x, a + 9 * (size_t)i); raw_ld<F29>(y, b + 9 * (size_t)i); raw_ld<F29>(z, c + 9 * (size_t)i); raw_ld<F29>(w, d + 9 * (size_t)i);
+  int32_t pred = 0;
+  r = x;
+  switch (op) {
+    case 0: F29::mul(r, x, y); break;
+    case 1: F29::sqr(r, x); break;
+    case 2: F29::mul2(r, x, y, z, w); break;
+    case 3: F29::mul_addhi(r, x, y, z); break;
+    case 4: F29::sqr_addhi(r, x, z); break;
+    case 5: F29::add(r, x, y); break;
+    case 6: F29::sub(r, x, y); break;
+    case 7: F29::neg(r, x); break;
+    case 8: F29::cneg(r, x, y.l[0] != 0); break;
+    case 9: F29::wnorm(r); break;
+    case 10: F29::canon(r); break;
+    case 11: F29::reduce_small(r, x); break;
+    case 12: F29::mul32(r, x); break;
+    case 13: F29::from_abi(r, x); break;
+    case 14: F29::div32(r, x); break;
+    case 15: pred = F29::is_zero_mod(x) ? 1 : 0; break;
+    case 16: pred = F29::limbs_zero(x) ? 1 : 0; break;
+    case 17: G29::hi_term(r, x, y); break;
+    case 18: pred = G29::pp_is_zero(x) ? 1 : 0; break;
+    default: break;
+  }
+  int32_t* o = out + 10 * (size_t)i;
+  raw_st<F29>(o, r);
+  o[9] = pred;
+}
+
+template <class G29>
+__device__ __forceinline__ void raw_ld_pt(typename G29::pt& p, const int32_t* s) {
+  typedef typename G29::F_ F29;
+  raw_ld<F29>(p.x, s); raw_ld<F29>(p.y, s + 9); raw_ld<F29>(p.zz, s + 18); raw_ld<F29>(p.zzz, s + 27);
+}
+template <class G29>
+__device__ __forceinline__ void raw_st_pt(int32_t* s, const typename G29::pt& p) {
+  typedef typename G29::F_ F29;
+  raw_st<F29>(s, p.x); raw_st<F29>(s + 9, p.y); raw_st<F29>(s + 18, p.zz); raw_st<F29>(s + 27, p.zzz);
+}
+// lemsm.h LEMSM_X29_* except ADD4_MEM: one thread per record; acc word 36 = `empty` on entry (madd, madd_abi)
+template <class G29>
+__global__ void k_dbg_xyzz29_raw(int op, const int32_t* __restrict__ acc_in, const int32_t* __restrict__ q_in, int32_t* __restrict__ out, u32 n) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* ap = acc_in + (size_t)i * 37;
+  const int32_t* qp = q_in + (size_t)i * 37;
+  typename G29::pt acc, q, res;
+  raw_ld_pt<G29>(acc, ap); raw_ld_pt<G29>(q, qp);
+  bool empty = ap[36] != 0;
+  res = acc;
+  switch (op) {
+    case 0: G29::madd(res, q.x, q.y, empty); break;
+    case 1: G29::madd_abi(res, q.x, q.y, empty); break;
+    case 2: G29::add(res, q); break;
+    case 3: G29::template dbl_impl<true>(res, acc); break;
+    case 4: G29::template dbl_impl<false>(res, acc); break;
+    case 5: G29::scale(res); break;
+    case 6: G29::unscale(res); break;
+    default: break;
+  }
+  int32_t* o = out + (size_t)i * 37;
+  raw_st_pt<G29>(o, res);
+  o[36] = empty ? 1 : 0;
+}
+// LEMSM_X29_ADD4_MEM as k_pyramid runs it: four lanes per pair, 16 pairs per 64-lane wave; record i of acc and q are the pair,
+// the 36-byte elements of a record are its x, y, zz, zzz.  `out` is zeroed by the caller (a pair whose quad returns false
+// stores nothing); lane 0 of the quad writes the return value.
+template <class G29>
+__global__ void k_dbg_add4_raw(const int32_t* __restrict__ acc_in, const int32_t* __restrict__ q_in, int32_t* __restrict__ out, u32 n) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 i = t >> 2, q = t & 3u;
+  if (i >= n) return;   // whole quads: 4 n threads are live, a quad is live in all or none of its lanes
+  bool ok = G29::add4_mem(reinterpret_cast<const char*>(acc_in + (size_t)i * 37), reinterpret_cast<const char*>(q_in + (size_t)i * 37),
+                          reinterpret_cast<char*>(out + (size_t)i * 37), q);
+  if (q == 0u) out[(size_t)i * 37 + 36] = ok ? 1 : 0;
+}
+
 // optional input validation (option "validate_points"): every affine point is (0,0) or satisfies y^2 = x^3 + b
 template <class F>
 __global__ __launch_bounds__(256) void k_validate_points(const uint4* __restrict__ pts, u32 n, int bcoef /* +3 or -17 */, u32* __restrict__ err) {
@@ -2475,6 +2573,61 @@ int lemsm_debug_pointop(lemsm_ctx* ctx, int curve, int op, const uint64_t* acc, 
   else hipLaunchKernelGGL((k_dbg_pointop<FrDev>), g, blk, 0, ctx->stream, op == 2 ? 0 : op, da, db, dout, (u32)n);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, dout, n * 128, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return LEMSM_OK;
+}
+
+int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
+                            int32_t* out, size_t n) {
+  if (!ctx || !a || !b || !c || !d || !out) return LEMSM_ERR_BAD_ARG;
+  int rc = check_curve(ctx, curve); if (rc) return rc;
+  if (op < 0 || op > LEMSM_F29_PP_IS_ZERO) return fail(ctx, LEMSM_ERR_BAD_ARG, "field29 raw op out of range (lemsm.h LEMSM_F29_*)");
+  if (!n) return LEMSM_OK;
+  if (n > ((size_t)1 << 24)) return fail(ctx, LEMSM_ERR_BAD_ARG, "field29 raw: at most 2^24 operands per call");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t eb = n * 36, ob = n * 40;
+  size_t o1 = align_up(eb, 256), o2 = o1 + align_up(eb, 256), o3 = o2 + align_up(eb, 256), o4 = o3 + align_up(eb, 256);
+  rc = reserve(ctx, ctx->ws, o4 + ob + 256); if (rc) return rc;
+  char* base = (char*)ctx->ws.p;
+  HIPCHK(ctx, hipMemcpyAsync(base, a, eb, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(base + o1, b, eb, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(base + o2, c, eb, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(base + o3, d, eb, hipMemcpyHostToDevice, ctx->stream));
+  const int32_t *da = (const int32_t*)base, *db = (const int32_t*)(base + o1), *dc = (const int32_t*)(base + o2), *dd = (const int32_t*)(base + o3);
+  int32_t* dout = (int32_t*)(base + o4);
+  dim3 g((u32)((n + 255) / 256)), blk(256);
+  if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_field29_raw<GqLazy>), g, blk, 0, ctx->stream, op, da, db, dc, dd, dout, (u32)n);
+  else hipLaunchKernelGGL((k_dbg_field29_raw<GrLazy>), g, blk, 0, ctx->stream, op, da, db, dc, dd, dout, (u32)n);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return LEMSM_OK;
+}
+
+int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc, const int32_t* q, int32_t* out, size_t n) {
+  if (!ctx || !acc || !q || !out) return LEMSM_ERR_BAD_ARG;
+  int rc = check_curve(ctx, curve); if (rc) return rc;
+  if (op < 0 || op > LEMSM_X29_ADD4_MEM) return fail(ctx, LEMSM_ERR_BAD_ARG, "xyzz29 raw op out of range (lemsm.h LEMSM_X29_*)");
+  if (!n) return LEMSM_OK;
+  if (n > ((size_t)1 << 24)) return fail(ctx, LEMSM_ERR_BAD_ARG, "xyzz29 raw: at most 2^24 records per call");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t rb = n * 37 * 4;
+  char *da, *db, *dout;
+  rc = dbg_run3(ctx, acc, rb, q, rb, rb, &da, &db, &dout); if (rc) return rc;
+  const int32_t *ia = (const int32_t*)da, *iq = (const int32_t*)db;
+  int32_t* io = (int32_t*)dout;
+  if (op == LEMSM_X29_ADD4_MEM) {
+    HIPCHK(ctx, hipMemsetAsync(dout, 0, rb, ctx->stream));
+    dim3 g((u32)((4 * n + 63) / 64)), blk(64);
+    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_add4_raw<GqLazy>), g, blk, 0, ctx->stream, ia, iq, io, (u32)n);
+    else hipLaunchKernelGGL((k_dbg_add4_raw<GrLazy>), g, blk, 0, ctx->stream, ia, iq, io, (u32)n);
+  } else {
+    dim3 g((u32)((n + 63) / 64)), blk(64);
+    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_xyzz29_raw<GqLazy>), g, blk, 0, ctx->stream, op, ia, iq, io, (u32)n);
+    else hipLaunchKernelGGL((k_dbg_xyzz29_raw<GrLazy>), g, blk, 0, ctx->stream, op, ia, iq, io, (u32)n);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, dout, rb, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return LEMSM_OK;
 }

@@ -10,6 +10,21 @@
 // (~2,000 VALU instructions).
 //
 // Points in memory: 160 bytes of raw limbs (see load/store below); identity = all zero.
+//
+// Range table (tests/lazy29.py RANGE_TABLE; tests/test_lazy29_model.py checks by interval arithmetic, statement by
+// statement, that madd, madd_abi, add, dbl_impl, scale / unscale and add4_mem map records inside it to records inside it).
+// Every record the kernels hold or store, in both forms (ZZ, ZZZ or 32 ZZ, 32 ZZZ), limbs 0..7 in [0, 2^29), and the
+// intermediates P = U2 - U1, PP = P^2 / 2^261, R = S2 - S1 and add4_mem's T = RR - PPP - 2Q:
+//   X    [-1.06, 3.08] N
+//   Y    [-1.04, 1.04] N
+//   ZZ   [0, 1.03] N
+//   ZZZ  [-0.02, 1.02] N
+//   P    [-3.08, 2.07] N
+//   PP   [0, 1.06] N
+//   R    [-1.05, 2.05] N
+//   T    [-3.02, 1.02] N
+// So every record meets canon's and reduce_raw29's |V| < 8N, a P == kN has |k| <= 3 (k^2 < 2^261 / N ~ 169: PP is 0 or
+// N, pp_is_zero's two arms), and no column of a product exceeds 20 * 2^58.
 #pragma once
 #include "field29.cuh"
 

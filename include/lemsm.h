@@ -415,6 +415,48 @@ int lemsm_debug_montmul(lemsm_ctx* ctx, int curve, const uint64_t* a, const uint
 int lemsm_debug_fieldop(lemsm_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int lemsm_debug_pointop(lemsm_ctx* ctx, int curve, int op, const uint64_t* acc_xyzz, const uint64_t* q,
                         uint64_t* out_xyzz, size_t n);
+/* Raw-limb entries of the lazy field (Field29) and its XYZZ law (XYZZ29): the inline functions the hot kernels call, on the
+   limbs as they sit in registers, with no conversion in or out (option "field" plays no part).  n <= 2^24.
+   field29_raw: a, b, c, d, n x 9 int32 each (pass zeros where an op has fewer operands); out n x 10 int32: the 9 result
+   limbs, then a predicate word (1/0 for the boolean ops, 0 otherwise; their limbs echo a). */
+enum {
+  LEMSM_F29_MUL = 0,          /* mul(a, b) */
+  LEMSM_F29_SQR = 1,          /* sqr(a) */
+  LEMSM_F29_MUL2 = 2,         /* mul2(a, b, c, d) */
+  LEMSM_F29_MUL_ADDHI = 3,    /* mul_addhi(a, b, hi = c) */
+  LEMSM_F29_SQR_ADDHI = 4,    /* sqr_addhi(a, hi = c) */
+  LEMSM_F29_ADD = 5,          /* add(a, b) */
+  LEMSM_F29_SUB = 6,          /* sub(a, b) */
+  LEMSM_F29_NEG = 7,          /* neg(a) */
+  LEMSM_F29_CNEG = 8,         /* cneg(a, flag = b[0] != 0) */
+  LEMSM_F29_WNORM = 9,        /* wnorm(a) */
+  LEMSM_F29_CANON = 10,       /* canon(a) */
+  LEMSM_F29_REDUCE_SMALL = 11,
+  LEMSM_F29_MUL32 = 12,
+  LEMSM_F29_FROM_ABI = 13,
+  LEMSM_F29_DIV32 = 14,
+  LEMSM_F29_IS_ZERO_MOD = 15, /* predicate */
+  LEMSM_F29_LIMBS_ZERO = 16,  /* predicate */
+  LEMSM_F29_HI_TERM = 17,     /* XYZZ29::hi_term(ppp = a, q = b) */
+  LEMSM_F29_PP_IS_ZERO = 18   /* XYZZ29::pp_is_zero(a), predicate */
+};
+int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a, const int32_t* b, const int32_t* c,
+                            const int32_t* d, int32_t* out, size_t n);
+/* xyzz29_raw: acc, q, out, n x 37 int32 each: 36 limbs (x, y, zz, zzz) and a flag word.  acc's flag is `empty` on entry to
+   madd / madd_abi; out's flag is `empty` on exit, or add4_mem's return value (its record stays zero where it is 0).  madd and
+   madd_abi take the incoming affine point from q's x and y; madd_abi runs on acc as given (the scaled form).  add4_mem runs
+   as k_pyramid runs it: four lanes per pair, 16 pairs per wave, the record's 36-byte elements as its operands. */
+enum {
+  LEMSM_X29_MADD = 0,         /* madd(acc, q.x, q.y, empty) */
+  LEMSM_X29_MADD_ABI = 1,     /* madd_abi(acc, q.x, q.y, empty) */
+  LEMSM_X29_ADD = 2,          /* add(acc, q) */
+  LEMSM_X29_DBL_AFFINE = 3,   /* dbl_impl<true>(acc) */
+  LEMSM_X29_DBL = 4,          /* dbl_impl<false>(acc) */
+  LEMSM_X29_SCALE = 5,
+  LEMSM_X29_UNSCALE = 6,
+  LEMSM_X29_ADD4_MEM = 7      /* add4_mem(acc, q) */
+};
+int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc, const int32_t* q, int32_t* out, size_t n);
 /* Plain transform over bn256::Fr of nseq sequences of 2^logn elements, natural order in and out, with the reference's
    omega = FftPrecomp::omega_pow(S - logn) (src/regular_functions_utils.rs:111-124); the inverse is scaled by 1/N. */
 int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, int inverse);

@@ -127,6 +127,47 @@ void raw29_checks() {
     host::fe got = reduce_raw29<P>(limbs);
     CHECK(F::eq(got, a));
   }
+  // records at the limits: V = c + k N for every k with |V| < 8N (+-(8N - 1) included) and c in {0, 1, N - 1}, and V at the
+  // ends of the range table of xyzz29.cuh (c = floor(r N / 100), k = floor(f), f = k + r / 100 the end in units of N)
+  struct Edge { u64 r100; int k; };
+  std::vector<Edge> edges;
+  for (int k = -8; k <= 7; k++) for (u64 r : {0ULL, 1ULL, 2ULL}) edges.push_back({r | (1ULL << 63), k});   // r: 0, 1, N - 1
+  static const int table_ends[] = {-106, 308, -104, 104, 0, 103, -2, 102};   // X, Y, ZZ, ZZZ ends x 100 (tests/lazy29.py)
+  for (int e : table_ends) { int k = e >= 0 ? e / 100 : -((-e + 99) / 100); edges.push_back({(u64)(e - 100 * k), k}); }
+  for (const Edge& ed : edges) {
+    host::fe c = {{0, 0, 0, 0}};
+    if (ed.r100 >> 63) {
+      u64 r = ed.r100 & 3;
+      if (r == 1) c.l[0] = 1;
+      if (r == 2) { for (int i = 0; i < 4; i++) c.l[i] = P::N[i]; c.l[0] -= 1; }
+    } else {   // floor(r N / 100): N times r in five words, then long division by 100
+      u64 w[5]; u128 cy = 0;
+      for (int i = 0; i < 4; i++) { u128 t = (u128)P::N[i] * ed.r100 + cy; w[i] = (u64)t; cy = t >> 64; }
+      w[4] = (u64)cy;
+      u128 rem = 0; u64 q[5];
+      for (int i = 4; i >= 0; i--) { u128 cur = (rem << 64) | w[i]; q[i] = (u64)(cur / 100); rem = cur % 100; }
+      CHECK(q[4] == 0);
+      for (int i = 0; i < 4; i++) c.l[i] = q[i];
+    }
+    // V = c + k N as signed 29-bit limbs (limbs 0..7 masked, limb 8 = V >> 232)
+    long long w[6] = {0};
+    __int128 cy = 0;
+    for (int i = 0; i < 4; i++) { __int128 t = (__int128)(u128)c.l[i] + (__int128)ed.k * (__int128)(u128)P::N[i] + cy; w[i] = (long long)(u64)t; cy = t >> 64; }
+    w[4] = (long long)cy; w[5] = cy < 0 ? -1 : 0;
+    int32_t limbs[9];
+    for (int i = 0; i < 8; i++) {
+      int bit = 29 * i, wi = bit >> 6, sh = bit & 63;
+      u128 lo = (u128)(u64)w[wi] | ((u128)(u64)w[wi + 1] << 64);
+      limbs[i] = (int32_t)((u64)(lo >> sh) & ((1u << 29) - 1));
+    }
+    __int128 full = (__int128)(((u128)(u64)w[4] << 64) | (u128)(u64)w[3]);
+    limbs[8] = (int32_t)(long long)(full >> (29 * 8 - 192));
+    host::fe got = reduce_raw29<P>(limbs);
+    for (int i = 0; i < 5; i++) got = F::dbl(got);   // reduce_raw29 returns c / 32
+    CHECK(F::eq(got, c));
+    if (ed.k == 7 && (ed.r100 & 3) == 2) CHECK(limbs[8] > 0);    // 8N - 1 itself
+    if (ed.k == -8 && (ed.r100 & 3) == 1) CHECK(limbs[8] < 0);   // -(8N - 1)
+  }
   // identity record: all-zero limbs convert to the identity point
   std::vector<char> raw(160 * 2, 0);
   host::pt out[2];
