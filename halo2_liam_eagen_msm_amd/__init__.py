@@ -11,4 +11,5 @@ from .api import (  # noqa: F401
     Bases, FixedBases, fixed_plan, Node, comm_unique_id, prepare_scalar_witness, table_entry_by_id, TooManyDigits, RefIndexOutOfBounds,
     RefArithmeticOverflow, ENTRY_DTYPE, SumNotIdentity, compute_divisor_witness, compute_divisor_witness_partial,
     to_curve_x, y_from_x, slope, WouldNotTerminate,
+    RefDivisionByZero, regfn_eval_plan, regular_function_ev, regular_function_ev_unchecked,
 )

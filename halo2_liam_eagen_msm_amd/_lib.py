@@ -59,6 +59,7 @@ SYMBOLS = [
     "lemsm_prepare_scalar_witness_batch", "lemsm_table_entries",
     "lemsm_divisor_witness", "lemsm_divisor_witness_device", "lemsm_divisor_witness_batch", "lemsm_divisor_last_ntt", "lemsm_lhs_witness", "lemsm_lhs_witness_device", "lemsm_lhs_witness_device_range", "lemsm_lhs_witness_last_phases", "lemsm_debug_ntt",
     "lemsm_to_curve_x", "lemsm_y_from_x", "lemsm_slope",
+    "lemsm_regfn_eval_plan", "lemsm_regfn_eval_device", "lemsm_regfn_eval", "lemsm_regfn_eval_last",
 ]
 
 
@@ -174,6 +175,10 @@ def load() -> ctypes.CDLL:
         "lemsm_to_curve_x": (i, [i, u64p, u64p]),
         "lemsm_y_from_x": (i, [i, u64p, u64p, ctypes.POINTER(i)]),
         "lemsm_slope": (i, [i, u64p, u64p]),
+        "lemsm_regfn_eval_plan": (i, [vp, sz, sz, vp, sz, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_regfn_eval_device": (i, [vp, i, vp, sz, vp, sz, u64p, i, vp, sz, u64p, szp]),
+        "lemsm_regfn_eval": (i, [vp, i, u64p, sz, vp, sz, u64p, i, vp, sz, u64p, szp]),
+        "lemsm_regfn_eval_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -86,6 +86,14 @@ class RefArithmeticOverflow(LemsmError, OverflowError):
         self.index = index
 
 
+class RefDivisionByZero(LemsmError, ZeroDivisionError):
+    """reference: `invert().unwrap()` on a zero Z in RegularFunction::ev (src/regular_functions_utils.rs:230)"""
+
+    def __init__(self, status, msg, index):
+        super().__init__(status, msg)
+        self.index = index
+
+
 # one Entry of prepare_scalar_witness (src/negbase_utils.rs:39-43) as the C ABI lays it out: 24 bytes
 ENTRY_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8"), ("mask", "<u4"), ("kind", "<u4")])
 ENTRY_KINDS = ("Scalar", "Bucket", "Limb")
@@ -192,6 +200,10 @@ class Context:
             cls = {_lib.LEMSM_ERR_TOO_MANY_DIGITS: TooManyDigits, _lib.LEMSM_ERR_INDEX_OUT_OF_BOUNDS: RefIndexOutOfBounds,
                    _lib.LEMSM_ERR_ARITH_OVERFLOW: RefArithmeticOverflow}[rc]
             raise cls(rc, msg, bad_index)
+        if rc == _lib.LEMSM_ERR_DIVISION_BY_ZERO:
+            if bad_index is None:
+                bad_index = int(self.lib.lemsm_last_bad_index(self.h))
+            raise RefDivisionByZero(rc, msg, bad_index)
         raise LemsmError(rc, msg)
 
     def set_option(self, name: str, value: int):
@@ -468,6 +480,56 @@ class Context:
         self._check(rc, bad.value)
         return carry, index, out
 
+    # ---- RegularFunction::ev ---------------------------------------------------------------
+    def _regfn_args(self, index, points, counts, jacobian):
+        index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+        pts = _limbs(points, 12 if jacobian else 8) if np.size(points) else np.zeros((0, 12 if jacobian else 8), np.uint64)
+        K = pts.shape[0]
+        cnt = None if counts is None else np.ascontiguousarray(counts, np.uintp).reshape(-1)
+        if cnt is not None and cnt.shape[0] != index.shape[0]:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "one count per function")
+        nvals = K if cnt is not None else index.shape[0] * K
+        return index, pts, K, cnt, np.zeros((nvals, 4), np.uint64)
+
+    def regfn_eval_device(self, curve, d_coeffs: int, cap: int, index, points, counts=None, jacobian: bool = False) -> np.ndarray:
+        """RegularFunction::ev / ev_unchecked (src/regular_functions_utils.rs:228-237) of the functions `index` describes
+        ((T, 4) rows {offset_a, len_a, offset_b, len_b} into the `cap` 32-byte coefficients at device pointer d_coeffs: what
+        lhs_witness_device returns) without the coefficients leaving HBM.  points: (K, 8) affine, taken literally, or
+        (K, 12) Jacobian with jacobian=True.  counts=None: every function at all K points, value (t, k) in row t K + k;
+        counts: function t at its own counts[t] points (lists concatenated), value k in row k.
+        Returns (num_values, 4) raw Montgomery limbs; RefDivisionByZero (with .index) for a Jacobian point with Z == 0."""
+        index, pts, K, cnt, out = self._regfn_args(index, points, counts, jacobian)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_regfn_eval_device(self.h, _curve_id(curve), d_coeffs, cap, _ptr(index) if index.size else None, index.shape[0],
+                                              _ptr(pts) if K else None, int(jacobian), _ptr(cnt) if cnt is not None else None, K,
+                                              _ptr(out) if out.size else None, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out
+
+    def regfn_eval(self, curve, fns, points, counts=None, jacobian: bool = False) -> np.ndarray:
+        """the same for fns = [(a, b), ...] coefficient arrays in host memory, as lhs_witness / divisor_witness_batch return
+        them (extra tuple members are ignored)"""
+        parts, rows, used = [], [], 0
+        for f in fns:
+            a = _limbs(f[0], 4) if np.size(f[0]) else np.zeros((0, 4), np.uint64)
+            b = _limbs(f[1], 4) if np.size(f[1]) else np.zeros((0, 4), np.uint64)
+            rows.append((used, a.shape[0], used + a.shape[0], b.shape[0]))
+            parts += [a, b]; used += a.shape[0] + b.shape[0]
+        coeffs = np.concatenate(parts) if used else np.zeros((0, 4), np.uint64)
+        index, pts, K, cnt, out = self._regfn_args(np.array(rows, np.uintp).reshape(-1, 4), points, counts, jacobian)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_regfn_eval(self.h, _curve_id(curve), _ptr(coeffs) if used else None, used, _ptr(index) if index.size else None,
+                                       index.shape[0], _ptr(pts) if K else None, int(jacobian), _ptr(cnt) if cnt is not None else None, K,
+                                       _ptr(out) if out.size else None, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out
+
+    def regfn_eval_last(self) -> Tuple[float, int, int]:
+        """(device ms, coeff_bytes, field_mults) of the last regfn_eval* call"""
+        ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_regfn_eval_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
+        return ms.value, by.value, fm.value
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -695,6 +757,22 @@ def fixed_plan(curve, n: int, window_bits: int = 0, tables: int = 0) -> dict:
     return {"c": v[0].value, "num_windows": v[1].value, "m": v[2].value, "h": v[3].value, "device_bytes": b.value}
 
 
+def regfn_eval_plan(index, cap: int, K: int, counts=None) -> dict:
+    """{"num_values", "field_mults", "coeff_bytes"} of a regfn_eval request (pure host: lemsm_regfn_eval_plan); raises
+    LemsmError / LengthMismatch where the device entry would"""
+    lib = _lib.load()
+    index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+    cnt = None if counts is None else np.ascontiguousarray(counts, np.uintp).reshape(-1)
+    nv = ctypes.c_size_t(); fm = ctypes.c_uint64(); by = ctypes.c_uint64()
+    rc = lib.lemsm_regfn_eval_plan(_ptr(index) if index.size else None, index.shape[0], cap, _ptr(cnt) if cnt is not None else None, K,
+                                   ctypes.byref(nv), ctypes.byref(fm), ctypes.byref(by))
+    if rc == _lib.LEMSM_ERR_LEN_MISMATCH:
+        raise LengthMismatch(rc, "K is not the sum of counts")
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"num_values": nv.value, "field_mults": fm.value, "coeff_bytes": by.value}
+
+
 def comm_unique_id() -> bytes:
     """rank 0: the 128-byte RCCL unique id every rank passes to Context.comm_init"""
     buf = np.zeros(_lib.LEMSM_COMM_ID_BYTES, np.uint8)
@@ -856,6 +934,19 @@ def compute_divisor_witness_partial(pts_affine, curve="grumpkin", ctx: Optional[
     """src/regular_functions_utils.rs:453-467: ((a, b), output point as affine raw limbs, zeros = identity)"""
     a, b, out = (ctx or default_context()).divisor_witness(curve, pts_affine, False, normalise)
     return (a, b), out
+
+
+def regular_function_ev(fn, pt_jacobian, curve="grumpkin", ctx: Optional[Context] = None) -> np.ndarray:
+    """RegularFunction::ev (src/regular_functions_utils.rs:228-231): fn = (a, b) at a Jacobian point (12 limbs), x = X/Z^2,
+    y = Y/Z^3; 4 raw Montgomery limbs.  RefDivisionByZero where the reference's invert().unwrap() panics (Z == 0)."""
+    return (ctx or default_context()).regfn_eval(curve, [fn], np.asarray(pt_jacobian, np.uint64).reshape(1, 12), None, True)[0]
+
+
+def regular_function_ev_unchecked(fn, x, y, curve="grumpkin", ctx: Optional[Context] = None) -> np.ndarray:
+    """RegularFunction::ev_unchecked (src/regular_functions_utils.rs:233-237): a(x) + y b(x) for field elements x, y (4 raw
+    Montgomery limbs each), no on-curve test; 4 raw Montgomery limbs"""
+    pt = np.concatenate([np.asarray(x, np.uint64).reshape(4), np.asarray(y, np.uint64).reshape(4)]).reshape(1, 8)
+    return (ctx or default_context()).regfn_eval(curve, [fn], pt, None, False)[0]
 
 
 def _neg_affine_raw(curve_id: int, pts: np.ndarray) -> np.ndarray:

@@ -360,6 +360,41 @@ int lemsm_lhs_witness_device_range(lemsm_ctx* ctx, int curve, const void* d_scal
    into the caller's buffer (32 B each over PCIe; pageable memory is paged in by this copy). */
 int lemsm_lhs_witness_last_phases(const lemsm_ctx* ctx, double out_ms[4]);
 
+/* ---- RegularFunction::ev: evaluating divisor witnesses -------------------------------- */
+/* RegularFunction::ev / ev_unchecked (src/regular_functions_utils.rs:228-237; Polynomial::ev :41-43), the one thing the
+   reference does with a witness (its tests :638-671, the argument's challenge points src/config.rs:224-283): for T functions
+   a(x) + y b(x) and a batch of points, ev_unchecked(x, y) = a(x) + y b(x), exact in bn256::Fr; an empty polynomial is 0.
+   Grumpkin only, like the divisor-witness entries.
+   index: T x 4 entries {offset_a, len_a, offset_b, len_b} in 32-byte elements into the coefficient buffer (constant term
+   first) -- the layout lemsm_lhs_witness* and lemsm_divisor_witness_batch write, rows of length (0, 0) included (they
+   evaluate to 0).  points: K x 8 limbs affine, taken literally (no on-curve test; (0,0) gives a[0]), or, jacobian != 0,
+   K x 12 limbs with x = X/Z^2, y = Y/Z^3 (:229-231); Z == 0 is the reference's invert().unwrap() panic (:230):
+   LEMSM_ERR_DIVISION_BY_ZERO, the first such point's index in *bad_index, out_values untouched.
+   counts == NULL: the K points are shared by all functions; value (t, k) is out_values[(t K + k) * 4 ..].
+   counts != NULL: function t has its own counts[t] points, lists concatenated (as lemsm_divisor_witness_batch);
+   K must be sum(counts) (LEMSM_ERR_LEN_MISMATCH); value k belongs to point k.
+   out_values: num_values x 4 raw-Montgomery limbs.  T == 0, K == 0 and functions with no points are allowed. */
+/* Pure host: validates a request and prices it.  num_values = T K (shared points) or K (lists); field_mults =
+   sum_t (len_a + len_b) points_t, the Horner count; coeff_bytes = 32 sum (len_a + len_b) over functions with at least one
+   point, what one pass over the coefficients reads.  LEMSM_ERR_BAD_ARG: a row with offset + len > cap_coeffs (or wrapping).
+   (RegularFunction::ev, :228-237) */
+int lemsm_regfn_eval_plan(const size_t* index, size_t T, size_t cap_coeffs, const size_t* counts, size_t K, size_t* num_values,
+                          uint64_t* field_mults, uint64_t* coeff_bytes);
+/* Coefficients resident in the context's HBM (d_coeffs: cap_coeffs 32-byte elements, e.g. what lemsm_lhs_witness_device
+   left there); index, points, counts and out_values in host memory.  Every coefficient is read from HBM once per tile of
+   four points.  (RegularFunction::ev / ev_unchecked, :228-237) */
+int lemsm_regfn_eval_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                            const uint64_t* points, int jacobian, const size_t* counts, size_t K, uint64_t* out_values,
+                            size_t* bad_index);
+/* The same with the coefficients in host memory (uploaded, then the device path).  (:228-237) */
+int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                     const uint64_t* points, int jacobian, const size_t* counts, size_t K, uint64_t* out_values,
+                     size_t* bad_index);
+/* Device time (ms, HIP events on the context's stream) of the evaluation launches of the last lemsm_regfn_eval* call --
+   power tables, tile kernel, fold -- and the plan's coeff_bytes and field_mults: the figures its HBM and VALU rooflines
+   are priced with (as lemsm_divisor_last_ntt).  (:228-237) */
+int lemsm_regfn_eval_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
