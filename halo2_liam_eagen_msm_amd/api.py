@@ -530,6 +530,106 @@ class Context:
         self._check(self.lib.lemsm_regfn_eval_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- the right-hand side: "rhs main" gate (src/config.rs:504-538) and lookup columns (:402-437) ----
+    def multiples_table_device(self, curve, d_points_affine: int, n: int, base: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """the fixed column of src/config.rs:542-560 left in HBM: n (base-1) rows of 64 B, row j (base-1) + (k-1) = affine
+        k P_j, from n affine rows at device pointer d_points_affine (the values of precompute_multiplicities_affine)"""
+        if not (3 <= base <= 255):
+            raise BadBase(_lib.LEMSM_ERR_BAD_BASE, "base must be in 3..=255")
+        if out is None:
+            out = DeviceBuffer(self, max(n * (base - 1) * 64, 16))
+        assert out.nbytes >= n * (base - 1) * 64
+        self._check(self.lib.lemsm_multiples_table_device(self.h, _curve_id(curve), d_points_affine, n, base, out.ptr))
+        return out
+
+    def _rhs_args(self, base, A, t, init, curve):
+        if not (3 <= base <= 255):
+            raise BadBase(_lib.LEMSM_ERR_BAD_BASE, "base must be in 3..=255")
+        a = np.ascontiguousarray(A, np.uint64).reshape(8)
+        tt = slope(a, curve) if t is None else np.ascontiguousarray(t, np.uint64).reshape(4)
+        ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(base - 1, 4)
+        return a, tt, ini
+
+    def rhs_witness_device(self, curve, d_scalars: int, d_table: int, n: int, base: int, A, t=None, init=None,
+                           out: Optional[DeviceBuffer] = None, want_running: bool = True):
+        """the column of the "rhs main" gate (src/config.rs:504-538) with scalars (n x 32 B) and table (multiples_table_device)
+        resident: (DeviceBuffer of the running sums (n, base-1, 4) or None, totals (base-1, 4), sum (4,)).  A: 8 limbs, t: 4 limbs
+        (None: slope(A), src/config.rs:184-187), init: (base-1, 4) or None = zeros.  RefDivisionByZero / ScalarOutOfRange carry .index."""
+        cid = _curve_id(curve)
+        a, tt, ini = self._rhs_args(base, A, t, init, cid)
+        if want_running and out is None:
+            out = DeviceBuffer(self, max(n * (base - 1) * 32, 16))
+        if want_running:
+            assert out.nbytes >= n * (base - 1) * 32
+        totals = np.zeros((base - 1, 4), np.uint64)
+        total = np.zeros(4, np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_rhs_witness_device(self.h, cid, d_scalars, d_table, n, base, _ptr(a), _ptr(tt), _ptr(ini) if ini is not None else None,
+                                               out.ptr if want_running else None, _ptr(totals), _ptr(total), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return (out if want_running else None), totals, total
+
+    def rhs_witness(self, curve, scalars, pts_jacobian, base: int, A, t=None, init=None, want_running: bool = True):
+        """the same from host memory, the points as the reference holds them ((n, 12) Jacobian, any Z):
+        (running (n, base-1, 4) or None, totals (base-1, 4), sum (4,))"""
+        cid = _curve_id(curve)
+        s = _scalars(scalars)
+        p = _limbs(pts_jacobian, 12) if np.size(pts_jacobian) else np.zeros((0, 12), np.uint64)
+        if s.shape[0] != p.shape[0]:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "incompatible amount of coefficients")
+        a, tt, ini = self._rhs_args(base, A, t, init, cid)
+        n = s.shape[0]
+        running = np.zeros((n, base - 1, 4), np.uint64) if want_running else None
+        totals = np.zeros((base - 1, 4), np.uint64)
+        total = np.zeros(4, np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_rhs_witness(self.h, cid, _ptr(s) if n else None, _ptr(p) if n else None, n, base, _ptr(a), _ptr(tt),
+                                        _ptr(ini) if ini is not None else None, _ptr(running) if want_running and n else None,
+                                        _ptr(totals), _ptr(total), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return running, totals, total
+
+    def fraction_sums_device(self, curve, d_num: Optional[int], d_den: int, n: int, chains: int = 1, init=None,
+                             out: Optional[DeviceBuffer] = None, want_running: bool = True):
+        """out[i] = (i < chains ? init[i] : out[i - chains]) + num[i] / den[i] on n resident field elements (d_num None: 1): the
+        running sums of the lookup columns (src/config.rs:402-437).  (DeviceBuffer (n, 4) or None, totals (chains, 4))"""
+        if chains < 1:
+            raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "chains must be >= 1")
+        ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(chains, 4)
+        if want_running and out is None:
+            out = DeviceBuffer(self, max(n * 32, 16))
+        totals = np.zeros((chains, 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_fraction_sums_device(self.h, _curve_id(curve), d_num, d_den, n, chains, _ptr(ini) if ini is not None else None,
+                                                 out.ptr if want_running else None, _ptr(totals), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return (out if want_running else None), totals
+
+    def fraction_sums(self, curve, num, den, chains: int = 1, init=None, want_running: bool = True):
+        """the same from host memory: num (n, 4) or None, den (n, 4); (running (n, 4) or None, totals (chains, 4))"""
+        if chains < 1:
+            raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "chains must be >= 1")
+        dn = _limbs(den, 4) if np.size(den) else np.zeros((0, 4), np.uint64)
+        nm = None if num is None else (_limbs(num, 4) if np.size(num) else np.zeros((0, 4), np.uint64))
+        n = dn.shape[0]
+        if nm is not None and nm.shape[0] != n:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "one numerator per denominator")
+        ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(chains, 4)
+        running = np.zeros((n, 4), np.uint64) if want_running else None
+        totals = np.zeros((chains, 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_fraction_sums(self.h, _curve_id(curve), _ptr(nm) if nm is not None and n else None, _ptr(dn) if n else None, n, chains,
+                                          _ptr(ini) if ini is not None else None, _ptr(running) if want_running and n else None, _ptr(totals),
+                                          ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return running, totals
+
+    def rhs_last(self) -> Tuple[float, int, int]:
+        """(device ms, bytes, field_mults) of the last rhs_witness* / fraction_sums* call"""
+        ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_rhs_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
+        return ms.value, by.value, fm.value
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -773,6 +873,20 @@ def regfn_eval_plan(index, cap: int, K: int, counts=None) -> dict:
     return {"num_values": nv.value, "field_mults": fm.value, "coeff_bytes": by.value}
 
 
+def rhs_plan(curve, base: int, n: int) -> dict:
+    """{"num_terms", "table_bytes", "out_bytes", "field_mults"} of an rhs_witness call (pure host: lemsm_rhs_plan)"""
+    lib = _lib.load()
+    nt = ctypes.c_size_t(); tb = ctypes.c_uint64(); ob = ctypes.c_uint64(); fm = ctypes.c_uint64()
+    if not (0 <= base <= 255):
+        raise BadBase(_lib.LEMSM_ERR_BAD_BASE, "base must be in 3..=255")
+    rc = lib.lemsm_rhs_plan(_curve_id(curve), base, n, ctypes.byref(nt), ctypes.byref(tb), ctypes.byref(ob), ctypes.byref(fm))
+    if rc == _lib.LEMSM_ERR_BAD_BASE:
+        raise BadBase(rc, "base must be in 3..=255")
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"num_terms": nt.value, "table_bytes": tb.value, "out_bytes": ob.value, "field_mults": fm.value}
+
+
 def comm_unique_id() -> bytes:
     """rank 0: the 128-byte RCCL unique id every rank passes to Context.comm_init"""
     buf = np.zeros(_lib.LEMSM_COMM_ID_BYTES, np.uint8)
@@ -921,6 +1035,13 @@ def compute_lhs_witness(scalars, pts, base: int, curve="grumpkin", ctx: Optional
     (linefunc takes whatever projective representative a point has); normalise=True returns the representative whose
     coefficient of highest pole order is 1."""
     return (ctx or default_context()).lhs_witness(curve, scalars, pts, base, normalise)
+
+
+def compute_rhs_witness(scalars, pts, base: int, A, t=None, curve="grumpkin", ctx: Optional[Context] = None, init=None):
+    """The advice cells of column c that the reference's "rhs main" gate fixes (src/config.rs:504-538; its synthesize is a
+    stub): (running (n, base-1, 4), totals (base-1, 4), sum (4,)) for scalars (n, 32), Jacobian pts (n, 12), the challenge
+    point A (8 limbs) and t (4 limbs; None: the tangent slope at A, src/config.rs:184-187)."""
+    return (ctx or default_context()).rhs_witness(curve, scalars, pts, base, A, t, init)
 
 
 def compute_divisor_witness(pts_affine, curve="grumpkin", ctx: Optional[Context] = None, normalise: bool = True):

@@ -22,6 +22,7 @@
 #include "roctx_dyn.hpp"
 #include "divisor.cuh"
 #include "regfn_eval.cuh"
+#include "rhs.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -108,6 +109,8 @@ struct lemsm_ctx {
   double dw_ntt_ms = 0; u64 dw_ntt_bytes = 0, dw_ntt_bflies = 0; u32 dw_reuse_levels = 0;
   DevBuf rf_coef, rf_ws;             // regular-function evaluation: staged coefficients (host entry), tables / partials / values
   double rf_ms = 0; u64 rf_bytes = 0, rf_mults = 0;   // lemsm_regfn_eval_last
+  DevBuf rhs_ws, rhs_tab, rhs_pw;    // rhs witness / fraction sums: engine workspace, table + staged columns (host entries), powers of -base
+  double rhs_ms = 0; u64 rhs_bytes = 0, rhs_mults = 0;   // lemsm_rhs_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
   int plan_world = 1;   // ranks sharing the current call's windows: > 1 pins 16-bit windows (16 split evenly over 2/4/8 ranks, 15 do not)
@@ -1720,7 +1723,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);
@@ -2640,3 +2643,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "divisor_abi.inc"
 #include "fixed_base.inc"
 #include "regfn_abi.inc"
+#include "rhs_abi.inc"

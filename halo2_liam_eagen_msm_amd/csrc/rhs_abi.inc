@@ -1,0 +1,308 @@
+// The right-hand side of the argument (include/lemsm.h: lemsm_rhs_*, lemsm_multiples_table_device, lemsm_fraction_sums*):
+// the running sums of the reference's "rhs main" gate (src/config.rs:504-538) and of its lookup columns (:402-437).
+// Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, stage, HIPCHK, fail, align_up, make_lhs_plan,
+// bound_of, k_precompute_mult_affine); the kernels are rhs.cuh's.
+
+namespace {
+
+namespace fs = lemsm::rhs;
+
+// geometry of one engine call over N terms in `chains` chains: pure host, shared by the plan entry and the launches
+struct FsGeom {
+  u64 N = 0, chains = 1, rows = 0, S = 1, nseg = 0, nblk = 0, R = 0, nthreads_inv = 0;
+  u32 rk = 1;
+};
+FsGeom fs_geom(u64 N, u64 chains) {
+  FsGeom g;
+  g.N = N; g.chains = chains;
+  g.rows = (N + chains - 1) / chains;
+  g.S = std::max<u64>(32, (g.rows + 32767) / 32768);             // rows per segment: at most 32768 segments per column
+  g.nseg = (g.rows + g.S - 1) / g.S;
+  g.nblk = (N + fs::FS_TILE - 1) / fs::FS_TILE;
+  g.R = g.nblk * 256;                                            // roots: one per thread of k_fs_prefix
+  g.rk = (u32)std::min<u64>(fs::FS_RK, std::max<u64>(1, g.R >> 10));   // a short call is latency, not work
+  g.nthreads_inv = (g.R + g.rk - 1) / g.rk;
+  return g;
+}
+// field multiplications of the shipped kernels for one call: per term the source's own (rhs: bucket conversion, t x,
+// bucket (x - Ax) = 3; arrays: 0), 1 in k_fs_prefix and 3 in k_fs_apply; per root 3 in k_fs_rootinv; per thread of
+// k_fs_rootinv one inversion counted as FS_INV_MULTS = 384 products
+u64 fs_mults(const FsGeom& g, u32 src_mults) { return g.N * (u64)(src_mults + 4) + 3 * g.R + (u64)fs::FS_INV_MULTS * g.nthreads_inv; }
+
+size_t fs_ws_bytes(const FsGeom& g) {
+  return 3 * align_up(g.N * 32, 256) + 2 * align_up(g.R * 32, 256) + align_up(g.nseg * g.chains * 32, 256) + 2 * align_up(g.chains * 32, 256) + 256;
+}
+
+// the engine: terms from `src`, running sums into d_out (may be null), totals (chains x 4 limbs) to the host.
+// On return *err_den / *err_range hold the lowest offending indices (~0: none).
+template <class F, class Src>
+int fs_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const uint64_t* init, void* d_out, uint64_t* out_totals, u64* err_den, u64* err_range) {
+  hipStream_t st = ctx->stream;
+  int rc = reserve(ctx, ctx->rhs_ws, fs_ws_bytes(g)); if (rc) return rc;
+  char* w = (char*)ctx->rhs_ws.p;
+  uint4* bufN = (uint4*)w; w += align_up(g.N * 32, 256);
+  uint4* bufD = (uint4*)w; w += align_up(g.N * 32, 256);
+  uint4* bufP = (uint4*)w; w += align_up(g.N * 32, 256);
+  uint4* roots = (uint4*)w; w += align_up(g.R * 32, 256);
+  uint4* rpre = (uint4*)w; w += align_up(g.R * 32, 256);
+  uint4* segsum = (uint4*)w; w += align_up(g.nseg * g.chains * 32, 256);
+  uint4* d_init = (uint4*)w; w += align_up(g.chains * 32, 256);
+  uint4* d_tot = (uint4*)w; w += align_up(g.chains * 32, 256);
+  fs::ErrWord* d_err = (fs::ErrWord*)w;
+  if (init) HIPCHK(ctx, hipMemcpyAsync(d_init, init, g.chains * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemsetAsync(d_err, 0xff, 16, st));
+  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
+  const u64 nsc = g.nseg * g.chains;
+  hipLaunchKernelGGL((fs::k_fs_prefix<F, Src>), dim3((u32)g.nblk), dim3(256), 0, st, src, g.N, bufN, bufD, bufP, roots, d_err);
+  hipLaunchKernelGGL((fs::k_fs_rootinv<F>), dim3((u32)((g.nthreads_inv + 255) / 256)), dim3(256), 0, st, roots, rpre, g.R, g.rk);
+  hipLaunchKernelGGL((fs::k_fs_apply<F>), dim3((u32)g.nblk), dim3(256), 0, st, g.N, bufN, (const uint4*)bufD, (const uint4*)bufP, (const uint4*)roots);
+  hipLaunchKernelGGL((fs::k_fs_segsum<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, segsum);
+  hipLaunchKernelGGL((fs::k_fs_segscan<F>), dim3((u32)g.chains), dim3(256), 0, st, segsum, g.chains, g.nseg, init ? (const uint4*)d_init : (const uint4*)nullptr, d_tot);
+  if (d_out)
+    hipLaunchKernelGGL((fs::k_fs_finish<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, (const uint4*)segsum, (uint4*)d_out);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+  u64 errw[2] = {~0ull, ~0ull};
+  HIPCHK(ctx, hipMemcpyAsync(errw, d_err, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipMemcpyAsync(out_totals, d_tot, g.chains * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->rhs_ms = ms;
+  *err_den = errw[0]; *err_range = errw[1];
+  return LEMSM_OK;
+}
+
+int fs_div_by_zero(lemsm_ctx* ctx, u64 index, size_t* bad_index, const char* what) {
+  if (bad_index) *bad_index = (size_t)index;
+  ctx->bad_index = (size_t)index;
+  return fail(ctx, LEMSM_ERR_DIVISION_BY_ZERO, what);
+}
+
+void fs_totals_of_init(const uint64_t* init, size_t chains, uint64_t* out_totals) {
+  if (init) memcpy(out_totals, init, chains * 32); else memset(out_totals, 0, chains * 32);
+}
+
+struct RhsPlan { size_t num_terms = 0; u64 table_bytes = 0, out_bytes = 0, field_mults = 0; u32 d = 0; };
+int rhs_plan(int curve, uint8_t base, size_t n, RhsPlan& p) {
+  if (curve != LEMSM_BN254_G1 && curve != LEMSM_GRUMPKIN) return LEMSM_ERR_BAD_CURVE;
+  LhsPlan lp;
+  if (make_lhs_plan(curve, base, lp)) return LEMSM_ERR_BAD_BASE;
+  const size_t nb = (size_t)base - 1;
+  if (n > ((size_t)-1 / 64) / nb) return LEMSM_ERR_BAD_ARG;       // 64 n (base - 1) must fit size_t
+  p.num_terms = n * nb; p.table_bytes = 64 * (u64)p.num_terms; p.out_bytes = 32 * (u64)p.num_terms; p.d = lp.d;
+  p.field_mults = p.num_terms ? fs_mults(fs_geom(p.num_terms, nb), 3) : 0;
+  return LEMSM_OK;
+}
+
+// (-base)^i, i < d, as 160-bit two's complement integers (5 words each)
+void rhs_power_table(u32 base, u32 d, std::vector<u32>& pw) {
+  pw.assign((size_t)5 * d, 0);
+  u32 mag[5] = {1, 0, 0, 0, 0};
+  for (u32 i = 0; i < d; i++) {
+    u32* o = &pw[(size_t)5 * i];
+    if (i & 1) { u64 cy = 1; for (int l = 0; l < 5; l++) { u64 v = (u64)(u32)~mag[l] + cy; o[l] = (u32)v; cy = v >> 32; } }
+    else for (int l = 0; l < 5; l++) o[l] = mag[l];
+    u64 cy = 0;
+    for (int l = 0; l < 5; l++) { u64 v = (u64)mag[l] * base + cy; mag[l] = (u32)v; cy = v >> 32; }
+  }
+}
+
+template <class F, class P, class P64>
+int rhs_device_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, const RhsPlan& pl, uint8_t base, const uint64_t a_xy[8],
+                 const uint64_t t[4], const uint64_t* init, void* d_out_running, uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index) {
+  typedef host::HF<P64> HF;
+  const size_t nb = (size_t)base - 1;
+  const FsGeom g = fs_geom(pl.num_terms, nb);
+  std::vector<u32> pw; rhs_power_table(base, pl.d, pw);
+  int rc = reserve(ctx, ctx->rhs_pw, pw.size() * 4 + 256); if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rhs_pw.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  fs::RhsSrc<F, P> src;
+  src.scalars = (const uint4*)d_scalars; src.table = (const uint4*)d_table; src.pw = (const u32*)ctx->rhs_pw.p;
+  src.nb = (u32)nb; src.base = base; src.d = pl.d;
+  host::fe ax, ay, tt; memcpy(ax.l, a_xy, 32); memcpy(ay.l, a_xy + 4, 32); memcpy(tt.l, t, 32);
+  const host::fe f = HF::sub(HF::mul(tt, ax), ay);                // f = t Ax - Ay (src/config.rs:519)
+  memcpy(src.c.ax, ax.l, 32); memcpy(src.c.t, tt.l, 32); memcpy(src.c.f, f.l, 32); memcpy(src.c.bound, bound_of(curve), 32);
+  std::vector<uint64_t> totals_tmp;
+  uint64_t* totals = out_totals;
+  if (!totals) { totals_tmp.resize(nb * 4); totals = totals_tmp.data(); }
+  u64 err_den = ~0ull, err_range = ~0ull;
+  rc = fs_run<F>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range); if (rc) return rc;   // (pw stays valid: the call has synchronised)
+  if (err_range != ~0ull) {
+    if (bad_index) *bad_index = (size_t)err_range;
+    ctx->bad_index = (size_t)err_range;
+    return fail(ctx, LEMSM_ERR_SCALAR_OUT_OF_RANGE, "scalar out of range (>= isqrt(order)+2)");
+  }
+  if (err_den != ~0ull) return fs_div_by_zero(ctx, err_den, bad_index, "rhs witness: a multiple k P_j with a non-zero bucket lies on the line through A (k P_j in {A, -2A}): the gate of src/config.rs:524 has no solution");
+  if (out_sum) {
+    host::fe s = HF::zero();
+    for (size_t k = 0; k < nb; k++) { host::fe v; memcpy(v.l, totals + 4 * k, 32); s = HF::add(s, v); }
+    memcpy(out_sum, s.l, 32);
+  }
+  return LEMSM_OK;
+}
+
+template <class P64>
+void fs_sum_host(const uint64_t* totals, size_t chains, uint64_t out_sum[4]) {
+  typedef host::HF<P64> HF;
+  host::fe s = HF::zero();
+  for (size_t k = 0; k < chains; k++) { host::fe v; memcpy(v.l, totals + 4 * k, 32); s = HF::add(s, v); }
+  memcpy(out_sum, s.l, 32);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lemsm_rhs_plan(int curve, uint8_t base, size_t n, size_t* num_terms, uint64_t* table_bytes, uint64_t* out_bytes, uint64_t* field_mults) {
+  RhsPlan p;
+  int rc = rhs_plan(curve, base, n, p); if (rc) return rc;
+  if (num_terms) *num_terms = p.num_terms;
+  if (table_bytes) *table_bytes = p.table_bytes;
+  if (out_bytes) *out_bytes = p.out_bytes;
+  if (field_mults) *field_mults = p.field_mults;
+  return LEMSM_OK;
+}
+
+int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points_affine, size_t n, uint8_t base, void* d_out_table) {
+  if (!ctx) return LEMSM_ERR_BAD_ARG;
+  RhsPlan pl;
+  int rc = rhs_plan(curve, base, n, pl);
+  if (rc) return fail(ctx, rc, rc == LEMSM_ERR_BAD_BASE ? "base must be >= 3" : rc == LEMSM_ERR_BAD_CURVE ? "unknown curve id" : "n (base - 1) too large");
+  if (n == 0) return LEMSM_OK;
+  if (!d_points_affine || !d_out_table) return LEMSM_ERR_BAD_ARG;
+  if (n >= ((size_t)1 << 28)) return fail(ctx, LEMSM_ERR_BAD_ARG, "n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t in_bytes = align_up(n * 96, 256), scr_bytes = pl.num_terms * 160;   // k_precompute_mult_affine: 160 B of scratch per multiple
+  rc = reserve(ctx, ctx->ws, in_bytes + scr_bytes + 256); if (rc) return rc;
+  char* b = (char*)ctx->ws.p;
+  const dim3 grid((u32)((n + 255) / 256)), blk(256);
+  if (curve == LEMSM_BN254_G1) {
+    hipLaunchKernelGGL((fs::k_affine_to_jacobian<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
+    hipLaunchKernelGGL((k_precompute_mult_affine<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
+  } else {
+    hipLaunchKernelGGL((fs::k_affine_to_jacobian<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
+    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return LEMSM_OK;
+}
+
+int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, size_t n, uint8_t base,
+                             const uint64_t a_xy[8], const uint64_t t[4], const uint64_t* init, void* d_out_running,
+                             uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index) {
+  if (!ctx) return LEMSM_ERR_BAD_ARG;
+  RhsPlan pl;
+  int rc = rhs_plan(curve, base, n, pl);
+  if (rc) return fail(ctx, rc, rc == LEMSM_ERR_BAD_BASE ? "base must be >= 3" : rc == LEMSM_ERR_BAD_CURVE ? "unknown curve id" : "n (base - 1) too large");
+  if (!a_xy || !t) return LEMSM_ERR_BAD_ARG;
+  const size_t nb = (size_t)base - 1;
+  ctx->rhs_ms = 0; ctx->rhs_bytes = pl.table_bytes + (d_out_running ? pl.out_bytes : 0); ctx->rhs_mults = pl.field_mults;
+  if (n == 0) {
+    std::vector<uint64_t> tot(nb * 4);
+    fs_totals_of_init(init, nb, tot.data());
+    if (out_totals) memcpy(out_totals, tot.data(), nb * 32);
+    if (out_sum) { if (curve == LEMSM_BN254_G1) fs_sum_host<host::FqParams64>(tot.data(), nb, out_sum); else fs_sum_host<host::FrParams64>(tot.data(), nb, out_sum); }
+    return LEMSM_OK;
+  }
+  if (!d_scalars || !d_table) return LEMSM_ERR_BAD_ARG;
+  if (n >= ((size_t)1 << 28)) return fail(ctx, LEMSM_ERR_BAD_ARG, "n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (curve == LEMSM_BN254_G1)
+    return rhs_device_t<FqDev, FqParams, host::FqParams64>(ctx, curve, d_scalars, d_table, pl, base, a_xy, t, init, d_out_running, out_totals, out_sum, bad_index);
+  return rhs_device_t<FrDev, FrParams, host::FrParams64>(ctx, curve, d_scalars, d_table, pl, base, a_xy, t, init, d_out_running, out_totals, out_sum, bad_index);
+}
+
+int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n, uint8_t base,
+                      const uint64_t a_xy[8], const uint64_t t[4], const uint64_t* init, uint64_t* out_running,
+                      uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index) {
+  if (!ctx || (n && (!scalars || !pts_jacobian))) return LEMSM_ERR_BAD_ARG;
+  RhsPlan pl;
+  int rc = rhs_plan(curve, base, n, pl);
+  if (rc) return fail(ctx, rc, rc == LEMSM_ERR_BAD_BASE ? "base must be >= 3" : rc == LEMSM_ERR_BAD_CURVE ? "unknown curve id" : "n (base - 1) too large");
+  if (n == 0) return lemsm_rhs_witness_device(ctx, curve, nullptr, nullptr, 0, base, a_xy, t, init, nullptr, out_totals, out_sum, bad_index);
+  if (n >= ((size_t)1 << 28)) return fail(ctx, LEMSM_ERR_BAD_ARG, "n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = stage(ctx, ctx->in_s, scalars, n * 32); if (rc) return rc;
+  rc = stage(ctx, ctx->in_aux, pts_jacobian, n * 96); if (rc) return rc;
+  const size_t tab_bytes = align_up(pl.num_terms * 64, 256);
+  rc = reserve(ctx, ctx->rhs_tab, tab_bytes + (out_running ? pl.num_terms * 32 : 0) + 256); if (rc) return rc;
+  rc = reserve(ctx, ctx->ws, pl.num_terms * 160 + 256); if (rc) return rc;
+  char* tab = (char*)ctx->rhs_tab.p;
+  char* d_run = out_running ? tab + tab_bytes : nullptr;
+  const dim3 grid((u32)((n + 255) / 256)), blk(256);
+  if (curve == LEMSM_BN254_G1)
+    hipLaunchKernelGGL((k_precompute_mult_affine<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
+  else
+    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
+  HIPCHK(ctx, hipGetLastError());
+  rc = lemsm_rhs_witness_device(ctx, curve, ctx->in_s.p, tab, n, base, a_xy, t, init, d_run, out_totals, out_sum, bad_index);
+  if (rc) return rc;
+  if (out_running) {
+    HIPCHK(ctx, hipMemcpyAsync(out_running, d_run, pl.num_terms * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return LEMSM_OK;
+}
+
+int lemsm_fraction_sums_device(lemsm_ctx* ctx, int curve, const void* d_num, const void* d_den, size_t n, size_t chains,
+                               const uint64_t* init, void* d_out_running, uint64_t* out_totals, size_t* bad_index) {
+  if (!ctx) return LEMSM_ERR_BAD_ARG;
+  int rc = check_curve(ctx, curve); if (rc) return rc;
+  if (chains == 0) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: chains must be >= 1");
+  if (n > (size_t)-1 / 64 || chains > (size_t)-1 / 64 || chains >= ((size_t)1 << 31)) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n or chains too large");
+  ctx->rhs_ms = 0; ctx->rhs_bytes = 32 * (u64)n * ((d_num ? 2 : 1) + (d_out_running ? 1 : 0));
+  ctx->rhs_mults = n ? fs_mults(fs_geom(n, chains), 0) : 0;
+  if (n == 0) { if (out_totals) fs_totals_of_init(init, chains, out_totals); return LEMSM_OK; }
+  if (!d_den) return LEMSM_ERR_BAD_ARG;
+  if (n >= ((size_t)1 << 40)) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const FsGeom g = fs_geom(n, chains);
+  std::vector<uint64_t> totals_tmp;
+  uint64_t* totals = out_totals;
+  if (!totals) { totals_tmp.resize(chains * 4); totals = totals_tmp.data(); }
+  u64 err_den = ~0ull, err_range = ~0ull;
+  if (curve == LEMSM_BN254_G1) {
+    fs::ArraySrc<FqDev> src; src.num = (const uint4*)d_num; src.den = (const uint4*)d_den;
+    rc = fs_run<FqDev>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range);
+  } else {
+    fs::ArraySrc<FrDev> src; src.num = (const uint4*)d_num; src.den = (const uint4*)d_den;
+    rc = fs_run<FrDev>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range);
+  }
+  if (rc) return rc;
+  if (err_den != ~0ull) return fs_div_by_zero(ctx, err_den, bad_index, "fraction sums: a zero denominator under a non-zero numerator (the lookup gate of src/config.rs:402-437 has no solution)");
+  return LEMSM_OK;
+}
+
+int lemsm_fraction_sums(lemsm_ctx* ctx, int curve, const uint64_t* num, const uint64_t* den, size_t n, size_t chains,
+                        const uint64_t* init, uint64_t* out_running, uint64_t* out_totals, size_t* bad_index) {
+  if (!ctx || (n && !den)) return LEMSM_ERR_BAD_ARG;
+  int rc = check_curve(ctx, curve); if (rc) return rc;
+  if (chains == 0) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: chains must be >= 1");
+  if (n == 0) return lemsm_fraction_sums_device(ctx, curve, nullptr, nullptr, 0, chains, init, nullptr, out_totals, bad_index);
+  if (n > (size_t)-1 / 128) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t col = align_up(n * 32, 256);
+  rc = reserve(ctx, ctx->rhs_tab, 3 * col + 256); if (rc) return rc;
+  char* b = (char*)ctx->rhs_tab.p;
+  char* d_num = num ? b : nullptr; char* d_den = b + col; char* d_run = out_running ? b + 2 * col : nullptr;
+  if (num) HIPCHK(ctx, hipMemcpyAsync(d_num, num, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_den, den, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  rc = lemsm_fraction_sums_device(ctx, curve, d_num, d_den, n, chains, init, d_run, out_totals, bad_index);
+  if (rc) return rc;
+  if (out_running) {
+    HIPCHK(ctx, hipMemcpyAsync(out_running, d_run, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return LEMSM_OK;
+}
+
+int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) {
+  if (!ctx) return LEMSM_ERR_BAD_ARG;
+  if (ms) *ms = ctx->rhs_ms;
+  if (bytes) *bytes = ctx->rhs_bytes;
+  if (field_mults) *field_mults = ctx->rhs_mults;
+  return LEMSM_OK;
+}
+
+}  // extern "C"

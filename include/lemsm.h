@@ -395,6 +395,62 @@ int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t c
    are priced with (as lemsm_divisor_last_ntt).  (:228-237) */
 int lemsm_regfn_eval_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults);
 
+/* ---- the right-hand side: bucket-weighted line sums ("rhs main" gate, src/config.rs:504-538) ---- */
+/* The cells the reference's "rhs main" gate fixes down column c (src/config.rs:504-538; synthesize is a stub upstream,
+   :635-683): for n scalars / points, base - 1 chains, one per non-zero digit value k, each stepping one scalar at a time
+   (Rotation(-sc_box_size), :507):
+     running[j][k-1] = init[k-1] + sum_{j' <= j} term(j', k),
+     term(j, k) = - bucket[j][k] (Ax - x) / (y - t x + f),  f = t Ax - Ay  (:519-524),  (x, y) = k P_j (the fixed column of :542-560),
+     bucket[j][k] = sum over the digit positions i < d with digit_{j,i} == k of (-base)^i, reduced into the field
+   (Entry::Bucket of row k, src/negbase_utils.rs:97,115, taken from the digits themselves: no i128 overflow), digits =
+   the negabase digits of scalar j, LSB first, d = lemsm_num_digits, padded as src/argument_witness_calc.rs:99.
+   All field elements are raw Montgomery limbs of the BASE field of `curve`; term index = j (base - 1) + (k - 1).
+   A term whose bucket is zero is zero whatever its denominator.  A zero denominator under a non-zero bucket (k P_j in
+   {A, -2A}: the gate has no solution) is LEMSM_ERR_DIVISION_BY_ZERO with the first such term's index in *bad_index; a scalar
+   >= isqrt(order) + 2 (:97) is LEMSM_ERR_SCALAR_OUT_OF_RANGE with its index in *bad_index.  On an error status nothing but
+   *bad_index is defined.  A = (Ax, Ay) need not lie on the curve and t need not be its tangent slope (lemsm_slope,
+   src/config.rs:184-187).  Both curves, base 3..255, n = 0 allowed (totals = init). */
+/* Pure host: validates (curve, base >= 3: LEMSM_ERR_BAD_BASE) and prices a call: num_terms = n (base - 1); table_bytes = 64 num_terms;
+   out_bytes = 32 num_terms; field_mults = the field multiplications of the shipped kernels per call: with T = num_terms,
+   R = 256 ceil(T / 4096) (one root per thread of the batched inversion) and rk = min(32, max(1, R / 1024)) roots per inverting
+   thread, 7 T + 3 R + 384 ceil(R / rk) -- per term 3 for the term itself (bucket into Montgomery form, t x, bucket (x - Ax)), 1 for
+   the prefix product, 3 to apply the inverse; 3 per root; 384 for a Fermat inversion.  size_t overflow of 64 n (base - 1):
+   LEMSM_ERR_BAD_ARG.  (src/config.rs:504-538) */
+int lemsm_rhs_plan(int curve, uint8_t base, size_t n, size_t* num_terms, uint64_t* table_bytes, uint64_t* out_bytes, uint64_t* field_mults);
+/* The fixed column of src/config.rs:542-560 left in HBM: d_out_table = n (base - 1) rows of 64 B, row j (base - 1) + (k - 1) =
+   affine k P_j, bit-identical to what lemsm_precompute_multiplicities_affine returns for the same points (d_points_affine:
+   n x 64 B affine rows, read as Jacobian with Z = 1; an all-zero row is the identity). */
+int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points_affine, size_t n, uint8_t base, void* d_out_table);
+/* Scalars (n x 32 B) and table (as above; rows are taken literally, no on-curve test) resident in HBM; d_out_running
+   (n (base - 1) x 32 B, row-major [j][k-1]) stays in HBM and may be NULL: totals only, no cell is written.  a_xy: 8 limbs, t: 4 limbs,
+   init: (base - 1) x 4 limbs or NULL = zeros.  out_totals ((base - 1) x 4, optional) = running[n-1][.]; out_sum (optional) = their
+   sum, the double sum of the argument's right-hand side with the gate's sign.  (src/config.rs:504-538) */
+int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, size_t n, uint8_t base,
+                             const uint64_t a_xy[8], const uint64_t t[4], const uint64_t* init, void* d_out_running,
+                             uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index);
+/* Host pointers, the points as the reference holds them (n x 12 limbs Jacobian, any Z; src/argument_witness_calc.rs:43-51):
+   builds the table on the device, runs the device path, downloads the running sums when out_running != NULL.
+   (src/config.rs:504-538, :542-560) */
+int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n, uint8_t base,
+                      const uint64_t a_xy[8], const uint64_t t[4], const uint64_t* init, uint64_t* out_running,
+                      uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index);
+/* The engine on its own, for the log-derivative lookup columns (src/config.rs:402-437: c[i+1] - c[i] = 1 / (v - b[i+1])):
+   out[i] = (i < chains ? init[i] : out[i - chains]) + num[i] / den[i] over n field elements of the BASE field of `curve`.
+   d_num == NULL means every numerator is 1.  num = 0 gives 0 whatever den; den = 0 otherwise: LEMSM_ERR_DIVISION_BY_ZERO with the
+   first such index in *bad_index.  chains >= 1 (0: LEMSM_ERR_BAD_ARG), n arbitrary (also n < chains); init: chains x 4 limbs or
+   NULL = zeros; d_out_running (n x 32 B) may be NULL; out_totals: chains x 4, the last cell of each chain (init where a
+   chain is empty). */
+int lemsm_fraction_sums_device(lemsm_ctx* ctx, int curve, const void* d_num, const void* d_den, size_t n, size_t chains,
+                               const uint64_t* init, void* d_out_running, uint64_t* out_totals, size_t* bad_index);
+/* The same with num (may be NULL), den and out_running (may be NULL) in host memory.  (src/config.rs:402-437) */
+int lemsm_fraction_sums(lemsm_ctx* ctx, int curve, const uint64_t* num, const uint64_t* den, size_t n, size_t chains,
+                        const uint64_t* init, uint64_t* out_running, uint64_t* out_totals, size_t* bad_index);
+/* Device time (ms, HIP events around the launches on the context's stream) of the last lemsm_rhs_witness* /
+   lemsm_fraction_sums* call and the bytes / field_mults its plan prices it with (rhs: table_bytes, plus out_bytes when
+   the running sums were written; fractions: 32 B per element read and written, 4 n + 3 R + 384 ceil(R / rk) products).
+   (src/config.rs:504-538, :402-437) */
+int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
