@@ -12,4 +12,5 @@ from .api import (  # noqa: F401
     RefArithmeticOverflow, ENTRY_DTYPE, SumNotIdentity, compute_divisor_witness, compute_divisor_witness_partial,
     to_curve_x, y_from_x, slope, WouldNotTerminate,
     RefDivisionByZero, regfn_eval_plan, regular_function_ev, regular_function_ev_unchecked,
+    regfn_logderiv_plan, argument_residual, compute_lhs_logderiv,
 )

@@ -60,6 +60,8 @@ SYMBOLS = [
     "lemsm_divisor_witness", "lemsm_divisor_witness_device", "lemsm_divisor_witness_batch", "lemsm_divisor_last_ntt", "lemsm_lhs_witness", "lemsm_lhs_witness_device", "lemsm_lhs_witness_device_range", "lemsm_lhs_witness_last_phases", "lemsm_debug_ntt",
     "lemsm_to_curve_x", "lemsm_y_from_x", "lemsm_slope",
     "lemsm_regfn_eval_plan", "lemsm_regfn_eval_device", "lemsm_regfn_eval", "lemsm_regfn_eval_last",
+    "lemsm_regfn_logderiv_plan", "lemsm_regfn_logderiv_device", "lemsm_regfn_logderiv", "lemsm_regfn_logderiv_last",
+    "lemsm_debug_regfn_deriv", "lemsm_argument_residual",
     "lemsm_rhs_plan", "lemsm_multiples_table_device", "lemsm_rhs_witness_device", "lemsm_rhs_witness",
     "lemsm_fraction_sums_device", "lemsm_fraction_sums", "lemsm_rhs_last",
 ]
@@ -181,6 +183,12 @@ def load() -> ctypes.CDLL:
         "lemsm_regfn_eval_device": (i, [vp, i, vp, sz, vp, sz, u64p, i, vp, sz, u64p, szp]),
         "lemsm_regfn_eval": (i, [vp, i, u64p, sz, vp, sz, u64p, i, vp, sz, u64p, szp]),
         "lemsm_regfn_eval_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_regfn_logderiv_plan": (i, [vp, sz, sz, sz, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_regfn_logderiv_device": (i, [vp, i, vp, sz, vp, sz, u64p, sz, ctypes.c_uint8, u64p, u64p, u64p, szp]),
+        "lemsm_regfn_logderiv": (i, [vp, i, u64p, sz, vp, sz, u64p, sz, ctypes.c_uint8, u64p, u64p, u64p, szp]),
+        "lemsm_regfn_logderiv_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_debug_regfn_deriv": (i, [vp, u64p, sz, vp, sz, u64p, sz, u64p]),
+        "lemsm_argument_residual": (i, [i, u64p, u64p, u64p, u64p, u64p, u64p]),
         "lemsm_rhs_plan": (i, [i, ctypes.c_uint8, sz, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "lemsm_multiples_table_device": (i, [vp, i, vp, sz, ctypes.c_uint8, vp]),
         "lemsm_rhs_witness_device": (i, [vp, i, vp, vp, sz, ctypes.c_uint8, u64p, u64p, u64p, vp, u64p, u64p, szp]),

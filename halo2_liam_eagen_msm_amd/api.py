@@ -530,6 +530,70 @@ class Context:
         self._check(self.lib.lemsm_regfn_eval_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- L(f): the left-hand side of the argument ---------------------------------------------
+    def _logderiv_args(self, index, A, base):
+        if not (3 <= base <= 255):
+            raise BadBase(_lib.LEMSM_ERR_BAD_BASE, "base must be in 3..=255")
+        index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+        a = _limbs(A, 8) if np.size(A) else np.zeros((0, 8), np.uint64)
+        T, K = index.shape[0], a.shape[0]
+        return index, a, T, K, np.zeros((T, K, 4), np.uint64), np.zeros((K, 4), np.uint64), np.zeros((K, 4), np.uint64)
+
+    def regfn_logderiv_device(self, curve, d_coeffs: int, cap: int, index, A, base: int):
+        """L(f) (include/lemsm.h; tests/rhs_ref.py::L) of the functions `index` describes -- (T, 4) rows into the `cap`
+        32-byte coefficients at device pointer d_coeffs, what lhs_witness_device returns -- at the K challenge points A
+        ((K, 8) affine points of the curve), without the coefficients leaving HBM: (L (T, K, 4), sum (K, 4) =
+        sum_f (-base)^f L[f], t (K, 4) = the tangent slopes used).  Rows of length (0, 0) are skipped.  RefDivisionByZero
+        with .index = f K + k where a function vanishes at A or -2A."""
+        index, a, T, K, L, total, tt = self._logderiv_args(index, A, base)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_regfn_logderiv_device(self.h, _curve_id(curve), d_coeffs, cap, _ptr(index) if index.size else None, T,
+                                                  _ptr(a) if K else None, K, base, _ptr(L) if L.size else None, _ptr(total) if K else None,
+                                                  _ptr(tt) if K else None, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return L, total, tt
+
+    def regfn_logderiv(self, curve, fns, A, base: int):
+        """the same for fns = [(a, b), ...] coefficient arrays in host memory, as lhs_witness returns them"""
+        parts, rows, used = [], [], 0
+        for f in fns:
+            pa = _limbs(f[0], 4) if np.size(f[0]) else np.zeros((0, 4), np.uint64)
+            pb = _limbs(f[1], 4) if np.size(f[1]) else np.zeros((0, 4), np.uint64)
+            rows.append((used, pa.shape[0], used + pa.shape[0], pb.shape[0]))
+            parts += [pa, pb]; used += pa.shape[0] + pb.shape[0]
+        coeffs = np.concatenate(parts) if used else np.zeros((0, 4), np.uint64)
+        index, a, T, K, L, total, tt = self._logderiv_args(np.array(rows, np.uintp).reshape(-1, 4), A, base)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_regfn_logderiv(self.h, _curve_id(curve), _ptr(coeffs) if used else None, used, _ptr(index) if index.size else None, T,
+                                           _ptr(a) if K else None, K, base, _ptr(L) if L.size else None, _ptr(total) if K else None,
+                                           _ptr(tt) if K else None, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return L, total, tt
+
+    def regfn_logderiv_last(self) -> Tuple[float, int, int]:
+        """(device ms, coeff_bytes, field_mults) of the last regfn_logderiv* call"""
+        ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_regfn_logderiv_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
+        return ms.value, by.value, fm.value
+
+    def debug_regfn_deriv(self, fns, xs) -> np.ndarray:
+        """test hook (lemsm_debug_regfn_deriv): (T, K, 2, 4, 4) = {a(x), a'(x), b(x), b'(x)} of fns = [(a, b)] at the K pairs of
+        field elements xs (K, 2, 4); no curve involved, x = 0 allowed"""
+        parts, rows, used = [], [], 0
+        for f in fns:
+            pa = _limbs(f[0], 4) if np.size(f[0]) else np.zeros((0, 4), np.uint64)
+            pb = _limbs(f[1], 4) if np.size(f[1]) else np.zeros((0, 4), np.uint64)
+            rows.append((used, pa.shape[0], used + pa.shape[0], pb.shape[0]))
+            parts += [pa, pb]; used += pa.shape[0] + pb.shape[0]
+        coeffs = np.concatenate(parts) if used else np.zeros((0, 4), np.uint64)
+        index = np.array(rows, np.uintp).reshape(-1, 4)
+        x = np.ascontiguousarray(xs, np.uint64).reshape(-1, 2, 4)
+        T, K = index.shape[0], x.shape[0]
+        out = np.zeros((T, K, 2, 4, 4), np.uint64)
+        self._check(self.lib.lemsm_debug_regfn_deriv(self.h, _ptr(coeffs) if used else None, used, _ptr(index) if index.size else None, T,
+                                                     _ptr(x), K, _ptr(out)))
+        return out
+
     # ---- the right-hand side: "rhs main" gate (src/config.rs:504-538) and lookup columns (:402-437) ----
     def multiples_table_device(self, curve, d_points_affine: int, n: int, base: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """the fixed column of src/config.rs:542-560 left in HBM: n (base-1) rows of 64 B, row j (base-1) + (k-1) = affine
@@ -873,6 +937,31 @@ def regfn_eval_plan(index, cap: int, K: int, counts=None) -> dict:
     return {"num_values": nv.value, "field_mults": fm.value, "coeff_bytes": by.value}
 
 
+def regfn_logderiv_plan(index, cap: int, K: int) -> dict:
+    """{"num_values", "field_mults", "coeff_bytes"} of a regfn_logderiv request (pure host: lemsm_regfn_logderiv_plan)"""
+    lib = _lib.load()
+    index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+    nv = ctypes.c_size_t(); fm = ctypes.c_uint64(); by = ctypes.c_uint64()
+    rc = lib.lemsm_regfn_logderiv_plan(_ptr(index) if index.size else None, index.shape[0], cap, K, ctypes.byref(nv), ctypes.byref(fm), ctypes.byref(by))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"num_values": nv.value, "field_mults": fm.value, "coeff_bytes": by.value}
+
+
+def argument_residual(lhs_sum, carry_jacobian, rhs_sum, A, t, curve="grumpkin") -> np.ndarray:
+    """lhs_sum - g(-R) + rhs_sum (pure host: lemsm_argument_residual), zero exactly when the argument closes: lhs_sum from
+    regfn_logderiv*, carry (12 Jacobian limbs) from lhs_witness*, rhs_sum from rhs_witness*, A (8 limbs) and its slope t.
+    4 raw Montgomery limbs; RefDivisionByZero when -R lies on the line through A."""
+    v = [np.ascontiguousarray(x, np.uint64).reshape(k) for x, k in ((lhs_sum, 4), (carry_jacobian, 12), (rhs_sum, 4), (A, 8), (t, 4))]
+    out = np.zeros(4, np.uint64)
+    rc = _lib.load().lemsm_argument_residual(_curve_id(curve), *[_ptr(x) for x in v], _ptr(out))
+    if rc == _lib.LEMSM_ERR_DIVISION_BY_ZERO:
+        raise RefDivisionByZero(rc, "argument residual: -R lies on the line through A", 0)
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, _lib.load().lemsm_strerror(rc).decode())
+    return out
+
+
 def rhs_plan(curve, base: int, n: int) -> dict:
     """{"num_terms", "table_bytes", "out_bytes", "field_mults"} of an rhs_witness call (pure host: lemsm_rhs_plan)"""
     lib = _lib.load()
@@ -1042,6 +1131,12 @@ def compute_rhs_witness(scalars, pts, base: int, A, t=None, curve="grumpkin", ct
     stub): (running (n, base-1, 4), totals (base-1, 4), sum (4,)) for scalars (n, 32), Jacobian pts (n, 12), the challenge
     point A (8 limbs) and t (4 limbs; None: the tangent slope at A, src/config.rs:184-187)."""
     return (ctx or default_context()).rhs_witness(curve, scalars, pts, base, A, t, init)
+
+
+def compute_lhs_logderiv(fns, A, base: int, curve="grumpkin", ctx: Optional[Context] = None):
+    """The left-hand side of the argument's identity from the functions compute_lhs_witness returns: (L (d, K, 4), sum (K, 4)
+    = sum_f (-base)^f L[f], t (K, 4)) at the challenge points A ((K, 8) or 8 limbs), t the tangent slopes."""
+    return (ctx or default_context()).regfn_logderiv(curve, fns, A, base)
 
 
 def compute_divisor_witness(pts_affine, curve="grumpkin", ctx: Optional[Context] = None, normalise: bool = True):

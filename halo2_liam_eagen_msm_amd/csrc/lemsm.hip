@@ -22,6 +22,7 @@
 #include "roctx_dyn.hpp"
 #include "divisor.cuh"
 #include "regfn_eval.cuh"
+#include "regfn_logderiv.cuh"
 #include "rhs.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
@@ -109,6 +110,7 @@ struct lemsm_ctx {
   double dw_ntt_ms = 0; u64 dw_ntt_bytes = 0, dw_ntt_bflies = 0; u32 dw_reuse_levels = 0;
   DevBuf rf_coef, rf_ws;             // regular-function evaluation: staged coefficients (host entry), tables / partials / values
   double rf_ms = 0; u64 rf_bytes = 0, rf_mults = 0;   // lemsm_regfn_eval_last
+  double ld_ms = 0; u64 ld_bytes = 0, ld_mults = 0;   // lemsm_regfn_logderiv_last
   DevBuf rhs_ws, rhs_tab, rhs_pw;    // rhs witness / fraction sums: engine workspace, table + staged columns (host entries), powers of -base
   double rhs_ms = 0; u64 rhs_bytes = 0, rhs_mults = 0;   // lemsm_rhs_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
@@ -2643,4 +2645,5 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "divisor_abi.inc"
 #include "fixed_base.inc"
 #include "regfn_abi.inc"
+#include "regfn_logderiv_abi.inc"
 #include "rhs_abi.inc"

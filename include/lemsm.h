@@ -395,6 +395,57 @@ int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t c
    are priced with (as lemsm_divisor_last_ntt).  (:228-237) */
 int lemsm_regfn_eval_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults);
 
+/* ---- the left-hand side of the argument: L(f) of divisor witnesses -------------------- */
+/* The identity the argument compares is
+     sum_f (-base)^f L(f_f)  =  g(-R) + sum_j sum_k bucket[j][k] g(k P_j),   g(P) = (Ax - x_P) / (y_P - t x_P + t Ax - Ay).
+   L(f), for f = a(x) + y b(x), is the derivative in the slope lambda, at the tangent slope t of the challenge point A, of
+   log f(B(lambda)) + log f(C(lambda)), B and C the two other intersections of the curve with the line of slope lambda
+   through A; at lambda = t they are A and -2A.  With (Cx, Cy) = -2A, dS = 2 t, dQ = 2 t Ax - 2 Ay and, for (Bx, By, Ox) in
+   {(Ax, Ay, Cx), (Cx, Cy, Ax)}, dBx = (Bx dS - dQ) / (Bx - Ox), dBy = (Bx - Ax) + t dBx:
+     L(f) = sum over the two of ((a'(Bx) + By b'(Bx)) dBx + b(Bx) dBy) / (a(Bx) + By b(Bx)).
+   L is invariant under scaling f, so either `normalise` of lemsm_lhs_witness* gives the same bytes.
+   Grumpkin only (LEMSM_ERR_BAD_CURVE otherwise, as the eval entries).  index / coefficients: as lemsm_regfn_eval*.  a_xy:
+   K x 8 limbs, K challenge points, each an affine point of the curve (off the curve: LEMSM_ERR_BAD_ARG, Ay == 0:
+   LEMSM_ERR_DIVISION_BY_ZERO, both with the challenge's index in *bad_index); t is always the tangent 3 Ax^2 / (2 Ay)
+   (lemsm_slope) -- unlike the rhs entry, which takes any t, the formula for L holds only there -- and is returned in out_t.
+   base: 3 .. 255 (LEMSM_ERR_BAD_BASE); function f, the row index, gets the weight (-base)^f: the order in which
+   lemsm_lhs_witness* returns the functions.  A row with len_a = len_b = 0 is skipped: its L is 0 and it is absent from
+   the sum -- the rows lemsm_lhs_witness_device_range leaves for the other ranks' functions, so each rank of a sharded
+   witness gets the partial sum over its own functions and the host adds K field elements.
+   f(A) == 0 or f(-2A) == 0 for a non-empty function (L has a pole): LEMSM_ERR_DIVISION_BY_ZERO, *bad_index = the lowest
+   f K + k, outputs untouched.
+   out_L: T x K x 4 limbs, L of function f at challenge k in row f K + k; out_sum: K x 4, sum_f (-base)^f L[f][k]; out_t: K x 4.
+   Each may be NULL.  T == 0 and K == 0 are allowed (T == 0: sums are zero). */
+/* Pure host: validates the rows exactly as lemsm_regfn_eval_plan and prices a call: num_values = T K; field_mults =
+   4 K sum (len_a + len_b) (two abscissae, value and derivative each: the dual Horner's products); coeff_bytes =
+   32 sum (len_a + len_b), what one pass over the coefficients reads (0 when K == 0: nothing is read). */
+int lemsm_regfn_logderiv_plan(const size_t* index, size_t T, size_t cap_coeffs, size_t K, size_t* num_values, uint64_t* field_mults,
+                              uint64_t* coeff_bytes);
+/* Coefficients resident in the context's HBM (what lemsm_lhs_witness_device left there); everything else in host memory.
+   Every coefficient is read from HBM once per challenge. */
+int lemsm_regfn_logderiv_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                                const uint64_t* a_xy, size_t K, uint8_t base, uint64_t* out_L, uint64_t* out_sum, uint64_t* out_t,
+                                size_t* bad_index);
+/* The same with the coefficients in host memory (uploaded, then the device path). */
+int lemsm_regfn_logderiv(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                         const uint64_t* a_xy, size_t K, uint8_t base, uint64_t* out_L, uint64_t* out_sum, uint64_t* out_t,
+                         size_t* bad_index);
+/* Device time (ms, HIP events around the launches) of the last lemsm_regfn_logderiv* call and its plan's figures. */
+int lemsm_regfn_logderiv_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults);
+/* Test hook: the polynomial values the L kernels work from.  For T functions (coefficients in host memory) and K pairs of
+   arbitrary field elements xs (2 K x 4 limbs; no curve involved, 0 allowed), out = T x K x 2 x 4 field elements
+   {a(x), a'(x), b(x), b'(x)} for the two x of pair k, row ((f K + k) 2 + s) 4. */
+int lemsm_debug_regfn_deriv(lemsm_ctx* ctx, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T, const uint64_t* xs,
+                            size_t K, uint64_t* out);
+/* Host only: out = lhs_sum - g(-R) + rhs_sum, zero exactly when the argument closes.  lhs_sum: out_sum of
+   lemsm_regfn_logderiv*; rhs_sum: out_sum of lemsm_rhs_witness* (it already carries the gate's minus sign); R: the carry of
+   lemsm_lhs_witness* as 12 Jacobian limbs, made affine here; a_xy, t: the challenge and its slope (out_t).  Field elements
+   of the base field of `curve` (both curves).  R = O (Z == 0): g(O) := 0 -- the identity holds with that value (the sum of
+   the digit lists' divisors then has no pole left to account for; tests/test_logderiv_plan.py checks it on inputs whose
+   sum is the identity).  -R on the line through A: LEMSM_ERR_DIVISION_BY_ZERO. */
+int lemsm_argument_residual(int curve, const uint64_t lhs_sum[4], const uint64_t carry_jacobian[12], const uint64_t rhs_sum[4],
+                            const uint64_t a_xy[8], const uint64_t t[4], uint64_t out[4]);
+
 /* ---- the right-hand side: bucket-weighted line sums ("rhs main" gate, src/config.rs:504-538) ---- */
 /* The cells the reference's "rhs main" gate fixes down column c (src/config.rs:504-538; synthesize is a stub upstream,
    :635-683): for n scalars / points, base - 1 chains, one per non-zero digit value k, each stepping one scalar at a time
