@@ -819,7 +819,7 @@ class Context:
 
     # raw-limb hooks of the lazy field and XYZZ29 (lemsm.h LEMSM_F29_* / LEMSM_X29_*): int32 limbs in and out, no conversion
     F29_OPS = ("mul", "sqr", "mul2", "mul_addhi", "sqr_addhi", "add", "sub", "neg", "cneg", "wnorm", "canon", "reduce_small",
-               "mul32", "from_abi", "div32", "is_zero_mod", "limbs_zero", "hi_term", "pp_is_zero")
+               "mul32", "from_abi", "div32", "is_zero_mod", "limbs_zero", "hi_term", "pp_is_zero", "sqr_subhi")
     X29_OPS = ("madd", "madd_abi", "add", "dbl_affine", "dbl", "scale", "unscale", "add4_mem")
 
     def debug_field29_raw(self, curve, op, a, b=None, c=None, d=None) -> np.ndarray:

@@ -81,9 +81,10 @@ struct Field29 {
     for (int i = 0; i < 9; i++) r.l[i] = -a.l[i];
   }
   static __device__ __forceinline__ void cneg(fe& r, const fe& a, bool flag) {
-    i32 s = flag ? -1 : 0;
+    const i32 s = flag ? -1 : 0;
+    const i32 t = flag ? 1 : 0;
 #pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = (a.l[i] ^ s) - s;
+    for (int i = 0; i < 9; i++) r.l[i] = (a.l[i] ^ s) + t;   // one v_xad_u32 per limb
   }
   // exact sequential carry propagation: limbs 0..7 into [0, 2^29), limb 8 keeps the sign
   static __device__ __forceinline__ void wnorm(fe& a) {
@@ -102,6 +103,8 @@ struct Field29 {
   //   sqr(r,a)              r = a*a / 2^261            (36 doubled cross products + 9 squares)
   //   mul_addhi(r,a,b,hi)   r = a*b / 2^261 + hi       (hi: lazy limbs, added on the upper columns)
   //   sqr_addhi(r,a,hi)     r = a*a / 2^261 + hi
+  //   sqr_subhi(r,a,ppp,q)  r = a*a / 2^261 + 2N - ppp - 2q   (limb j of 2N - ppp - 2q, formed in 32 bits, is one more
+  //                         multiply-add -- by the inline constant 1 -- of column 9 + j)
   //   mul2(r,a,b,c,d)       r = (a*b + c*d) / 2^261
   // all results exactly normalised.
 #include "field29_gen.inc"
@@ -195,11 +198,13 @@ struct Field29 {
   // Since 32 = 2^261 / 2^256 this also takes x*2^256 (the C ABI's form) to x*2^261.
   static __device__ __forceinline__ void mul32(fe& r, const fe& a) {
     const float inv = 32.0f / (float)P::N[8];
-    i32 q = (i32)((float)a.l[8] * inv);            // |32a/N - q| < 2
+    const i32 nq = -(i32)((float)a.l[8] * inv);    // |32a/N - q| < 2
     i64 t = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
-      t += (i64)a.l[i] * 32 - (i64)q * P::N[i];
+      // t += 32 a_i - q N_i as two multiply-adds (left to itself hipcc builds the 64-bit terms from 32-bit shifts and adds)
+      asm("v_mad_i64_i32 %0, vcc, %1, 32, %0\n\t"
+          "v_mad_i64_i32 %0, vcc, %2, %3, %0\n\t" : "+v"(t) : "v"(a.l[i]), "v"(nq), "s"(P::N[i]) : "vcc");
       if (i < 8) { r.l[i] = (i32)t & MASK; t >>= 29; }
       else r.l[i] = (i32)t;
     }

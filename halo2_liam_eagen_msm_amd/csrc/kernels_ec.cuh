@@ -105,7 +105,10 @@ __global__ __launch_bounds__(256, WPS) void k_accum1(GroupPlan pl, const u32* __
 
   // One loop over the chunk with every lane in lockstep (a per-segment inner loop would let the
   // lanes of a wave drift apart: measured 1.5x slower).  The flush is a rare divergent branch.
-  for (u32 i = start; i < end; i++) {
+  // rel = i - start counts in a scalar register: start differs from lane to lane, the distance from it does not, and
+  // what hangs on it alone (the ring's block turnover) is then a scalar branch, not an exec-mask save and restore.
+  u32 rel = 0;
+  for (u32 i = start; i < end; i++, rel++) {
     u32 e = e_next; fe px, py;
     F::from_words(px, nx0, nx1); F::from_words(py, ny0, ny1);
     // Bucket boundary first, the next point's loads after it, and NO load inside the boundary branch (some lane
@@ -119,15 +122,20 @@ __global__ __launch_bounds__(256, WPS) void k_accum1(GroupPlan pl, const u32* __
       kbeg = i; seg_begin = i;
       G::set_identity(acc); empty = true;
     }
-    if (i + 1 < end) {
-      if constexpr (RING) {
-        const u32 rel1 = i + 1 - start;               // the same in every lane of the wave
-        if ((rel1 & 15u) == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // block rel1/16, requested 16 iterations ago
-        e_next = ring_read(rel1);
-        if ((rel1 & 15u) == 0 && rel1 + 16u < pl.L1) ring_fill((rel1 >> 4) + 1u);  // reuse the buffer of the block just finished
-      } else {
-        e_next = sorted[i + 1];
-      }
+    if constexpr (RING) {
+      // The gather below is unconditional: a lane at its last entry asks for the point it already has (e_next stays
+      // e, a valid index), so the raw words are loaded in place and need no copy around a branch.
+      const bool more = i + 1 < end;
+      const u32 rel1 = rel + 1;                       // the same in every lane of the wave
+      const bool turn = (rel1 & 15u) == 0;            // scalar
+      if (turn) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // block rel1/16, requested 16 iterations ago
+      const u32 en = ring_read(rel1);                 // (indices are masked: always inside the ring)
+      e_next = more ? en : e;
+      if (turn && rel1 + 16u < pl.L1) { if (more) ring_fill((rel1 >> 4) + 1u); }  // reuse the buffer of the block just finished
+      const uint4* p = points + (size_t)(e_next & 0xffffffu) * 4;
+      nx0 = p[0]; nx1 = p[1]; ny0 = p[2]; ny1 = p[3];
+    } else if (i + 1 < end) {
+      e_next = sorted[i + 1];
       const uint4* p = points + (size_t)(e_next & 0xffffffu) * 4;
       nx0 = p[0]; nx1 = p[1]; ny0 = p[2]; ny1 = p[3];
     }

@@ -1571,6 +1571,7 @@ __global__ void k_dbg_field29_raw(int op, const int32_t* __restrict__ a, const i
     case 16: pred = F29::limbs_zero(x) ? 1 : 0; break;
     case 17: G29::hi_term(r, x, y); break;
     case 18: pred = G29::pp_is_zero(x) ? 1 : 0; break;
+    case 19: F29::sqr_subhi(r, x, y, z); break;
     default: break;
   }
   int32_t* o = out + 10 * (size_t)i;
@@ -2589,7 +2590,7 @@ int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a,
                             int32_t* out, size_t n) {
   if (!ctx || !a || !b || !c || !d || !out) return LEMSM_ERR_BAD_ARG;
   int rc = check_curve(ctx, curve); if (rc) return rc;
-  if (op < 0 || op > LEMSM_F29_PP_IS_ZERO) return fail(ctx, LEMSM_ERR_BAD_ARG, "field29 raw op out of range (lemsm.h LEMSM_F29_*)");
+  if (op < 0 || op > LEMSM_F29_SQR_SUBHI) return fail(ctx, LEMSM_ERR_BAD_ARG, "field29 raw op out of range (lemsm.h LEMSM_F29_*)");
   if (!n) return LEMSM_OK;
   if (n > ((size_t)1 << 24)) return fail(ctx, LEMSM_ERR_BAD_ARG, "field29 raw: at most 2^24 operands per call");
   HIPCHK(ctx, hipSetDevice(ctx->device));

@@ -3,8 +3,8 @@
 // handling as xyzz.cuh; what differs is how the field operations are composed so that no
 // operand of a product ever exceeds the limb bound of field29.cuh:
 //   * differences of two normalised values (|limb| < 2^29) feed products directly,
-//   * X3 = R^2 - PPP - 2Q is ONE Montgomery reduction: (2N - PPP - 2Q) rides in on the upper
-//     columns of R*R, so X3 comes out normalised,
+//   * X3 = R^2 - PPP - 2Q is ONE Montgomery reduction: the limbs of (2N - PPP - 2Q) ride in on the upper
+//     columns of R*R (F::sqr_subhi), so X3 comes out normalised,
 //   * Y3 = R*(Q - X3) - Y1*PPP is ONE reduction of a two-product column sum.
 // A mixed addition is 7 multiplications + 2 squarings worth of products and 9 reductions
 // (~2,000 VALU instructions).
@@ -47,7 +47,8 @@ struct XYZZ29 {
   // as literal zeros, so the limb pattern test is exact.
   static __device__ __forceinline__ bool is_identity(const pt& p) { return F::limbs_zero(p.zz); }
 
-  // hi = 2N - ppp - 2q  (lazy limbs; only ever added into the upper columns of a product)
+  // hi = 2N - ppp - 2q  (lazy limbs).  The group law no longer forms it as a value: F::sqr_subhi takes ppp and q and
+  // feeds the same limbs into the upper columns of the squaring; this is its definition, kept for the raw-limb tests.
   static __device__ __forceinline__ void hi_term(fe& t, const fe& ppp, const fe& q) {
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -75,10 +76,9 @@ struct XYZZ29 {
     F::mul(W, U, V);                                  // W = U*V
     F::mul(S, p.x, V);                                // S = X*V
     F::sqr(t, p.x); F::add(M, t, t); F::add(M, M, t); F::wnorm(M);   // M = 3X^2
-    // X3 = M^2 - 2S :  hi = 2N - 0 - 2S
+    // X3 = M^2 + 2N - 0 - 2S
     fe zero; F::set_zero(zero);
-    hi_term(t, zero, S);
-    F::sqr_addhi(x3, M, t);
+    F::sqr_subhi(x3, M, zero, S);
     // Y3 = M*(S - X3) - W*Y
     F::sub(t, S, x3); F::neg(nW, W);
     fe y = p.y; F::wnorm(y);
@@ -125,9 +125,8 @@ struct XYZZ29 {
     fe PPP, Q, t, nY;
     F::mul(PPP, P, PP);
     F::mul(Q, acc.x, PP);
-    hi_term(t, PPP, Q);
     F::neg(nY, acc.y);
-    F::sqr_addhi(acc.x, R, t);                     // X3 = R^2 - PPP - 2Q
+    F::sqr_subhi(acc.x, R, PPP, Q);                // X3 = R^2 + 2N - PPP - 2Q
     F::sub(t, Q, acc.x);
     F::mul2(acc.y, R, t, nY, PPP);                 // Y3 = R(Q - X3) - Y1*PPP
     F::mul(acc.zz, acc.zz, PP);
@@ -168,9 +167,8 @@ struct XYZZ29 {
     fe PPP, Q, t, nY;
     F::mul(PPP, P, PP);
     F::mul(Q, acc.x, PP);
-    hi_term(t, PPP, Q);
     F::neg(nY, acc.y);
-    F::sqr_addhi(acc.x, R, t);                     // X3 = R^2 - PPP - 2Q
+    F::sqr_subhi(acc.x, R, PPP, Q);                // X3 = R^2 + 2N - PPP - 2Q
     F::sub(t, Q, acc.x);
     F::mul2(acc.y, R, t, nY, PPP);                 // Y3 = R(Q - X3) - Y1*PPP
     F::mul(acc.zz, acc.zz, PP);
@@ -208,9 +206,8 @@ struct XYZZ29 {
     fe PPP, Q, t, nS;
     F::mul(PPP, P, PP);
     F::mul(Q, U1, PP);
-    hi_term(t, PPP, Q);
     F::neg(nS, S1);
-    F::sqr_addhi(acc.x, R, t);
+    F::sqr_subhi(acc.x, R, PPP, Q);
     F::sub(t, Q, acc.x);
     F::mul2(acc.y, R, t, nS, PPP);
     F::mul(t, acc.zz, q.zz); F::mul(acc.zz, t, PP);

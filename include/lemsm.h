@@ -580,7 +580,8 @@ enum {
   LEMSM_F29_IS_ZERO_MOD = 15, /* predicate */
   LEMSM_F29_LIMBS_ZERO = 16,  /* predicate */
   LEMSM_F29_HI_TERM = 17,     /* XYZZ29::hi_term(ppp = a, q = b) */
-  LEMSM_F29_PP_IS_ZERO = 18   /* XYZZ29::pp_is_zero(a), predicate */
+  LEMSM_F29_PP_IS_ZERO = 18,  /* XYZZ29::pp_is_zero(a), predicate */
+  LEMSM_F29_SQR_SUBHI = 19    /* sqr_subhi(a, ppp = b, q = c) = a^2/R + 2N - b - 2c */
 };
 int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a, const int32_t* b, const int32_t* c,
                             const int32_t* d, int32_t* out, size_t n);
