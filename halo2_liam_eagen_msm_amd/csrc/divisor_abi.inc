@@ -87,7 +87,7 @@ void dw_ntt(lemsm_ctx* ctx, u32* buf, u32 nseq, u32 logN, bool inverse, const le
   using lemsm::dw::TileIO; using lemsm::dw::k_ntt_tile;
   const u32 lhm = ctx->dw_logn - 1;
   const u64 total = (u64)nseq << logN;
-  if (ctx->opt_ntt_tiled == 2) {      // (never with `fuse`: the caller keeps k_load / k_store in this mode)
+  if (ctx->opt.ntt_tiled == 2) {      // (never with `fuse`: the caller keeps k_load / k_store in this mode)
     const u64 threads = (u64)nseq << (logN - 1);
     const dim3 grid((u32)((threads + 255) / 256)), blk(256);
     if (!inverse) for (int lm = (int)logN - 1; lm >= 0; lm--)
@@ -110,7 +110,7 @@ void dw_ntt(lemsm_ctx* ctx, u32* buf, u32 nseq, u32 logN, bool inverse, const le
     const u32* W = (const u32*)dw_W(ctx);
     const u32* src = (inverse && !first_done && src_first) ? src_first : (const u32*)buf;
     first_done = true;
-    if (ctx->opt_dw_ntt_lazy == 1) {       // A/B knob: butterflies in the lazy 29-bit field (k_ntt_tile_lz); measured 1 % slower than the strict-field kernel (profiles/r03/l_ntt_lazy_field_ab.txt)
+    if (ctx->opt.dw_ntt_lazy == 1) {       // A/B knob: butterflies in the lazy 29-bit field (k_ntt_tile_lz); measured 1 % slower than the strict-field kernel (profiles/r03/l_ntt_lazy_field_ab.txt)
       const u32* W32 = (const u32*)dw_W32(ctx);
       if (!inverse) {
         if (edge && fuse && fwd_io == 3) hipLaunchKernelGGL((k_ntt_tile_lz<false, 3>), grid, blk, 0, ctx->stream, buf, total, logN, lo, S, W32, lhm, *fuse, src);
@@ -144,7 +144,7 @@ void dw_ntt(lemsm_ctx* ctx, u32* buf, u32 nseq, u32 logN, bool inverse, const le
 }
 
 // passes over HBM one transform of 2^logN elements makes (dw_ntt)
-u32 dw_ntt_passes(const lemsm_ctx* ctx, u32 logN) { return ctx->opt_ntt_tiled == 2 ? logN : 1u + (logN > 10 ? (logN - 10 + 7) / 8 : 0u); }
+u32 dw_ntt_passes(const lemsm_ctx* ctx, u32 logN) { return ctx->opt.ntt_tiled == 2 ? logN : 1u + (logN > 10 ? (logN - 10 + 7) / 8 : 0u); }
 
 struct DwResult {
   const u32* A = nullptr; const u32* B = nullptr;   // device, 32-byte coefficients
@@ -209,7 +209,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
   size_t half_max = 0;
   for (size_t l = 1; l < lv.size(); l++) half_max = std::max(half_max, ((size_t)1 << ceil_log2_u32(lv[l].cap)) / 2);
   const size_t feven_bytes = (size_t)2 * T * half_max * 32;
-  const bool reuse_opt = ctx->opt_dw_reuse != 2 && ctx->opt_dw_fuse != 2 && ctx->opt_ntt_tiled != 2 && lv.size() > 2 && feven_bytes <= ((size_t)16 << 30);   // (the bound is 4x what a wrap-mode level needs; beyond 16 GB -- many trees beside a huge one -- whole transforms)
+  const bool reuse_opt = ctx->opt.dw_reuse != 2 && ctx->opt.dw_fuse != 2 && ctx->opt.ntt_tiled != 2 && lv.size() > 2 && feven_bytes <= ((size_t)16 << 30);   // (the bound is 4x what a wrap-mode level needs; beyond 16 GB -- many trees beside a huge one -- whole transforms)
   const size_t oFb = take(fbuf_bytes + 256), oSt = take(256), oC = take(256 + (size_t)T * 32), oXS = take(xs_bytes + 256);
   const size_t oFb2 = reuse_opt ? take(fbuf_bytes + 256) : oFb, oFinv = reuse_opt ? take(fbuf_bytes / 2 + 256) : oFb, oFodd = reuse_opt ? take(fbuf_bytes / 2 + 256) : oFb;
   const size_t oFev = reuse_opt ? take(feven_bytes + 256) : oFb, oGo = reuse_opt ? take(half_max * 32 + 256) : oFb, oExc = take((size_t)T * 4 + 256);
@@ -270,7 +270,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
     // with the value at x = 0
     const u32 maxchild = hs[STAT_MAXCHILD], hs_maxpass = hs[STAT_MAXPASS];
     bool fused = false; TileIO tio;
-    bool wrap = ctx->opt_dw_wrap != 2 && maxlen >= 3 && ((maxlen - 1) & (maxlen - 2)) == 0 && maxchild <= maxlen - 1;
+    bool wrap = ctx->opt.dw_wrap != 2 && maxlen >= 3 && ((maxlen - 1) & (maxlen - 2)) == 0 && maxchild <= maxlen - 1;
     u32 logN = wrap ? ceil_log2_u32(maxlen - 1) : ceil_log2_u32(maxlen);
     if (((size_t)4 * nn << logN) * 32 > fbuf_bytes + 256) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal transform buffer bound exceeded");
     // reuse mode for this level: the level below left its quotient values on exactly the even half of this level's domain
@@ -304,7 +304,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
       // fused: the first forward pass gathers its input from the coefficient arrays (k_load's work) and the last inverse
       // pass scatters into them (k_store's): one write and one read of every transform buffer less per level.  Needs every
       // length of the level, passed-through nodes included, to fit the transform (N, or N + 1 in wrap mode).
-      fused = ctx->opt_dw_fuse != 2 && ctx->opt_ntt_tiled != 2 && hs_maxpass <= ((u32)1 << logN) && maxlen <= ((u32)1 << logN) + (wrap ? 1u : 0u);
+      fused = ctx->opt.dw_fuse != 2 && ctx->opt.ntt_tiled != 2 && hs_maxpass <= ((u32)1 << logN) && maxlen <= ((u32)1 << logN) + (wrap ? 1u : 0u);
       // reuse needs the fused gather, the coset of the level below, and children no longer than N/2 (+ the one coefficient that folds)
       reuse = can_reuse && fused && gexp == prev_gexp && maxchild <= ((u32)1 << (logN - 1)) + 1u;
       memset(&tio, 0, sizeof tio);
@@ -328,7 +328,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
       HIPCHK(ctx, hipEventRecord(e1, st));
       // slots per thread of the pointwise kernel (they share one field inversion): 64 when the level has millions of
       // elements, fewer -- down to 8 -- when that would leave the chip short of threads
-      u32 kb = ctx->opt_dw_kb >= DW_KB_MIN && ctx->opt_dw_kb <= DW_KB ? (u32)ctx->opt_dw_kb : (u32)DW_KB_AUTO;
+      u32 kb = ctx->opt.dw_kb >= DW_KB_MIN && ctx->opt.dw_kb <= DW_KB ? (u32)ctx->opt.dw_kb : (u32)DW_KB_AUTO;
       while (kb > (u32)DW_KB_MIN && (((u64)nn << logN) / kb) < ((u64)1 << 17)) kb >>= 1;
       const u32 chunks = (((u32)1 << logN) + kb - 1) / kb;
       const u64 pthreads = (u64)nn * chunks;
@@ -340,7 +340,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
         // half's numerators (option dw_halves = 2: one chain, as before).
         auto pw_num = [&](hipStream_t q, u32 k0, u32 kn) {
           const u64 nthreads = ((u64)kn << logN) + (wrap ? kn : 0u);
-          if (ctx->opt_dw_pw_lazy == 1)
+          if (ctx->opt.dw_pw_lazy == 1)
             hipLaunchKernelGGL((k_pw_num<true>), dim3((u32)((nthreads + 255) / 256)), dim3(256), 0, q, fbuf, (const Plan*)plan, nn, logN, (const u32*)xs,
                              (const u32*)consts, stats, wrap ? c0in : (u32*)nullptr, c0out,
                              reuse ? (const u32*)fodd : (const u32*)nullptr, (const u32*)fb2[1 - cf], (const u32*)feven, prev_nn, k0, kn);
@@ -360,7 +360,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
           hipLaunchKernelGGL(k_pw_apply, dim3((u32)((pth + 255) / 256)), dim3(256), 0, q, fbuf, (const Plan*)plan, nn, logN, chunks,
                              wrap ? (const u32*)c0in : (const u32*)nullptr, c0out, (const u32*)roots_q, k0, kn);
         };
-        const bool halves = ctx->opt_dw_halves == 1 && nn >= 2 && pthreads >= ((u64)1 << 16);
+        const bool halves = ctx->opt.dw_halves == 1 && nn >= 2 && pthreads >= ((u64)1 << 16);
         if (halves) {
           // staggered: the second half's numerators start when the first half's are done (two numerator kernels side by side
           // ran 24 % slower than one after the other: profiles/r03/k_halves_trace.txt), beside the first half's division chain
@@ -804,11 +804,12 @@ struct CurveMath {
   }
 };
 
-template <class P64>
-int post_t(int what, u64 gen, u64 bcoef, bool bneg, const uint64_t* in, uint64_t* out, int* flag) {
-  typedef CurveMath<P64> M; typedef host::HF<P64> F;
+template <class C>   // the curve's traits: its base field (generator C::GEN) and y^2 = x^3 + C::B
+int post_t(int what, const uint64_t* in, uint64_t* out, int* flag) {
+  typedef typename C::P64 P64; typedef CurveMath<P64> M; typedef host::HF<P64> F;
+  const u64 gen = C::GEN;
   host::fe x; memcpy(x.l, in, 32);
-  host::fe bb = M::from_u64(bcoef); if (bneg) bb = F::neg(bb);
+  host::fe bb = M::from_u64(C::B < 0 ? -C::B : C::B); if (C::B < 0) bb = F::neg(bb);
   host::fe rhs = F::add(F::mul(F::sqr(x), x), bb);               // x^3 + a x + b, a = 0  (:169, :179)
   if (what == 0) {                                               // to_curve_x :166-175
     host::fe y;
@@ -834,9 +835,8 @@ int post_t(int what, u64 gen, u64 bcoef, bool bneg, const uint64_t* in, uint64_t
 int post_dispatch(int curve, int what, const uint64_t* in, uint64_t* out, int* flag) {
   if (!in || !out) return LEMSM_ERR_BAD_ARG;
   // base field of BN254 G1 is Fq (generator 3, y^2 = x^3 + 3); of Grumpkin Fr (generator 7, y^2 = x^3 - 17)
-  if (curve == LEMSM_BN254_G1) return post_t<host::FqParams64>(what, 3, 3, false, in, out, flag);
-  if (curve == LEMSM_GRUMPKIN) return post_t<host::FrParams64>(what, 7, 17, true, in, out, flag);
-  return LEMSM_ERR_BAD_CURVE;
+  if (curve != LEMSM_BN254_G1 && curve != LEMSM_GRUMPKIN) return LEMSM_ERR_BAD_CURVE;
+  return with_curve(curve, [&](auto cv) { return post_t<decltype(cv)>(what, in, out, flag); });
 }
 
 }  // namespace

@@ -257,8 +257,9 @@ int lemsm_fixed_bases_create(lemsm_ctx* ctx, const lemsm_bases* bases, uint32_t 
     const u32 cnt = (u32)std::min<size_t>(CHUNK, n - i0);
     const uint4* src = (const uint4*)((const char*)bases->d_points + i0 * 64);
     uint4* dst = (uint4*)((char*)d + i0 * p.m * 64);
-    if (bases->curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_fixed_table<FqDev>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, src, cnt, p.m, shift, dst, (char*)scratch);
-    else hipLaunchKernelGGL((k_fixed_table<FrDev>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, src, cnt, p.m, shift, dst, (char*)scratch);
+    with_curve(bases->curve, [&](auto cv) {
+      hipLaunchKernelGGL((k_fixed_table<typename decltype(cv)::F>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, src, cnt, p.m, shift, dst, (char*)scratch);
+    });
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -293,8 +294,10 @@ int lemsm_msm_fixed_device(lemsm_ctx* ctx, const lemsm_fixed_bases* fb, const vo
   if (n > fb->n) return fail(ctx, LEMSM_ERR_LEN_MISMATCH, "more scalars than the table has bases");
   if (n == 0) { memset(out, 0, 96); return LEMSM_OK; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (fb->curve == LEMSM_BN254_G1) return msm_fixed_t<host::FqParams64, GqLazy>(ctx, fb, d_scalars, n, out);
-  return msm_fixed_t<host::FrParams64, GrLazy>(ctx, fb, d_scalars, n, out);
+  return with_curve(fb->curve, [&](auto cv) {
+    typedef decltype(cv) C;
+    return msm_fixed_t<typename C::P64, typename C::GLazy>(ctx, fb, d_scalars, n, out);
+  });
 }
 
 int lemsm_msm_fixed(lemsm_ctx* ctx, const lemsm_fixed_bases* fb, const uint8_t* scalars, size_t n, uint64_t out[12]) {

@@ -1,6 +1,7 @@
 // C ABI implementation (include/lemsm.h): contexts, workspace, launch plans, the kernel
 // pipeline and the host-side tail.  gfx950 only; there is no CPU path.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -40,15 +41,48 @@ typedef XYZZ<FrDev> GrStrict;
 typedef XYZZ29<Field29<Fq29Params>> GqLazy;   // lazy radix-2^29 field: the default hot path
 typedef XYZZ29<Field29<Fr29Params>> GrLazy;
 
-// scalar-field orders as 8 x u32 (BN254 G1: r, Grumpkin: p) and isqrt(order)+2
-const u32 ORDER_R[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-const u32 ORDER_P[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-// isqrt(r)+2 = 0x6f4d8248eeb859fcc6fb4e9fc7b81b1b ; isqrt(p)+2 = 0x6f4d8248eeb859fcc6fb4e9fc7b81b1c
-const u32 BOUND_R[8] = {0xc7b81b1bu, 0xc6fb4e9fu, 0xeeb859fcu, 0x6f4d8248u, 0, 0, 0, 0};
-const u32 BOUND_P[8] = {0xc7b81b1cu, 0xc6fb4e9fu, 0xeeb859fcu, 0x6f4d8248u, 0, 0, 0, 0};
+// Everything that follows from the curve id: the parameter sets of its coordinate field on the host and on the device,
+// the strict and the lazy field and group over it, the scalar-field order as 8 x u32 (BN254 G1: r, Grumpkin: p) and
+// BOUND = isqrt(ORDER) + 2, the curve's b (y^2 = x^3 + b) and the coordinate field's generator
+struct Bn254G1 {
+  typedef host::FqParams64 P64; typedef FqParams P; typedef FqDev F; typedef Field29<Fq29Params> F29;
+  typedef GqStrict GStrict; typedef GqLazy GLazy;
+  static constexpr u32 ORDER[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+  static constexpr u32 BOUND[8] = {0xc7b81b1bu, 0xc6fb4e9fu, 0xeeb859fcu, 0x6f4d8248u, 0, 0, 0, 0};   // 0x6f4d8248eeb859fcc6fb4e9fc7b81b1b
+  static constexpr int B = 3; static constexpr u64 GEN = 3;
+};
+struct Grumpkin {
+  typedef host::FrParams64 P64; typedef FrParams P; typedef FrDev F; typedef Field29<Fr29Params> F29;
+  typedef GrStrict GStrict; typedef GrLazy GLazy;
+  static constexpr u32 ORDER[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+  static constexpr u32 BOUND[8] = {0xc7b81b1cu, 0xc6fb4e9fu, 0xeeb859fcu, 0x6f4d8248u, 0, 0, 0, 0};   // 0x6f4d8248eeb859fcc6fb4e9fc7b81b1c
+  static constexpr int B = -17; static constexpr u64 GEN = 7;
+};
 
-const u32* order_of(int curve) { return curve == LEMSM_BN254_G1 ? ORDER_R : ORDER_P; }
-const u32* bound_of(int curve) { return curve == LEMSM_BN254_G1 ? BOUND_R : BOUND_P; }
+// Options of a context (lemsm_set_option), 0 = default each; OPTION_ROWS below lists the values every one accepts
+struct Options {
+  long host_threads = 0, window_bits = 0, chunk = 0, tile = 0, field = 0, accum_waves = 0, groups = 0, host_slab_bits = 0, slab_bits = 0,
+       abi_points = 0, stage2x = 0, xcd_windows = 0, entry_ring = 0, validate_points = 0, pyr_fuse = 0, pyr_first2 = 0, pyr_quad = 0,
+       ws_canary = 0, binsort = 0, merge_slice = 0, merge_wave_th = 0, slab_tail = 0, scatter_lean = 0, ntt_tiled = 0, dw_wrap = 0,
+       dw_fuse = 0, dw_kb = 0, dw_reuse = 0, dw_pw_lazy = 0, dw_halves = 0, dw_ntt_lazy = 0;
+};
+
+// fn(Traits{}) for the curve id; callers have checked the id (check_curve, or the inline test of the context-free entries)
+template <class Fn>
+auto with_curve(int curve, Fn&& fn) {
+  if (curve == LEMSM_BN254_G1) return fn(Bn254G1{});
+  return fn(Grumpkin{});
+}
+// the entries that honour option "field" (0 = lazy radix-2^29, the default; 1 = strict 32-bit limbs): fn(Traits{}, Group{})
+template <class Fn>
+auto with_arith(int curve, const Options& opt, Fn&& fn) {
+  return with_curve(curve, [&](auto cv) {
+    if (opt.field == 1) return fn(cv, typename decltype(cv)::GStrict{});
+    return fn(cv, typename decltype(cv)::GLazy{});
+  });
+}
+const u32* order_of(int curve) { return with_curve(curve, [](auto cv) -> const u32* { return decltype(cv)::ORDER; }); }
+const u32* bound_of(int curve) { return with_curve(curve, [](auto cv) -> const u32* { return decltype(cv)::BOUND; }); }
 
 }  // namespace
 // heavy kernels are instantiated in inst_*.hip
@@ -121,8 +155,7 @@ struct lemsm_ctx {
   void* h_pin = nullptr; size_t h_pin_cap = 0;   // pinned staging for the read-back of one call's records (one async copy, no pageable bounce)
   std::unique_ptr<lemsm::host::Pool> pool;        // host tail: per-window work of one call (hostpool.hpp); created on first use
   std::string last_error;
-  long opt_host_threads = 0;
-  long opt_window_bits = 0, opt_chunk = 0, opt_tile = 0, opt_field = 0, opt_accum_waves = 0, opt_groups = 0, opt_host_slab_bits = 0, opt_slab_bits = 0, opt_abi_points = 0, opt_stage2x = 0, opt_xcd_windows = 0, opt_entry_ring = 0, opt_validate_points = 0, opt_pyr_fuse = 0, opt_ntt_tiled = 0, opt_ws_canary = 0, opt_binsort = 0, opt_dw_wrap = 0, opt_dw_fuse = 0, opt_dw_kb = 0, opt_merge_slice = 0, opt_merge_wave_th = 0, opt_dbg_repeat = 0, opt_pyr_first2 = 0, opt_dw_reuse = 0, opt_dw_pw_lazy = 0, opt_dw_halves = 0, opt_dw_ntt_lazy = 0, opt_slab_tail = 0, opt_pyr_quad = 0, opt_scatter_lean = 0;
+  Options opt;                                    // lemsm_set_option
   u32 plan_slab_n = 0;                            // choose_lb: points of a FULL slab of the running call (every slab of a call, the ragged last one too, uses the same bin geometry)
   bool plan_ring = false;                         // make_group_plan: round the accumulate chunk to the entry ring's 16-entry blocks
   const struct HostStage* host_stage = nullptr;   // set by the host-pointer entries for the duration of one call
@@ -176,8 +209,8 @@ int reserve_pinned(lemsm_ctx* ctx, size_t bytes) {
 // host tail in parallel: jobs are independent pieces of ~10 us (one window's records); option "host_threads":
 // 0 = auto (up to 8 threads including the caller, never more than the CPUs this process may use), 1 = serial
 void host_parallel(lemsm_ctx* ctx, int njobs, const std::function<void(int)>& fn) {
-  if (!ctx || njobs <= 1 || ctx->opt_host_threads == 1) { for (int i = 0; i < njobs; i++) fn(i); return; }
-  int want = ctx->opt_host_threads > 1 ? (int)ctx->opt_host_threads : std::min(8, lemsm::host::Pool::usable_cpus());
+  if (!ctx || njobs <= 1 || ctx->opt.host_threads == 1) { for (int i = 0; i < njobs; i++) fn(i); return; }
+  int want = ctx->opt.host_threads > 1 ? (int)ctx->opt.host_threads : std::min(8, lemsm::host::Pool::usable_cpus());
   if (!ctx->pool || ctx->pool->workers() != want - 1) ctx->pool.reset(new lemsm::host::Pool(std::max(0, want - 1)));
   ctx->pool->run(njobs, fn);
 }
@@ -214,7 +247,7 @@ struct MsmPlan {
 // window bits for an n-point MSM: 16 for large n (2-byte windows, 16 windows of 2^15 buckets
 // for 254-bit scalars: divisible by 1/2/4/8 GPUs); fewer for small n so buckets are not mostly empty.
 u32 choose_c(const lemsm_ctx* ctx, size_t n) {
-  if (ctx && ctx->opt_window_bits >= 2 && ctx->opt_window_bits <= 17) return (u32)ctx->opt_window_bits;
+  if (ctx && ctx->opt.window_bits >= 2 && ctx->opt.window_bits <= 17) return (u32)ctx->opt.window_bits;
   u32 lg = 0; while (((size_t)1 << (lg + 1)) <= n) lg++;
   // 17-bit windows (15 windows of 2^16 buckets, 512 coarse bins each, one window group) from 2^24
   // points per slab: 6 % less accumulation, 0.5 ms more sort + tail -> 3 % faster end to end at
@@ -237,16 +270,16 @@ u32 host_slab_log(const lemsm_ctx* ctx, size_t n) {
   // kernels do, so fewer, larger slabs win (each slab pays its own sort + tail): 2^22 measured best at 2^24
   // (profiles/r02/m_host_path_2p24.txt)
   if (ctx->host_stage && !ctx->host_stage->h_points) auto_log = std::min(22u, std::max(19u, lg >= 2 ? lg - 2 : 0u));
-  return std::min<u32>(MAX_SLAB_LOG, ctx->opt_host_slab_bits ? (u32)ctx->opt_host_slab_bits : auto_log);
+  return std::min<u32>(MAX_SLAB_LOG, ctx->opt.host_slab_bits ? (u32)ctx->opt.host_slab_bits : auto_log);
 }
 
-MsmPlan make_msm_plan(const lemsm_ctx* ctx, int curve, size_t n) {
+MsmPlan make_msm_plan(const lemsm_ctx* ctx, int curve, size_t n, u32 force_c = 0 /* this window width whatever n and the options say */) {
   MsmPlan p; memset(&p, 0, sizeof p);
   // the window width follows the number of pairs one pass of the pipeline sees (a slab), not the call's total
   size_t n_pass = n;
   if (ctx && ctx->host_stage) n_pass = std::min(n, (size_t)1 << host_slab_log(ctx, n));
-  else if (ctx && ctx->opt_slab_bits) n_pass = std::min(n, (size_t)1 << ctx->opt_slab_bits);
-  p.c = choose_c(ctx, n_pass);
+  else if (ctx && ctx->opt.slab_bits) n_pass = std::min(n, (size_t)1 << ctx->opt.slab_bits);
+  p.c = force_c ? force_c : choose_c(ctx, n_pass);
   p.nb = 1u << (p.c - 1);
   p.nbp = p.nb; p.L = ilog2(p.nbp);
   const u32* order = order_of(curve);
@@ -275,10 +308,7 @@ MsmPlan make_msm_plan(const lemsm_ctx* ctx, int curve, size_t n) {
     if (sh >= 256) { fits = true; }
     if (fits) { p.W = W; memcpy(p.kadd, K, 32); break; }
   }
-  if (p.c == 17 && p.W != 15) {   // the 17-bit digit kernel is written for 15 windows (254-bit orders)
-    lemsm_ctx tmp_opts; tmp_opts.opt_window_bits = 16;
-    return make_msm_plan(&tmp_opts, curve, n);
-  }
+  if (p.c == 17 && p.W != 15) return make_msm_plan(ctx, curve, n, 16);   // the 17-bit digit kernel is written for 15 windows (254-bit orders)
   return p;
 }
 
@@ -306,8 +336,8 @@ struct GroupWs {
 };
 
 MqLayout make_mq_layout(const lemsm_ctx* ctx, u32 nthr1) {
-  return make_mq_layout_t(nthr1, ctx && ctx->opt_merge_slice ? (u32)ctx->opt_merge_slice : 512u,
-                          ctx && ctx->opt_merge_wave_th ? (u32)ctx->opt_merge_wave_th - 1u : 2048u);
+  return make_mq_layout_t(nthr1, ctx && ctx->opt.merge_slice ? (u32)ctx->opt.merge_slice : 512u,
+                          ctx && ctx->opt.merge_wave_th ? (u32)ctx->opt.merge_wave_th - 1u : 2048u);
 }
 
 const size_t WS_GUARD = 256;
@@ -367,8 +397,8 @@ u32 choose_lb(const lemsm_ctx* ctx, u32 nb, u32 n, u32 d) {
   if (ctx && ctx->plan_slab_n) n = ctx->plan_slab_n;
   u32 LB = 0;
   while (((nb + (1u << LB) - 1) >> LB) > 256 && LB < MAX_LB) LB++;
-  if (d == 0 && ctx && ctx->opt_binsort != 2 && LB > 0) {
-    const u32 cap = ctx->opt_binsort > 2 ? std::min((u32)ctx->opt_binsort, (u32)BIN_CAP) : (u32)BIN_CAP;
+  if (d == 0 && ctx && ctx->opt.binsort != 2 && LB > 0) {
+    const u32 cap = ctx->opt.binsort > 2 ? std::min((u32)ctx->opt.binsort, (u32)BIN_CAP) : (u32)BIN_CAP;
     const u32 BW = (nb + (1u << LB) - 1) >> LB;
     if ((u64)n / BW > (u64)cap * 9 / 10 && 2 * BW <= BW_MAX && (u64)n / (2 * BW) <= (u64)cap * 9 / 10) LB--;
   }
@@ -388,21 +418,21 @@ GroupPlan make_group_plan(const lemsm_ctx* ctx, u32 n, u32 c, u32 nb, u32 W, u32
   spb = std::max(256u, std::min((u32)STAGE, spb));
   spb = (spb + 255) / 256 * 256;
   if (n >= (1u << 16)) spb = STAGE;     // long (block, bin) runs -> full-line writes
-  if (n >= (1u << 16) && d == 0 && ctx->opt_stage2x == 4) spb = 4 * STAGE;   // 1024-thread pass-1 blocks staging 16384 entries: 128-byte runs at 512 bins per window
-  if (n >= (1u << 16) && d == 0 && ctx->opt_stage2x == 2) spb = 2 * STAGE;   // A/B knob: 64-byte runs at 512 bins per window; measured slower (fewer resident blocks), profiles/r01/y_scatter1_staging_ab.txt
+  if (n >= (1u << 16) && d == 0 && ctx->opt.stage2x == 4) spb = 4 * STAGE;   // 1024-thread pass-1 blocks staging 16384 entries: 128-byte runs at 512 bins per window
+  if (n >= (1u << 16) && d == 0 && ctx->opt.stage2x == 2) spb = 2 * STAGE;   // A/B knob: 64-byte runs at 512 bins per window; measured slower (fewer resident blocks), profiles/r01/y_scatter1_staging_ab.txt
   g.spb = spb;
   g.dstride = (n + 63u) / 64u * 64u;
   g.nblk1 = (n + spb - 1) / spb;
   if (g.nblk1 == 0) g.nblk1 = 1;
   size_t Mmax = (size_t)n * (w1 - w0);
-  u32 T2 = ctx->opt_tile > 0 ? std::min((u32)ctx->opt_tile, (u32)STAGE2) : (u32)STAGE2;
+  u32 T2 = ctx->opt.tile > 0 ? std::min((u32)ctx->opt.tile, (u32)STAGE2) : (u32)STAGE2;
   g.T2 = T2;
   g.max_tiles = (u32)(Mmax / T2) + g.nbins + 1;
-  g.bin_cap = ctx->opt_binsort == 2 ? 0u : (ctx->opt_binsort > 2 ? std::min((u32)ctx->opt_binsort, (u32)BIN_CAP) : (u32)BIN_CAP);
+  g.bin_cap = ctx->opt.binsort == 2 ? 0u : (ctx->opt.binsort > 2 ? std::min((u32)ctx->opt.binsort, (u32)BIN_CAP) : (u32)BIN_CAP);
   // short bins (uniform digits put n / BW entries in each): the 32-KiB variant of k_binsort, with room for 1.5x the mean
   if (g.bin_cap == BIN_CAP && g.BW && (u64)n * 3 / 2 / g.BW <= BIN_CAP_SMALL) g.bin_cap = BIN_CAP_SMALL;
   u32 L1;
-  if (ctx->opt_chunk > 0) L1 = (u32)ctx->opt_chunk;
+  if (ctx->opt.chunk > 0) L1 = (u32)ctx->opt.chunk;
   else {
     // two full rounds of the accumulate kernel's 3 waves per SIMD (256 CUs x 4 SIMDs x 3 x 64 lanes x 2):
     // measured best at 2^20..2^22 (profiles/r01/q_chunk_sweep.txt); from 2^23 the cap of 256 applies
@@ -412,7 +442,7 @@ GroupPlan make_group_plan(const lemsm_ctx* ctx, u32 n, u32 c, u32 nb, u32 W, u32
   }
   // the entry ring of k_accum1 stages 16-entry blocks: when that form will run (run_windows sets the flag once it
   // has chosen the ABI form), chunks are a multiple of 16 entries
-  if (ctx->plan_ring && ctx->opt_chunk == 0 && L1 >= 128) L1 = (L1 + 15u) & ~15u;   // (short chunks: the ring's per-chunk prologue costs more than it saves: profiles/r01/zz_entry_ring_small_sizes.txt)
+  if (ctx->plan_ring && ctx->opt.chunk == 0 && L1 >= 128) L1 = (L1 + 15u) & ~15u;   // (short chunks: the ring's per-chunk prologue costs more than it saves: profiles/r01/zz_entry_ring_small_sizes.txt)
   g.L1 = L1;
   g.nthr1 = (u32)((Mmax + L1 - 1) / L1);
   if (g.nthr1 == 0) g.nthr1 = 1;
@@ -518,13 +548,13 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
   CopyTask* d_copy = (CopyTask*)((char*)pit->second.buf.p + align_up(ntasks_total * sizeof(PyrTask), 256));
   const size_t ptb = G::PT_BYTES;
   const MqLayout mq = make_mq_layout(ctx, pl.nthr1);
-  GroupWs w = carve(ws_base, pl, ar, mq, ptb, ctx->opt_ws_canary != 0);
+  GroupWs w = carve(ws_base, pl, ar, mq, ptb, ctx->opt.ws_canary != 0);
   // the kernels below size LDS arrays and workspace slots by these limits: never launch a plan that exceeds them
   if (pl.nbins > MAX_BINS || pl.BW > BW_MAX || pl.LB > MAX_LB || pl.spb > 4 * STAGE || (pl.c && pl.dstride < pl.n) || pl.T2 > STAGE2 || pl.bin_cap > BIN_CAP)
     return fail(ctx, LEMSM_ERR_HIP, "internal: window-group plan exceeds a kernel limit (bins " + std::to_string(pl.nbins) + ", bins per window " + std::to_string(pl.BW) + ")");
 
   // k_pyramid_first2 recognises empty buckets from bucket_start[]: with it only the counters are zeroed, not the bucket sums
-  const bool first2 = L >= 5 && ctx->opt_pyr_first2 == 1 && nba == 1;
+  const bool first2 = L >= 5 && ctx->opt.pyr_first2 == 1 && nba == 1;
   RoctxRange rg_group("lemsm: window group (digits + sort + accumulate + tail enqueued)");
   // (shared tail: the first slab clears every slab's bucket area, the later ones only the counters)
   // (r03: clearing the bucket sums on the second queue beside the digit and sort passes was measured and dropped -- the
@@ -536,13 +566,13 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
   { int rcp = prov.prepare(ctx, st, pl, w.dig16, w.signbm, w.block_counts, w.bin_total, w.err, dec); if (rcp) return rcp; }
   hipLaunchKernelGGL(k_binscan, dim3(1), dim3(1024), 0, st, pl, w.bin_total, w.bin_start, w.tile_prefix, w.meta);
   // >= 8 windows: 1-D grid, one XCD per window (see the kernel); else (windows, ranges)
-  const u32 xw = (gw >= 8 && ctx->opt_xcd_windows != 1) ? 1u : 0u;
+  const u32 xw = (gw >= 8 && ctx->opt.xcd_windows != 1) ? 1u : 0u;
   dim3 g1 = xw ? dim3(8u * ((gw + 7) / 8) * pl.nblk1) : dim3(gw, pl.nblk1);
   if (pl.spb > 2 * STAGE)
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, 4 * STAGE, 1024>), g1, dim3(1024), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
   else if (pl.spb > STAGE)
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, 2 * STAGE>), g1, dim3(256), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
-  else if (Prov::Dec::VEC && (pl.BW & 1u) == 0 && ctx->opt_scatter_lean == 1)   // A/B knob (needs an even number of bins per window): 899 us against 880 at 2^24, profiles/r03/s_scatter_lean_and_clear_beside_ab.txt
+  else if (Prov::Dec::VEC && (pl.BW & 1u) == 0 && ctx->opt.scatter_lean == 1)   // A/B knob (needs an even number of bins per window): 899 us against 880 at 2^24, profiles/r03/s_scatter_lean_and_clear_beside_ab.txt
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, STAGE, 256, true>), g1, dim3(256), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
   else
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, STAGE>), g1, dim3(256), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
@@ -574,11 +604,11 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
     dim3 grid((pl.nthr1 + 255) / 256), blk(256);
     char* bsum = w.arena + ((size_t)ar.bucket_off + (size_t)slab_k * NBpad) * ptb;
     // register-budget variant of the accumulate kernel (lazy field: 2, 3 or 4 waves per SIMD)
-    int wps = G::CONVERTED_DOMAIN ? (ctx->opt_accum_waves ? (int)ctx->opt_accum_waves : 3) : 4;
+    int wps = G::CONVERTED_DOMAIN ? (ctx->opt.accum_waves ? (int)ctx->opt.accum_waves : 3) : 4;
     if constexpr (G::CONVERTED_DOMAIN) {
       if (wps == 2) hipLaunchKernelGGL((k_accum1<G, 2>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
       else if (wps == 4) hipLaunchKernelGGL((k_accum1<G, 4>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
-      else if (abi && (pl.L1 & 15u) == 0 && pl.L1 >= 32 && ctx->opt_entry_ring != 1) hipLaunchKernelGGL((k_accum1<G, 3, true, true>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
+      else if (abi && (pl.L1 & 15u) == 0 && pl.L1 >= 32 && ctx->opt.entry_ring != 1) hipLaunchKernelGGL((k_accum1<G, 3, true, true>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
       else if (abi) hipLaunchKernelGGL((k_accum1<G, 3, true>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
       else hipLaunchKernelGGL((k_accum1<G, 3>), grid, blk, 0, st, pl, d_sorted, d_bstart, w.meta, (const uint4*)d_points, bsum, w.rec_key, w.rec_pt);
     } else {
@@ -625,8 +655,8 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
     // `lim` items: 256 by default -- one wave per SIMD of the block's CU, so a fused step costs one addition (~6.5 us)
     // where a launch of its own costs ~10; with more items per step the block's waves share SIMDs and a fused step
     // gets slower than a launch spread over the chip (option pyr_fuse = 2: 2048, measured slower; 1: never fuse)
-    if (ctx->opt_pyr_fuse != 1) {
-      const size_t lim = ctx->opt_pyr_fuse == 2 ? 2048 : 256;
+    if (ctx->opt.pyr_fuse != 1) {
+      const size_t lim = ctx->opt.pyr_fuse == 2 ? 2048 : 256;
       for (u32 s = s_begin; s <= L; s++) {
         bool fits = true;
         for (u32 q = s; q <= L; q++) if ((size_t)pp.steps[q - 1].size() * pp.step_max_count[q - 1] > lim) fits = false;
@@ -639,7 +669,7 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
       u32 maxc = pp.step_max_count[s - 1];
       size_t threads = (size_t)tasks.size() * maxc * gw;
       // a step that leaves most SIMDs without a wave is one addition deep: four lanes per addition (XYZZ29::add4_mem) make it ~2.6x shallower
-      const u32 quad = (G::CONVERTED_DOMAIN && ctx->opt_pyr_quad != 2 && threads <= 32768 && !(s == 1 && abi_pyr)) ? 1u : 0u;
+      const u32 quad = (G::CONVERTED_DOMAIN && ctx->opt.pyr_quad != 2 && threads <= 32768 && !(s == 1 && abi_pyr)) ? 1u : 0u;
       if (quad) threads *= 4;
       hipLaunchKernelGGL((k_pyramid<G>), dim3((u32)((threads + 255) / 256)), dim3(256), 0, st, d_tasks + toff, (u32)tasks.size(), gw, maxc, w.arena, quad);
       toff += tasks.size();
@@ -652,7 +682,7 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
       for (u32 s = first_fused; s <= L; s++) { ta.step_off[s - first_fused] = o; ta.max_count[s - first_fused] = pp.step_max_count[s - 1]; o += (u32)pp.steps[s - 1].size(); }
       ta.step_off[L - first_fused + 1] = o;
       hipLaunchKernelGGL((k_pyramid_tail<G>), dim3(gw), dim3(1024), 0, st, (const PyrTask*)d_tasks, ta, (const CopyTaskPod*)d_copy, need_copy ? 1u : 0u, w.arena,
-                         (G::CONVERTED_DOMAIN && ctx->opt_pyr_quad != 2) ? 1u : 0u);
+                         (G::CONVERTED_DOMAIN && ctx->opt.pyr_quad != 2) ? 1u : 0u);
     } else if (need_copy) {
       u32 cthreads = gw * (u32)(ptb / 16);
       hipLaunchKernelGGL(k_copy_points, dim3((cthreads + 63) / 64), dim3(64), 0, st, d_copy, 1u, gw, (u32)ptb, w.arena);
@@ -704,13 +734,13 @@ struct WinRun {
 // and leaves ONE block of records, where the slabs would otherwise each pay the ~0.3 ms latency chain of the tail and the
 // host add their records (option slab_tail = 2: a tail per slab, as before).  Up to 8 slabs (8 x 75 MB of bucket areas
 // per window group at c = 16); a function of the call's arguments and options alone, so every rank decides alike.
-bool shared_tail(const lemsm_ctx* ctx, size_t nslabs) { return nslabs > 1 && nslabs <= 8 && ctx->opt_slab_tail != 2 && ctx->opt_groups <= 1; }
+bool shared_tail(const lemsm_ctx* ctx, size_t nslabs) { return nslabs > 1 && nslabs <= 8 && ctx->opt.slab_tail != 2 && ctx->opt.groups <= 1; }
 
 // The part of run_windows_enqueue's bookkeeping that fixes what a rank sends in the exchange (device-pointer entries):
 // a function of the call's arguments and options alone, the same on every rank.
 template <class G>
 void win_sizes(const lemsm_ctx* ctx, size_t n, u32 nw_pad, u32 L, WinRun& wr) {
-  const u32 slab_log = ctx->opt_slab_bits ? (u32)ctx->opt_slab_bits : MAX_SLAB_LOG;
+  const u32 slab_log = ctx->opt.slab_bits ? (u32)ctx->opt.slab_bits : MAX_SLAB_LOG;
   wr.SLAB = (size_t)1 << slab_log;
   wr.nslabs = n ? (n + wr.SLAB - 1) / wr.SLAB : 1;
   wr.nrec = shared_tail(ctx, wr.nslabs) ? 1 : wr.nslabs;
@@ -745,7 +775,7 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
   // k+1 (upload queue, host blocked in the copy) overlaps the kernels of slab k (main queue).
   ctx->plan_ring = false;
   const HostStage* hs = ctx->host_stage;
-  u32 slab_log = ctx->opt_slab_bits ? (u32)ctx->opt_slab_bits : MAX_SLAB_LOG;
+  u32 slab_log = ctx->opt.slab_bits ? (u32)ctx->opt.slab_bits : MAX_SLAB_LOG;
   if (hs) slab_log = host_slab_log(ctx, n);
   const size_t SLAB = (size_t)1 << slab_log;
   const size_t nslabs = n ? (n + SLAB - 1) / SLAB : 1;
@@ -760,7 +790,7 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
   // measured (profiles/r01/pipelined_groups_trace.txt) this does NOT pay on MI355X: k_accum1 is
   // power-bound, so sort kernels running beside it slow it down by as much as they hide.
   u32 ngroups = 1;
-  if (ctx->opt_groups > 0) ngroups = std::min((u32)ctx->opt_groups, std::max(nw, 1u));
+  if (ctx->opt.groups > 0) ngroups = std::min((u32)ctx->opt.groups, std::max(nw, 1u));
   u32 gsz = std::max(1u, std::min(gmax, (nw + ngroups - 1) / ngroups));
   struct Grp { u32 g0, g1; size_t off; };
   std::vector<Grp> groups;
@@ -771,8 +801,8 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
     u32 sn0 = (u32)std::min(SLAB, n), snl = (u32)(n - (nslabs - 1) * SLAB);
     for (u32 g0 = wb; g0 < we; g0 += gsz) {
       u32 g1 = std::min(we, g0 + gsz);
-      size_t bytes = group_ws_bytes(ctx, make_group_plan(ctx, sn0, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt_ws_canary != 0, nba);
-      if (snl != sn0) bytes = std::max(bytes, group_ws_bytes(ctx, make_group_plan(ctx, snl, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt_ws_canary != 0, nba));
+      size_t bytes = group_ws_bytes(ctx, make_group_plan(ctx, sn0, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt.ws_canary != 0, nba);
+      if (snl != sn0) bytes = std::max(bytes, group_ws_bytes(ctx, make_group_plan(ctx, snl, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt.ws_canary != 0, nba));
       groups.push_back({g0, g1, ws_total});
       ws_total += align_up(bytes + 8192, 256);     // (+ slack for the 16-entry rounding of the accumulate chunk, see make_group_plan)
     }
@@ -798,7 +828,7 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
   }
   hipEvent_t* ev_up = ctx->evpool.data() + 3 * ng * nslabs;
   hipStream_t s_sort = ctx->stream_sort, s_acc = ctx->stream, s_tail = ctx->stream_tail;
-  const bool one_queue = ctx->opt_groups <= 1;
+  const bool one_queue = ctx->opt.groups <= 1;
   if (one_queue) { s_sort = s_acc; s_tail = s_acc; }   // one queue unless pipelining was asked for: exact event timing
   hipStream_t s_up = ctx->stream_sort;                 // upload queue of the host-pointer path (one_queue is forced there)
   if (hs && !one_queue) return fail(ctx, LEMSM_ERR_BAD_ARG, "option groups > 1 is only available on the device-pointer entries");
@@ -831,10 +861,10 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
       GroupPlan pl0 = make_group_plan(ctx, sn, c, nb, W, groups[0].g0, groups[0].g1, d);
       double S = std::max(1.0, std::min((double)pl0.L1, (double)sn / (double)nb));
       double P = 1.0 - std::pow(1.0 - 1.0 / S, 64.0);
-      abi = P * (double)(groups[0].g1 - groups[0].g0) < 7.0 && (ctx->opt_accum_waves == 0 || ctx->opt_accum_waves == 3);
-      if (ctx->opt_abi_points == 1) abi = false;
-      if (ctx->opt_abi_points == 2) abi = (ctx->opt_accum_waves == 0 || ctx->opt_accum_waves == 3);
-      ctx->plan_ring = abi && ctx->opt_entry_ring != 1;
+      abi = P * (double)(groups[0].g1 - groups[0].g0) < 7.0 && (ctx->opt.accum_waves == 0 || ctx->opt.accum_waves == 3);
+      if (ctx->opt.abi_points == 1) abi = false;
+      if (ctx->opt.abi_points == 2) abi = (ctx->opt.accum_waves == 0 || ctx->opt.accum_waves == 3);
+      ctx->plan_ring = abi && ctx->opt.entry_ring != 1;
       if (!abi) {
         if (one_queue && !hs) {
           // the conversion (HBM-bound, 2 x 64 B per point) runs on the second queue beside this slab's digit and sort passes
@@ -875,7 +905,7 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
 }
 
 // The queue the records of run_windows_enqueue become final on (where a collective or the read-back is enqueued).
-hipStream_t records_stream(const lemsm_ctx* ctx) { return ctx->opt_groups <= 1 ? ctx->stream : ctx->stream_tail; }
+hipStream_t records_stream(const lemsm_ctx* ctx) { return ctx->opt.groups <= 1 ? ctx->stream : ctx->stream_tail; }
 
 // This rank's own bookkeeping out of its status slots (host copy `slots`, wr.err_cap bytes): merge-queue counters, clock
 // stamps and accumulate timings of the last call.
@@ -1172,24 +1202,17 @@ int lhs_partial_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* 
 template <class P64>
 void lhs_combine_t(const LhsPlan& lp, const host::pt* sums, u64 out_carry[12], u64* out_carries) { lhs_combine_positions<P64>(lp.base, lp.d, sums, out_carry, out_carries); }
 
-// field selection: option "field" 0 = lazy radix-2^29 (default), 1 = strict 32-bit limbs
 int msm_partial_dispatch(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, u32 wb, u32 we,
                          std::vector<host::pt>& out) {
-  if (ctx->opt_field == 1) {
-    if (curve == LEMSM_BN254_G1) return msm_partial_t<host::FqParams64, GqStrict>(ctx, curve, d_scalars, d_points, n, wb, we, out);
-    return msm_partial_t<host::FrParams64, GrStrict>(ctx, curve, d_scalars, d_points, n, wb, we, out);
-  }
-  if (curve == LEMSM_BN254_G1) return msm_partial_t<host::FqParams64, GqLazy>(ctx, curve, d_scalars, d_points, n, wb, we, out);
-  return msm_partial_t<host::FrParams64, GrLazy>(ctx, curve, d_scalars, d_points, n, wb, we, out);
+  return with_arith(curve, ctx->opt, [&](auto cv, auto g) {
+    return msm_partial_t<typename decltype(cv)::P64, decltype(g)>(ctx, curve, d_scalars, d_points, n, wb, we, out);
+  });
 }
 int lhs_partial_dispatch(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, const LhsPlan& lp,
                          u32 pb, u32 pe, std::vector<host::pt>& out, size_t* bad_index) {
-  if (ctx->opt_field == 1) {
-    if (curve == LEMSM_BN254_G1) return lhs_partial_t<host::FqParams64, GqStrict>(ctx, curve, d_scalars, d_points, n, lp, pb, pe, out, bad_index);
-    return lhs_partial_t<host::FrParams64, GrStrict>(ctx, curve, d_scalars, d_points, n, lp, pb, pe, out, bad_index);
-  }
-  if (curve == LEMSM_BN254_G1) return lhs_partial_t<host::FqParams64, GqLazy>(ctx, curve, d_scalars, d_points, n, lp, pb, pe, out, bad_index);
-  return lhs_partial_t<host::FrParams64, GrLazy>(ctx, curve, d_scalars, d_points, n, lp, pb, pe, out, bad_index);
+  return with_arith(curve, ctx->opt, [&](auto cv, auto g) {
+    return lhs_partial_t<typename decltype(cv)::P64, decltype(g)>(ctx, curve, d_scalars, d_points, n, lp, pb, pe, out, bad_index);
+  });
 }
 
 // ---- multi-GPU: window / digit-position sharding with ONE all-gather of raw device records -------------------
@@ -1348,25 +1371,17 @@ int lhs_sharded_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* 
 int msm_sharded_dispatch(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, const Exchange& ex, u64 out[12]) {
   if (n == 0) { memset(out, 0, 96); return LEMSM_OK; }
   int saved = ctx->plan_world; ctx->plan_world = ex.world;
-  int rc;
-  if (ctx->opt_field == 1) {
-    rc = curve == LEMSM_BN254_G1 ? msm_sharded_t<host::FqParams64, GqStrict>(ctx, curve, d_scalars, d_points, n, ex, out)
-                                 : msm_sharded_t<host::FrParams64, GrStrict>(ctx, curve, d_scalars, d_points, n, ex, out);
-  } else {
-    rc = curve == LEMSM_BN254_G1 ? msm_sharded_t<host::FqParams64, GqLazy>(ctx, curve, d_scalars, d_points, n, ex, out)
-                                 : msm_sharded_t<host::FrParams64, GrLazy>(ctx, curve, d_scalars, d_points, n, ex, out);
-  }
+  int rc = with_arith(curve, ctx->opt, [&](auto cv, auto g) {
+    return msm_sharded_t<typename decltype(cv)::P64, decltype(g)>(ctx, curve, d_scalars, d_points, n, ex, out);
+  });
   ctx->plan_world = saved;
   return rc;
 }
 int lhs_sharded_dispatch(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, const LhsPlan& lp,
                          const Exchange& ex, u64 out_carry[12], u64* out_carries, size_t* bad_index) {
-  if (ctx->opt_field == 1) {
-    if (curve == LEMSM_BN254_G1) return lhs_sharded_t<host::FqParams64, GqStrict>(ctx, curve, d_scalars, d_points, n, lp, ex, out_carry, out_carries, bad_index);
-    return lhs_sharded_t<host::FrParams64, GrStrict>(ctx, curve, d_scalars, d_points, n, lp, ex, out_carry, out_carries, bad_index);
-  }
-  if (curve == LEMSM_BN254_G1) return lhs_sharded_t<host::FqParams64, GqLazy>(ctx, curve, d_scalars, d_points, n, lp, ex, out_carry, out_carries, bad_index);
-  return lhs_sharded_t<host::FrParams64, GrLazy>(ctx, curve, d_scalars, d_points, n, lp, ex, out_carry, out_carries, bad_index);
+  return with_arith(curve, ctx->opt, [&](auto cv, auto g) {
+    return lhs_sharded_t<typename decltype(cv)::P64, decltype(g)>(ctx, curve, d_scalars, d_points, n, lp, ex, out_carry, out_carries, bad_index);
+  });
 }
 
 template <class F>
@@ -1644,7 +1659,7 @@ __global__ __launch_bounds__(256) void k_validate_points(const uint4* __restrict
 }
 
 int validate_points(lemsm_ctx* ctx, int curve, const void* d_points, size_t n) {
-  if (!ctx->opt_validate_points || n == 0) return LEMSM_OK;
+  if (!ctx->opt.validate_points || n == 0) return LEMSM_OK;
   int rc = reserve(ctx, ctx->in_aux, 256); if (rc) return rc;
   u32 init = 0xffffffffu;
   HIPCHK(ctx, hipMemcpyAsync(ctx->in_aux.p, &init, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1652,8 +1667,10 @@ int validate_points(lemsm_ctx* ctx, int curve, const void* d_points, size_t n) {
   for (size_t s0 = 0; s0 < n; s0 += (size_t)1 << 30) {
     u32 cnt = (u32)std::min((size_t)1 << 30, n - s0);
     const uint4* p = (const uint4*)((const char*)d_points + s0 * 64);
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_validate_points<FqDev>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, p, cnt, 3, (u32*)ctx->in_aux.p);
-    else hipLaunchKernelGGL((k_validate_points<FrDev>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, p, cnt, -17, (u32*)ctx->in_aux.p);
+    with_curve(curve, [&](auto cv) {
+      typedef decltype(cv) C;
+      hipLaunchKernelGGL((k_validate_points<typename C::F>), dim3((cnt + 255) / 256), dim3(256), 0, ctx->stream, p, cnt, C::B, (u32*)ctx->in_aux.p);
+    });
     u32 bad = 0xffffffffu;
     HIPCHK(ctx, hipMemcpyAsync(&bad, ctx->in_aux.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1738,42 +1755,52 @@ void lemsm_destroy(lemsm_ctx* ctx) {
 
 const char* lemsm_last_error(const lemsm_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
 
+// name, field, accepted range [lo, hi], and whether 0 is accepted beside the range
+static const struct OptionRow { const char* name; long Options::*field; long lo, hi; bool or_zero; } OPTION_ROWS[] = {
+  {"window_bits", &Options::window_bits, 2, 17, true},
+  {"chunk", &Options::chunk, 0, 65536, false},
+  {"binsort", &Options::binsort, 0, LONG_MAX, false},
+  {"tile", &Options::tile, 256, LONG_MAX, true},
+  {"groups", &Options::groups, 0, 64, false},
+  {"merge_slice", &Options::merge_slice, 33, 65536, true},
+  {"merge_wave_th", &Options::merge_wave_th, 0, 1 << 24, false},
+  {"abi_points", &Options::abi_points, 0, 2, false},
+  {"pyr_fuse", &Options::pyr_fuse, 0, 2, false},
+  {"stage2x", &Options::stage2x, 0, 4, false},                // (but not 3: below)
+  {"dw_kb", &Options::dw_kb, 0, 64, false},
+  {"host_threads", &Options::host_threads, 0, 64, false},     // (resets the pool: below)
+  {"slab_bits", &Options::slab_bits, 12, 24, true},
+  {"host_slab_bits", &Options::host_slab_bits, 12, 24, true},
+  {"accum_waves", &Options::accum_waves, 2, 4, true},
+  {"pyr_first2", &Options::pyr_first2, 0, 1, false},
+  {"xcd_windows", &Options::xcd_windows, 0, 1, false},
+  {"ws_canary", &Options::ws_canary, 0, 1, false},
+  {"scatter_lean", &Options::scatter_lean, 0, 1, false},      // 1: k_scatter1 with two adjacent bins per thread (A/B knob: measured no faster)
+  {"validate_points", &Options::validate_points, 0, 1, false},
+  {"entry_ring", &Options::entry_ring, 0, 1, false},
+  {"dw_pw_lazy", &Options::dw_pw_lazy, 0, 1, false},
+  {"dw_halves", &Options::dw_halves, 0, 1, false},
+  {"dw_ntt_lazy", &Options::dw_ntt_lazy, 0, 1, false},
+  {"field", &Options::field, 0, 1, false},
+  {"dw_fuse", &Options::dw_fuse, 2, 2, true},
+  {"pyr_quad", &Options::pyr_quad, 2, 2, true},
+  {"slab_tail", &Options::slab_tail, 2, 2, true},
+  {"dw_reuse", &Options::dw_reuse, 2, 2, true},
+  {"dw_wrap", &Options::dw_wrap, 2, 2, true},
+  {"ntt_tiled", &Options::ntt_tiled, 2, 2, true},
+};
+
 int lemsm_set_option(lemsm_ctx* ctx, const char* name, long value) {
   if (!ctx || !name) return LEMSM_ERR_BAD_ARG;
-  if (!strcmp(name, "window_bits")) { if (value != 0 && (value < 2 || value > 17)) return LEMSM_ERR_BAD_ARG; ctx->opt_window_bits = value; }
-  else if (!strcmp(name, "chunk")) { if (value < 0 || value > 65536) return LEMSM_ERR_BAD_ARG; ctx->opt_chunk = value; }
-  else if (!strcmp(name, "binsort")) { if (value < 0) return LEMSM_ERR_BAD_ARG; ctx->opt_binsort = value; }
-  else if (!strcmp(name, "tile")) { if (value < 0 || (value && value < 256)) return LEMSM_ERR_BAD_ARG; ctx->opt_tile = value; }
-  else if (!strcmp(name, "groups")) { if (value < 0 || value > 64) return LEMSM_ERR_BAD_ARG; ctx->opt_groups = value; }
-  else if (!strcmp(name, "merge_slice")) { if (value != 0 && (value < 33 || value > 65536)) return LEMSM_ERR_BAD_ARG; ctx->opt_merge_slice = value; }
-  else if (!strcmp(name, "dbg_repeat")) { ctx->opt_dbg_repeat = value; }
-  else if (!strcmp(name, "pyr_first2")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_pyr_first2 = value; }
-  else if (!strcmp(name, "merge_wave_th")) { if (value < 0 || value > (1 << 24)) return LEMSM_ERR_BAD_ARG; ctx->opt_merge_wave_th = value; }
-  else if (!strcmp(name, "abi_points")) { if (value < 0 || value > 2) return LEMSM_ERR_BAD_ARG; ctx->opt_abi_points = value; }
-  else if (!strcmp(name, "stage2x")) { if (value < 0 || value > 4 || value == 3) return LEMSM_ERR_BAD_ARG; ctx->opt_stage2x = value; }
-  else if (!strcmp(name, "xcd_windows")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_xcd_windows = value; }
-  else if (!strcmp(name, "ws_canary")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_ws_canary = value; }
-  else if (!strcmp(name, "dw_kb")) { if (value < 0 || value > 64) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_kb = value; }
-  else if (!strcmp(name, "dw_fuse")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_fuse = value; }
-  else if (!strcmp(name, "dw_pw_lazy")) { if (value != 0 && value != 1) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_pw_lazy = value; }
-  else if (!strcmp(name, "scatter_lean")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_scatter_lean = value; }   // 1: k_scatter1 with two adjacent bins per thread (A/B knob: measured no faster)
-  else if (!strcmp(name, "pyr_quad")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_pyr_quad = value; }
-  else if (!strcmp(name, "slab_tail")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_slab_tail = value; }
-  else if (!strcmp(name, "dw_halves")) { if (value != 0 && value != 1) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_halves = value; }
-  else if (!strcmp(name, "dw_ntt_lazy")) { if (value != 0 && value != 1) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_ntt_lazy = value; }
-  else if (!strcmp(name, "dw_reuse")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_reuse = value; }
-  else if (!strcmp(name, "dw_wrap")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_dw_wrap = value; }
-  else if (!strcmp(name, "ntt_tiled")) { if (value != 0 && value != 2) return LEMSM_ERR_BAD_ARG; ctx->opt_ntt_tiled = value; }
-  else if (!strcmp(name, "pyr_fuse")) { if (value < 0 || value > 2) return LEMSM_ERR_BAD_ARG; ctx->opt_pyr_fuse = value; }
-  else if (!strcmp(name, "validate_points")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_validate_points = value; }
-  else if (!strcmp(name, "entry_ring")) { if (value < 0 || value > 1) return LEMSM_ERR_BAD_ARG; ctx->opt_entry_ring = value; }
-  else if (!strcmp(name, "slab_bits")) { if (value != 0 && (value < 12 || value > 24)) return LEMSM_ERR_BAD_ARG; ctx->opt_slab_bits = value; }
-  else if (!strcmp(name, "host_slab_bits")) { if (value != 0 && (value < 12 || value > 24)) return LEMSM_ERR_BAD_ARG; ctx->opt_host_slab_bits = value; }
-  else if (!strcmp(name, "accum_waves")) { if (value != 0 && (value < 2 || value > 4)) return LEMSM_ERR_BAD_ARG; ctx->opt_accum_waves = value; }
-  else if (!strcmp(name, "host_threads")) { if (value < 0 || value > 64) return LEMSM_ERR_BAD_ARG; ctx->opt_host_threads = value; ctx->pool.reset(); }
-  else if (!strcmp(name, "field")) { if (value != 0 && value != 1) return LEMSM_ERR_BAD_ARG; ctx->opt_field = value; }
-  else return LEMSM_ERR_BAD_ARG;
-  return LEMSM_OK;
+  for (const OptionRow& r : OPTION_ROWS) {
+    if (strcmp(name, r.name)) continue;
+    if (!((value >= r.lo && value <= r.hi) || (r.or_zero && value == 0))) return LEMSM_ERR_BAD_ARG;
+    if (r.field == &Options::stage2x && value == 3) return LEMSM_ERR_BAD_ARG;
+    ctx->opt.*r.field = value;
+    if (r.field == &Options::host_threads) ctx->pool.reset();
+    return LEMSM_OK;
+  }
+  return LEMSM_ERR_BAD_ARG;
 }
 
 size_t lemsm_last_bad_index(const lemsm_ctx* ctx) { return ctx ? ctx->bad_index : 0; }
@@ -1825,8 +1852,7 @@ int lemsm_msm_combine(const lemsm_ctx* ctx, int curve, size_t n, const uint8_t* 
   MsmPlan mp = make_msm_plan(ctx, curve, n);
   std::vector<host::pt> recs((size_t)mp.W);
   memcpy(recs.data(), partials, recs.size() * sizeof(host::pt));
-  if (curve == LEMSM_BN254_G1) msm_combine_t<host::FqParams64>(mp, recs.data(), out);
-  else msm_combine_t<host::FrParams64>(mp, recs.data(), out);
+  with_curve(curve, [&](auto cv) { msm_combine_t<typename decltype(cv)::P64>(mp, recs.data(), out); });
   return LEMSM_OK;
 }
 
@@ -1843,8 +1869,7 @@ int lemsm_msm_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const voi
   rc = msm_partial_dispatch(ctx, curve, d_scalars, d_points, n, 0, mp.W, sums);
   if (rc) return rc;
   const auto th0 = std::chrono::steady_clock::now();
-  if (curve == LEMSM_BN254_G1) msm_combine_t<host::FqParams64>(mp, sums.data(), out);
-  else msm_combine_t<host::FrParams64>(mp, sums.data(), out);
+  with_curve(curve, [&](auto cv) { msm_combine_t<typename decltype(cv)::P64>(mp, sums.data(), out); });
   ctx->host_us[3] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
   if (getenv("LEMSM_DEBUG_STAMPS")) fprintf(stderr, "[lemsm] host tail (us): device wait %.1f, records + window sums %.1f, (unused) %.1f, Horner %.1f\n", ctx->host_us[0], ctx->host_us[1], ctx->host_us[2], ctx->host_us[3]);
   return LEMSM_OK;
@@ -1860,7 +1885,7 @@ static int msm_batch_entry(lemsm_ctx* ctx, int curve, const void* const* d_scala
   for (size_t k = 0; k < batch; k++) if (h_scalars ? !h_scalars[k] : !d_scalars[k]) return LEMSM_ERR_BAD_ARG;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!(bases && bases->validated)) { rc = validate_points(ctx, curve, d_points, n); if (rc) return rc; }
-  if (ctx->opt_field == 1 || ctx->opt_groups > 1 || batch == 1) {       // A/B arithmetic, pipelined window groups, or nothing to overlap: one call after the other
+  if (ctx->opt.field == 1 || ctx->opt.groups > 1 || batch == 1) {       // A/B arithmetic, pipelined window groups, or nothing to overlap: one call after the other
     for (size_t k = 0; k < batch; k++) {
       rc = h_scalars ? lemsm_msm_with_bases(ctx, bases, h_scalars[k], n, outs + 12 * k) : lemsm_msm_device(ctx, curve, d_scalars[k], d_points, n, outs + 12 * k);
       if (rc) return rc;
@@ -1868,16 +1893,11 @@ static int msm_batch_entry(lemsm_ctx* ctx, int curve, const void* const* d_scala
     return LEMSM_OK;
   }
   if (!ctx->peer) { rc = lemsm_create(ctx->device, &ctx->peer); if (rc) return fail(ctx, rc, "lemsm_msm_batch_device: second lane could not be created"); }
-  {   // the peer plans exactly like the context
-    lemsm_ctx* p = ctx->peer;
-    p->opt_window_bits = ctx->opt_window_bits; p->opt_chunk = ctx->opt_chunk; p->opt_tile = ctx->opt_tile; p->opt_field = ctx->opt_field;
-    p->opt_accum_waves = ctx->opt_accum_waves; p->opt_groups = ctx->opt_groups; p->opt_slab_bits = ctx->opt_slab_bits; p->opt_abi_points = ctx->opt_abi_points;
-    p->opt_stage2x = ctx->opt_stage2x; p->opt_xcd_windows = ctx->opt_xcd_windows; p->opt_entry_ring = ctx->opt_entry_ring; p->opt_pyr_fuse = ctx->opt_pyr_fuse;
-    p->opt_ws_canary = ctx->opt_ws_canary; p->opt_binsort = ctx->opt_binsort; p->opt_merge_slice = ctx->opt_merge_slice; p->opt_merge_wave_th = ctx->opt_merge_wave_th;
-    p->opt_pyr_first2 = ctx->opt_pyr_first2; p->opt_host_threads = ctx->opt_host_threads; p->plan_world = ctx->plan_world; p->opt_slab_tail = ctx->opt_slab_tail; p->opt_pyr_quad = ctx->opt_pyr_quad; p->opt_scatter_lean = ctx->opt_scatter_lean;
-  }
-  if (curve == LEMSM_BN254_G1) return msm_batch_t<host::FqParams64, GqLazy>(ctx, curve, d_scalars, d_points, n, batch, outs, h_scalars);
-  return msm_batch_t<host::FrParams64, GrLazy>(ctx, curve, d_scalars, d_points, n, batch, outs, h_scalars);
+  ctx->peer->opt = ctx->opt; ctx->peer->plan_world = ctx->plan_world;   // the peer plans exactly like the context
+  return with_curve(curve, [&](auto cv) {
+    typedef decltype(cv) C;
+    return msm_batch_t<typename C::P64, typename C::GLazy>(ctx, curve, d_scalars, d_points, n, batch, outs, h_scalars);
+  });
 }
 
 int lemsm_msm_batch_device(lemsm_ctx* ctx, int curve, const void* const* d_scalars, size_t batch, const void* d_points, size_t n, uint64_t* outs) {
@@ -1894,7 +1914,7 @@ int lemsm_msm(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t*
   rc = reserve(ctx, ctx->in_s, n * 32); if (rc) return rc;
   rc = reserve(ctx, ctx->in_p, n * 64); if (rc) return rc;
   HostStage hs{scalars, points, (char*)ctx->in_s.p, (char*)ctx->in_p.p};
-  if (ctx->opt_validate_points) {   // validated inputs: the points are uploaded whole and checked before any slab runs
+  if (ctx->opt.validate_points) {   // validated inputs: the points are uploaded whole and checked before any slab runs
     HIPCHK(ctx, hipMemcpy(ctx->in_p.p, points, n * 64, hipMemcpyHostToDevice));
     hs.h_points = nullptr;
   }
@@ -2005,8 +2025,9 @@ int lemsm_table_entries(lemsm_ctx* ctx, int curve, uint8_t base, uint64_t id_beg
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = reserve(ctx, ctx->ws, count * 32 + 256); if (rc) return rc;
   dim3 grid((u32)((count + 255) / 256)), blk(256);
-  if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_table_entries<FqDev>), grid, blk, 0, ctx->stream, (u32)base, (unsigned long long)id_begin, (u32)count, (uint4*)ctx->ws.p);
-  else hipLaunchKernelGGL((k_table_entries<FrDev>), grid, blk, 0, ctx->stream, (u32)base, (unsigned long long)id_begin, (u32)count, (uint4*)ctx->ws.p);
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_table_entries<typename decltype(cv)::F>), grid, blk, 0, ctx->stream, (u32)base, (unsigned long long)id_begin, (u32)count, (uint4*)ctx->ws.p);
+  });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->ws.p, count * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2040,8 +2061,7 @@ int lemsm_lhs_combine(int curve, uint8_t base, const uint8_t* partials, uint64_t
   LhsPlan lp; int rc = make_lhs_plan(curve, base, lp); if (rc) return rc;
   std::vector<host::pt> recs((size_t)lp.d);
   memcpy(recs.data(), partials, recs.size() * sizeof(host::pt));
-  if (curve == LEMSM_BN254_G1) lhs_combine_t<host::FqParams64>(lp, recs.data(), out_carry, out_carries);
-  else lhs_combine_t<host::FrParams64>(lp, recs.data(), out_carry, out_carries);
+  with_curve(curve, [&](auto cv) { lhs_combine_t<typename decltype(cv)::P64>(lp, recs.data(), out_carry, out_carries); });
   return LEMSM_OK;
 }
 
@@ -2055,8 +2075,7 @@ int lemsm_lhs_msm_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const
   std::vector<host::pt> recs;
   rc = lhs_partial_dispatch(ctx, curve, d_scalars, d_points, n, lp, 0, lp.d, recs, bad_index);
   if (rc) return rc;
-  if (curve == LEMSM_BN254_G1) lhs_combine_t<host::FqParams64>(lp, recs.data(), out_carry, out_carries);
-  else lhs_combine_t<host::FrParams64>(lp, recs.data(), out_carry, out_carries);
+  with_curve(curve, [&](auto cv) { lhs_combine_t<typename decltype(cv)::P64>(lp, recs.data(), out_carry, out_carries); });
   return LEMSM_OK;
 }
 
@@ -2076,12 +2095,10 @@ int lemsm_lhs_msm(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint6
   rc = reserve(ctx, ctx->in_p, n ? n * 64 : 16); if (rc) return rc;
   if (n) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->ws.p, pts_jac, n * 96, hipMemcpyHostToDevice, ctx->stream));
-    if (curve == LEMSM_BN254_G1)
-      hipLaunchKernelGGL((k_jac_to_affine<FqDev, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)ctx->ws.p, (u32)n,
+    with_curve(curve, [&](auto cv) {
+      hipLaunchKernelGGL((k_jac_to_affine<typename decltype(cv)::F, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)ctx->ws.p, (u32)n,
                          (uint4*)ctx->in_p.p, (char*)ctx->ws.p + jac_bytes);
-    else
-      hipLaunchKernelGGL((k_jac_to_affine<FrDev, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)ctx->ws.p, (u32)n,
-                         (uint4*)ctx->in_p.p, (char*)ctx->ws.p + jac_bytes);
+    });
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the workspace is re-carved by the MSM below
   }
@@ -2187,8 +2204,8 @@ int lemsm_bases_upload(lemsm_ctx* ctx, int curve, const uint64_t* points_affine,
   if (e != hipSuccess) return fail(ctx, LEMSM_ERR_NOMEM, hipGetErrorString(e));
   if (n) { e = hipMemcpy(d, points_affine, n * 64, hipMemcpyHostToDevice); if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, LEMSM_ERR_HIP, hipGetErrorString(e)); } }
   // option validate_points: resident bases are checked ONCE, here, not on every call that uses them
-  if (ctx->opt_validate_points) { rc = validate_points(ctx, curve, d, n); if (rc) { (void)hipFree(d); return rc; } }
-  *out = new lemsm_bases{ctx, ctx->device, curve, n, d, ctx->opt_validate_points != 0};
+  if (ctx->opt.validate_points) { rc = validate_points(ctx, curve, d, n); if (rc) { (void)hipFree(d); return rc; } }
+  *out = new lemsm_bases{ctx, ctx->device, curve, n, d, ctx->opt.validate_points != 0};
   return LEMSM_OK;
 }
 void lemsm_bases_free(lemsm_bases* b) {
@@ -2209,10 +2226,10 @@ int lemsm_msm_with_bases(lemsm_ctx* ctx, const lemsm_bases* bases, const uint8_t
   int rc = reserve(ctx, ctx->in_s, n * 32); if (rc) return rc;
   HostStage hs{scalars, nullptr, (char*)ctx->in_s.p, (char*)bases->d_points};
   ctx->host_stage = &hs;
-  const long saved_validate = ctx->opt_validate_points;
-  if (bases->validated) ctx->opt_validate_points = 0;   // checked at upload
+  const long saved_validate = ctx->opt.validate_points;
+  if (bases->validated) ctx->opt.validate_points = 0;   // checked at upload
   rc = lemsm_msm_device(ctx, bases->curve, ctx->in_s.p, bases->d_points, n, out);
-  ctx->opt_validate_points = saved_validate;
+  ctx->opt.validate_points = saved_validate;
   ctx->host_stage = nullptr;
   return rc;
 }
@@ -2399,10 +2416,9 @@ int lemsm_precompute_multiplicities(lemsm_ctx* ctx, int curve, const uint64_t* p
   rc = reserve(ctx, ctx->ws, in_bytes + out_bytes + 256); if (rc) return rc;
   char* b = (char*)ctx->ws.p;
   HIPCHK(ctx, hipMemcpyAsync(b, pts_jac, n * 96, hipMemcpyHostToDevice, ctx->stream));
-  if (curve == LEMSM_BN254_G1)
-    hipLaunchKernelGGL((k_precompute_mult<FqDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)(b + in_bytes));
-  else
-    hipLaunchKernelGGL((k_precompute_mult<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)(b + in_bytes));
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_precompute_mult<typename decltype(cv)::F>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)(b + in_bytes));
+  });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, b + in_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2421,12 +2437,10 @@ int lemsm_precompute_multiplicities_affine(lemsm_ctx* ctx, int curve, const uint
   rc = reserve(ctx, ctx->ws, in_bytes + out_bytes + scr_bytes + 256); if (rc) return rc;
   char* b = (char*)ctx->ws.p;
   HIPCHK(ctx, hipMemcpyAsync(b, pts_jac, n * 96, hipMemcpyHostToDevice, ctx->stream));
-  if (curve == LEMSM_BN254_G1)
-    hipLaunchKernelGGL((k_precompute_mult_affine<FqDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base,
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_precompute_mult_affine<typename decltype(cv)::F>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base,
                        (uint4*)(b + in_bytes), b + in_bytes + out_bytes);
-  else
-    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base,
-                       (uint4*)(b + in_bytes), b + in_bytes + out_bytes);
+  });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, b + in_bytes, nm * 64, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2436,31 +2450,23 @@ int lemsm_precompute_multiplicities_affine(lemsm_ctx* ctx, int curve, const uint
 int lemsm_jacobian_to_canonical(int curve, const uint64_t jac[12], uint8_t out[64]) {
   if (!jac || !out) return LEMSM_ERR_BAD_ARG;
   if (curve != LEMSM_BN254_G1 && curve != LEMSM_GRUMPKIN) return LEMSM_ERR_BAD_CURVE;
-  u64 aff[8];
-  host::fe one_plain = {{1, 0, 0, 0}};
-  if (curve == LEMSM_BN254_G1) {
-    typedef host::HG<host::FqParams64> G; typedef host::HF<host::FqParams64> F;
+  with_curve(curve, [&](auto cv) {
+    typedef host::HG<typename decltype(cv)::P64> G; typedef host::HF<typename decltype(cv)::P64> F;
+    u64 aff[8];
+    const host::fe one_plain = {{1, 0, 0, 0}};
     host::pt p = G::from_jacobian(jac); G::to_affine(p, aff);
-    if (G::is_identity(p)) { memset(out, 0, 64); return LEMSM_OK; }
+    if (G::is_identity(p)) { memset(out, 0, 64); return; }
     host::fe x, y; memcpy(x.l, aff, 32); memcpy(y.l, aff + 4, 32);
     x = F::mul(x, one_plain); y = F::mul(y, one_plain);
     memcpy(out, x.l, 32); memcpy(out + 32, y.l, 32);
-  } else {
-    typedef host::HG<host::FrParams64> G; typedef host::HF<host::FrParams64> F;
-    host::pt p = G::from_jacobian(jac); G::to_affine(p, aff);
-    if (G::is_identity(p)) { memset(out, 0, 64); return LEMSM_OK; }
-    host::fe x, y; memcpy(x.l, aff, 32); memcpy(y.l, aff + 4, 32);
-    x = F::mul(x, one_plain); y = F::mul(y, one_plain);
-    memcpy(out, x.l, 32); memcpy(out + 32, y.l, 32);
-  }
+  });
   return LEMSM_OK;
 }
 
 int lemsm_jacobian_sum(int curve, const uint64_t* jac, size_t count, uint64_t out[12]) {
   if (!out || (count && !jac)) return LEMSM_ERR_BAD_ARG;
-  if (curve == LEMSM_BN254_G1) jacobian_sum_t<host::FqParams64>(jac, count, out);
-  else if (curve == LEMSM_GRUMPKIN) jacobian_sum_t<host::FrParams64>(jac, count, out);
-  else return LEMSM_ERR_BAD_CURVE;
+  if (curve != LEMSM_BN254_G1 && curve != LEMSM_GRUMPKIN) return LEMSM_ERR_BAD_CURVE;
+  with_curve(curve, [&](auto cv) { jacobian_sum_t<typename decltype(cv)::P64>(jac, count, out); });
   return LEMSM_OK;
 }
 
@@ -2503,10 +2509,9 @@ int lemsm_device_gen_walk(lemsm_ctx* ctx, int curve, const uint64_t q_affine[8],
   char* b = (char*)ctx->ws.p;
   HIPCHK(ctx, hipMemcpyAsync(b, q_affine, 64, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (curve == LEMSM_BN254_G1)
-    hipLaunchKernelGGL((k_gen_walk<FqDev, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (uint4*)d_out, b + 256);
-  else
-    hipLaunchKernelGGL((k_gen_walk<FrDev, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (uint4*)d_out, b + 256);
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_gen_walk<typename decltype(cv)::F, KB>), dim3((u32)(nthreads / 256)), dim3(256), 0, ctx->stream, (const uint4*)b, (u32)n, (uint4*)d_out, b + 256);
+  });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return LEMSM_OK;
@@ -2522,6 +2527,13 @@ static int dbg_run3(lemsm_ctx* ctx, const void* a, size_t abytes, const void* b,
   if (bbytes) HIPCHK(ctx, hipMemcpyAsync(*db, b, bbytes, hipMemcpyHostToDevice, ctx->stream));
   return LEMSM_OK;
 }
+// ... and the tail of a hook after its launch: launch status, the result back to the host, wait
+static int dbg_finish(lemsm_ctx* ctx, void* out, const void* dout, size_t obytes) {
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, dout, obytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return LEMSM_OK;
+}
 
 int lemsm_debug_montmul(lemsm_ctx* ctx, int curve, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   if (!ctx || !a || !b || !out) return LEMSM_ERR_BAD_ARG;
@@ -2531,15 +2543,14 @@ int lemsm_debug_montmul(lemsm_ctx* ctx, int curve, const uint64_t* a, const uint
   char *da, *db, *dout;
   rc = dbg_run3(ctx, a, n * 32, b, n * 32, n * 32, &da, &db, &dout); if (rc) return rc;
   dim3 g((u32)((n + 255) / 256)), blk(256);
-  if (ctx->opt_field == 0) {   // the hot kernels' default arithmetic
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_fieldop29<Field29<Fq29Params>>), g, blk, 0, ctx->stream, 8, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_fieldop29<Field29<Fr29Params>>), g, blk, 0, ctx->stream, 8, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  } else if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_montmul<FqDev>), g, blk, 0, ctx->stream, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  else hipLaunchKernelGGL((k_dbg_montmul<FrDev>), g, blk, 0, ctx->stream, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(out, dout, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  with_arith(curve, ctx->opt, [&](auto, auto gr) {
+    typedef decltype(gr) G;
+    if constexpr (G::CONVERTED_DOMAIN)   // the hot kernels' default arithmetic
+      hipLaunchKernelGGL((k_dbg_fieldop29<typename G::F_>), g, blk, 0, ctx->stream, 8, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
+    else
+      hipLaunchKernelGGL((k_dbg_montmul<typename G::F_>), g, blk, 0, ctx->stream, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
+  });
+  return dbg_finish(ctx, out, dout, n * 32);
 }
 
 int lemsm_debug_fieldop(lemsm_ctx* ctx, int curve, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
@@ -2550,19 +2561,19 @@ int lemsm_debug_fieldop(lemsm_ctx* ctx, int curve, int op, const uint64_t* a, co
   char *da, *db, *dout;
   rc = dbg_run3(ctx, a, n * 32, b, n * 32, n * 32, &da, &db, &dout); if (rc) return rc;
   dim3 g((u32)((n + 255) / 256)), blk(256);
-  if (ctx->opt_field == 0 && op == 3) {
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_inv_lazy<FqDev>), g, blk, 0, ctx->stream, (const uint4*)da, (uint4*)dout, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_inv_lazy<FrDev>), g, blk, 0, ctx->stream, (const uint4*)da, (uint4*)dout, (u32)n);
-  } else if (ctx->opt_field == 0) {
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_fieldop29<Field29<Fq29Params>>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_fieldop29<Field29<Fr29Params>>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  } else if (op > 4) return fail(ctx, LEMSM_ERR_BAD_ARG, "field ops 5..9 exist in the lazy field only (option field = 0)");
-  else if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_fieldop<FqDev>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  else hipLaunchKernelGGL((k_dbg_fieldop<FrDev>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(out, dout, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  rc = with_arith(curve, ctx->opt, [&](auto cv, auto gr) {
+    typedef decltype(gr) G; typedef typename decltype(cv)::F F;
+    if constexpr (G::CONVERTED_DOMAIN) {
+      if (op == 3) hipLaunchKernelGGL((k_dbg_inv_lazy<F>), g, blk, 0, ctx->stream, (const uint4*)da, (uint4*)dout, (u32)n);
+      else hipLaunchKernelGGL((k_dbg_fieldop29<typename G::F_>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
+    } else {
+      if (op > 4) return fail(ctx, LEMSM_ERR_BAD_ARG, "field ops 5..9 exist in the lazy field only (option field = 0)");
+      hipLaunchKernelGGL((k_dbg_fieldop<F>), g, blk, 0, ctx->stream, op, (const uint4*)da, (const uint4*)db, (uint4*)dout, (u32)n);
+    }
+    return (int)LEMSM_OK;
+  });
+  if (rc) return rc;
+  return dbg_finish(ctx, out, dout, n * 32);
 }
 
 int lemsm_debug_pointop(lemsm_ctx* ctx, int curve, int op, const uint64_t* acc, const uint64_t* q, uint64_t* out, size_t n) {
@@ -2575,15 +2586,12 @@ int lemsm_debug_pointop(lemsm_ctx* ctx, int curve, int op, const uint64_t* acc, 
   char *da, *db, *dout;
   rc = dbg_run3(ctx, acc, n * 128, q, n * qb, n * 128, &da, &db, &dout); if (rc) return rc;
   dim3 g((u32)((n + 63) / 64)), blk(64);
-  if (ctx->opt_field == 0) {
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_pointop29<GqLazy>), g, blk, 0, ctx->stream, op, da, db, dout, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_pointop29<GrLazy>), g, blk, 0, ctx->stream, op, da, db, dout, (u32)n);
-  } else if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_pointop<FqDev>), g, blk, 0, ctx->stream, op == 2 ? 0 : op, da, db, dout, (u32)n);
-  else hipLaunchKernelGGL((k_dbg_pointop<FrDev>), g, blk, 0, ctx->stream, op == 2 ? 0 : op, da, db, dout, (u32)n);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(out, dout, n * 128, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  with_arith(curve, ctx->opt, [&](auto, auto gr) {
+    typedef decltype(gr) G;
+    if constexpr (G::CONVERTED_DOMAIN) hipLaunchKernelGGL((k_dbg_pointop29<G>), g, blk, 0, ctx->stream, op, da, db, dout, (u32)n);
+    else hipLaunchKernelGGL((k_dbg_pointop<typename G::F_>), g, blk, 0, ctx->stream, op == 2 ? 0 : op, da, db, dout, (u32)n);
+  });
+  return dbg_finish(ctx, out, dout, n * 128);
 }
 
 int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
@@ -2605,12 +2613,10 @@ int lemsm_debug_field29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* a,
   const int32_t *da = (const int32_t*)base, *db = (const int32_t*)(base + o1), *dc = (const int32_t*)(base + o2), *dd = (const int32_t*)(base + o3);
   int32_t* dout = (int32_t*)(base + o4);
   dim3 g((u32)((n + 255) / 256)), blk(256);
-  if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_field29_raw<GqLazy>), g, blk, 0, ctx->stream, op, da, db, dc, dd, dout, (u32)n);
-  else hipLaunchKernelGGL((k_dbg_field29_raw<GrLazy>), g, blk, 0, ctx->stream, op, da, db, dc, dd, dout, (u32)n);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_dbg_field29_raw<typename decltype(cv)::GLazy>), g, blk, 0, ctx->stream, op, da, db, dc, dd, dout, (u32)n);
+  });
+  return dbg_finish(ctx, out, dout, ob);
 }
 
 int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc, const int32_t* q, int32_t* out, size_t n) {
@@ -2625,20 +2631,13 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
   rc = dbg_run3(ctx, acc, rb, q, rb, rb, &da, &db, &dout); if (rc) return rc;
   const int32_t *ia = (const int32_t*)da, *iq = (const int32_t*)db;
   int32_t* io = (int32_t*)dout;
-  if (op == LEMSM_X29_ADD4_MEM) {
-    HIPCHK(ctx, hipMemsetAsync(dout, 0, rb, ctx->stream));
-    dim3 g((u32)((4 * n + 63) / 64)), blk(64);
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_add4_raw<GqLazy>), g, blk, 0, ctx->stream, ia, iq, io, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_add4_raw<GrLazy>), g, blk, 0, ctx->stream, ia, iq, io, (u32)n);
-  } else {
-    dim3 g((u32)((n + 63) / 64)), blk(64);
-    if (curve == LEMSM_BN254_G1) hipLaunchKernelGGL((k_dbg_xyzz29_raw<GqLazy>), g, blk, 0, ctx->stream, op, ia, iq, io, (u32)n);
-    else hipLaunchKernelGGL((k_dbg_xyzz29_raw<GrLazy>), g, blk, 0, ctx->stream, op, ia, iq, io, (u32)n);
-  }
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(out, dout, rb, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  if (op == LEMSM_X29_ADD4_MEM) HIPCHK(ctx, hipMemsetAsync(dout, 0, rb, ctx->stream));
+  with_curve(curve, [&](auto cv) {
+    typedef typename decltype(cv)::GLazy G;
+    if (op == LEMSM_X29_ADD4_MEM) hipLaunchKernelGGL((k_dbg_add4_raw<G>), dim3((u32)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream, ia, iq, io, (u32)n);
+    else hipLaunchKernelGGL((k_dbg_xyzz29_raw<G>), dim3((u32)((n + 63) / 64)), dim3(64), 0, ctx->stream, op, ia, iq, io, (u32)n);
+  });
+  return dbg_finish(ctx, out, dout, rb);
 }
 
 }  // extern "C"

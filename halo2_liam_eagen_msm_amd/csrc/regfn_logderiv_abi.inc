@@ -244,9 +244,8 @@ int lemsm_debug_regfn_deriv(lemsm_ctx* ctx, const uint64_t* coeffs, size_t cap_c
 int lemsm_argument_residual(int curve, const uint64_t lhs_sum[4], const uint64_t carry_jacobian[12], const uint64_t rhs_sum[4],
                             const uint64_t a_xy[8], const uint64_t t[4], uint64_t out[4]) {
   if (!lhs_sum || !carry_jacobian || !rhs_sum || !a_xy || !t || !out) return LEMSM_ERR_BAD_ARG;
-  if (curve == LEMSM_BN254_G1) return residual_t<host::FqParams64>(lhs_sum, carry_jacobian, rhs_sum, a_xy, t, out);
-  if (curve == LEMSM_GRUMPKIN) return residual_t<host::FrParams64>(lhs_sum, carry_jacobian, rhs_sum, a_xy, t, out);
-  return LEMSM_ERR_BAD_CURVE;
+  if (curve != LEMSM_BN254_G1 && curve != LEMSM_GRUMPKIN) return LEMSM_ERR_BAD_CURVE;
+  return with_curve(curve, [&](auto cv) { return residual_t<typename decltype(cv)::P64>(lhs_sum, carry_jacobian, rhs_sum, a_xy, t, out); });
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // The right-hand side of the argument (include/lemsm.h: lemsm_rhs_*, lemsm_multiples_table_device, lemsm_fraction_sums*):
 // the running sums of the reference's "rhs main" gate (src/config.rs:504-538) and of its lookup columns (:402-437).
 // Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, stage, HIPCHK, fail, align_up, make_lhs_plan,
-// bound_of, k_precompute_mult_affine); the kernels are rhs.cuh's.
+// with_curve, k_precompute_mult_affine); the kernels are rhs.cuh's.
 
 namespace {
 
@@ -107,21 +107,29 @@ void rhs_power_table(u32 base, u32 d, std::vector<u32>& pw) {
   }
 }
 
-template <class F, class P, class P64>
-int rhs_device_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, const RhsPlan& pl, uint8_t base, const uint64_t a_xy[8],
-                 const uint64_t t[4], const uint64_t* init, void* d_out_running, uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index) {
+template <class P64>
+void fs_sum_host(const uint64_t* totals, size_t chains, uint64_t out_sum[4]) {
   typedef host::HF<P64> HF;
+  host::fe s = HF::zero();
+  for (size_t k = 0; k < chains; k++) { host::fe v; memcpy(v.l, totals + 4 * k, 32); s = HF::add(s, v); }
+  memcpy(out_sum, s.l, 32);
+}
+
+template <class C>   // the curve's traits
+int rhs_device_t(lemsm_ctx* ctx, const void* d_scalars, const void* d_table, const RhsPlan& pl, uint8_t base, const uint64_t a_xy[8],
+                 const uint64_t t[4], const uint64_t* init, void* d_out_running, uint64_t* out_totals, uint64_t out_sum[4], size_t* bad_index) {
+  typedef typename C::F F; typedef host::HF<typename C::P64> HF;
   const size_t nb = (size_t)base - 1;
   const FsGeom g = fs_geom(pl.num_terms, nb);
   std::vector<u32> pw; rhs_power_table(base, pl.d, pw);
   int rc = reserve(ctx, ctx->rhs_pw, pw.size() * 4 + 256); if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->rhs_pw.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  fs::RhsSrc<F, P> src;
+  fs::RhsSrc<F, typename C::P> src;
   src.scalars = (const uint4*)d_scalars; src.table = (const uint4*)d_table; src.pw = (const u32*)ctx->rhs_pw.p;
   src.nb = (u32)nb; src.base = base; src.d = pl.d;
   host::fe ax, ay, tt; memcpy(ax.l, a_xy, 32); memcpy(ay.l, a_xy + 4, 32); memcpy(tt.l, t, 32);
   const host::fe f = HF::sub(HF::mul(tt, ax), ay);                // f = t Ax - Ay (src/config.rs:519)
-  memcpy(src.c.ax, ax.l, 32); memcpy(src.c.t, tt.l, 32); memcpy(src.c.f, f.l, 32); memcpy(src.c.bound, bound_of(curve), 32);
+  memcpy(src.c.ax, ax.l, 32); memcpy(src.c.t, tt.l, 32); memcpy(src.c.f, f.l, 32); memcpy(src.c.bound, C::BOUND, 32);
   std::vector<uint64_t> totals_tmp;
   uint64_t* totals = out_totals;
   if (!totals) { totals_tmp.resize(nb * 4); totals = totals_tmp.data(); }
@@ -133,20 +141,8 @@ int rhs_device_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d
     return fail(ctx, LEMSM_ERR_SCALAR_OUT_OF_RANGE, "scalar out of range (>= isqrt(order)+2)");
   }
   if (err_den != ~0ull) return fs_div_by_zero(ctx, err_den, bad_index, "rhs witness: a multiple k P_j with a non-zero bucket lies on the line through A (k P_j in {A, -2A}): the gate of src/config.rs:524 has no solution");
-  if (out_sum) {
-    host::fe s = HF::zero();
-    for (size_t k = 0; k < nb; k++) { host::fe v; memcpy(v.l, totals + 4 * k, 32); s = HF::add(s, v); }
-    memcpy(out_sum, s.l, 32);
-  }
+  if (out_sum) fs_sum_host<typename C::P64>(totals, nb, out_sum);
   return LEMSM_OK;
-}
-
-template <class P64>
-void fs_sum_host(const uint64_t* totals, size_t chains, uint64_t out_sum[4]) {
-  typedef host::HF<P64> HF;
-  host::fe s = HF::zero();
-  for (size_t k = 0; k < chains; k++) { host::fe v; memcpy(v.l, totals + 4 * k, 32); s = HF::add(s, v); }
-  memcpy(out_sum, s.l, 32);
 }
 
 }  // namespace
@@ -176,13 +172,11 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   rc = reserve(ctx, ctx->ws, in_bytes + scr_bytes + 256); if (rc) return rc;
   char* b = (char*)ctx->ws.p;
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
-  if (curve == LEMSM_BN254_G1) {
-    hipLaunchKernelGGL((fs::k_affine_to_jacobian<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
-    hipLaunchKernelGGL((k_precompute_mult_affine<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
-  } else {
-    hipLaunchKernelGGL((fs::k_affine_to_jacobian<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
-    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
-  }
+  with_curve(curve, [&](auto cv) {
+    typedef typename decltype(cv)::F F;
+    hipLaunchKernelGGL((fs::k_affine_to_jacobian<F>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
+    hipLaunchKernelGGL((k_precompute_mult_affine<F>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
+  });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return LEMSM_OK;
@@ -202,15 +196,15 @@ int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, c
     std::vector<uint64_t> tot(nb * 4);
     fs_totals_of_init(init, nb, tot.data());
     if (out_totals) memcpy(out_totals, tot.data(), nb * 32);
-    if (out_sum) { if (curve == LEMSM_BN254_G1) fs_sum_host<host::FqParams64>(tot.data(), nb, out_sum); else fs_sum_host<host::FrParams64>(tot.data(), nb, out_sum); }
+    if (out_sum) with_curve(curve, [&](auto cv) { fs_sum_host<typename decltype(cv)::P64>(tot.data(), nb, out_sum); });
     return LEMSM_OK;
   }
   if (!d_scalars || !d_table) return LEMSM_ERR_BAD_ARG;
   if (n >= ((size_t)1 << 28)) return fail(ctx, LEMSM_ERR_BAD_ARG, "n too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (curve == LEMSM_BN254_G1)
-    return rhs_device_t<FqDev, FqParams, host::FqParams64>(ctx, curve, d_scalars, d_table, pl, base, a_xy, t, init, d_out_running, out_totals, out_sum, bad_index);
-  return rhs_device_t<FrDev, FrParams, host::FrParams64>(ctx, curve, d_scalars, d_table, pl, base, a_xy, t, init, d_out_running, out_totals, out_sum, bad_index);
+  return with_curve(curve, [&](auto cv) {
+    return rhs_device_t<decltype(cv)>(ctx, d_scalars, d_table, pl, base, a_xy, t, init, d_out_running, out_totals, out_sum, bad_index);
+  });
 }
 
 int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n, uint8_t base,
@@ -231,10 +225,9 @@ int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const u
   char* tab = (char*)ctx->rhs_tab.p;
   char* d_run = out_running ? tab + tab_bytes : nullptr;
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
-  if (curve == LEMSM_BN254_G1)
-    hipLaunchKernelGGL((k_precompute_mult_affine<FqDev>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
-  else
-    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
+  with_curve(curve, [&](auto cv) {
+    hipLaunchKernelGGL((k_precompute_mult_affine<typename decltype(cv)::F>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
+  });
   HIPCHK(ctx, hipGetLastError());
   rc = lemsm_rhs_witness_device(ctx, curve, ctx->in_s.p, tab, n, base, a_xy, t, init, d_run, out_totals, out_sum, bad_index);
   if (rc) return rc;
@@ -262,13 +255,11 @@ int lemsm_fraction_sums_device(lemsm_ctx* ctx, int curve, const void* d_num, con
   uint64_t* totals = out_totals;
   if (!totals) { totals_tmp.resize(chains * 4); totals = totals_tmp.data(); }
   u64 err_den = ~0ull, err_range = ~0ull;
-  if (curve == LEMSM_BN254_G1) {
-    fs::ArraySrc<FqDev> src; src.num = (const uint4*)d_num; src.den = (const uint4*)d_den;
-    rc = fs_run<FqDev>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range);
-  } else {
-    fs::ArraySrc<FrDev> src; src.num = (const uint4*)d_num; src.den = (const uint4*)d_den;
-    rc = fs_run<FrDev>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range);
-  }
+  rc = with_curve(curve, [&](auto cv) {
+    typedef typename decltype(cv)::F F;
+    fs::ArraySrc<F> src; src.num = (const uint4*)d_num; src.den = (const uint4*)d_den;
+    return fs_run<F>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range);
+  });
   if (rc) return rc;
   if (err_den != ~0ull) return fs_div_by_zero(ctx, err_den, bad_index, "fraction sums: a zero denominator under a non-zero numerator (the lookup gate of src/config.rs:402-437 has no solution)");
   return LEMSM_OK;

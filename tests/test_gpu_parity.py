@@ -11,7 +11,7 @@ import pytest
 
 from helpers import (CURVES, canon, golden_points_raw, golden_scalars, int_of, jacobian_with_random_z, limbs4,
                      load_json, regenerate_chain_digests)
-from halo2_liam_eagen_msm_amd import api
+from halo2_liam_eagen_msm_amd import _lib, api
 from oracle import cref, pyref
 
 pytestmark = pytest.mark.gpu
@@ -410,6 +410,125 @@ def test_msm_batch_with_bases_host_scalars(ctx, curve):
     again = ctx.msm_batch_with_bases(bases, scs[:2])
     for k in range(2):
         assert canon(curve, again[k]) == canon(curve, got[k])
+
+
+# every setting of a batch call the second lane has to inherit (or that sends the batch down its serial path): (options)
+BATCH_SETTINGS = [
+    {"window_bits": 8}, {"chunk": 3}, {"tile": 256}, {"accum_waves": 2}, {"slab_bits": 12}, {"abi_points": 1}, {"abi_points": 2},
+    {"xcd_windows": 1}, {"entry_ring": 1, "abi_points": 2}, {"pyr_fuse": 1}, {"pyr_first2": 1}, {"pyr_quad": 2}, {"binsort": 2},
+    {"merge_slice": 33, "chunk": 4}, {"merge_wave_th": 1}, {"scatter_lean": 1}, {"slab_tail": 2, "slab_bits": 12}, {"host_threads": 1},
+    {"ws_canary": 1}, {"stage2x": 2}, {"field": 1}, {"groups": 2},
+]
+
+
+@pytest.fixture(scope="module")
+def batch_case(ctx):
+    """Grumpkin, 7000 points, 3 scalar vectors (both lanes, lane 0 twice; two slabs at slab_bits = 12, the second ragged):
+    inputs on the host and on the device, and the oracle's results, computed once"""
+    curve = pyref.GRUMPKIN
+    n = 7000
+    pts = cref.gen_points(curve.cid, 990, n)
+    scs = [cref.gen_scalars(curve.cid, 991 + k, n) for k in range(3)]
+    exp = [canon(curve, cref.best_multiexp(curve.cid, s, pts, 8)) for s in scs]
+    return curve, n, pts, scs, exp, ctx.to_device(pts), [ctx.to_device(s) for s in scs], ctx.bases_upload(curve.cid, pts)
+
+
+@pytest.mark.parametrize("opts", BATCH_SETTINGS, ids=lambda o: "-".join("%s%d" % kv for kv in o.items()))
+def test_msm_batch_entries_under_options(ctx, batch_case, opts):
+    """both batch entries under every option the second lane inherits, all others at their defaults: for every k the
+    oracle's best_multiexp and a single lemsm_msm_device call under the same options.  (field 1 and groups 2 send the
+    batch down its serial path.)  One combination has no result to compare: pipelined window groups exist on the
+    device-pointer entries only (lemsm.h), so under groups 2 the serial path of lemsm_msm_batch_with_bases returns
+    LEMSM_ERR_BAD_ARG exactly as the lemsm_msm_with_bases calls it stands for do; that is pinned instead."""
+    curve, n, pts, scs, exp, dp, dss, bases = batch_case
+    host_entry_rejects = opts.get("groups", 0) > 1
+    try:
+        for name, value in opts.items():
+            ctx.set_option(name, value)
+        single = [canon(curve, ctx.msm_device(curve.cid, d.ptr, dp.ptr, n)) for d in dss]
+        got_dev = ctx.msm_batch_device(curve.cid, [d.ptr for d in dss], dp.ptr, n)
+        if host_entry_rejects:
+            for call in (lambda: ctx.msm_with_bases(bases, scs[0]), lambda: ctx.msm_batch_with_bases(bases, scs)):
+                with pytest.raises(api.LemsmError) as e:
+                    call()
+                assert e.value.status == _lib.LEMSM_ERR_BAD_ARG
+            got_host = None
+        else:
+            got_host = ctx.msm_batch_with_bases(bases, scs)
+    finally:
+        for name in opts:
+            ctx.set_option(name, 0)
+    for k in range(3):
+        for entry, got in (("lemsm_msm_batch_device", got_dev), ("lemsm_msm_batch_with_bases", got_host)):
+            if got is None:
+                continue
+            assert canon(curve, got[k]) == exp[k], (entry, k)
+            assert canon(curve, got[k]) == single[k], (entry, k)
+
+
+# lemsm_set_option: (names, accepted, rejected)
+OPTION_VALUES = [
+    (["window_bits"], [0, 2, 17], [1, 18, -1]),
+    (["chunk"], [0, 65536], [-1, 65537]),
+    (["binsort"], [0, 2, 36865], [-1]),
+    (["tile"], [0, 256, 100000], [1, 255, -1]),
+    (["groups"], [0, 64], [-1, 65]),
+    (["merge_slice"], [0, 33, 65536], [1, 32, 65537]),
+    (["merge_wave_th"], [0, 1 << 24], [-1, (1 << 24) + 1]),
+    (["abi_points", "pyr_fuse"], [0, 1, 2], [3, -1]),
+    (["stage2x"], [0, 1, 2, 4], [3, 5, -1]),
+    (["dw_kb"], [0, 64], [-1, 65]),
+    (["host_threads"], [0, 64], [-1, 65]),
+    (["slab_bits", "host_slab_bits"], [0, 12, 24], [1, 11, 25]),
+    (["accum_waves"], [0, 2, 4], [1, 5]),
+    (["pyr_first2", "xcd_windows", "ws_canary", "scatter_lean", "validate_points", "entry_ring", "dw_pw_lazy", "dw_halves", "dw_ntt_lazy",
+      "field"], [0, 1], [2, -1]),
+    (["dw_fuse", "pyr_quad", "slab_tail", "dw_reuse", "dw_wrap", "ntt_tiled"], [0, 2], [1, 3, -1]),
+]
+
+
+def test_set_option_acceptance_table(ctx):
+    """lemsm_set_option accepts exactly these values per name (no kernel runs); a rejected value is LEMSM_ERR_BAD_ARG and
+    the call after it is accepted.  That the rejected value was not stored is observed for the three options an entry
+    shows without a launch: window_bits and slab_bits through lemsm_msm_plan, field through lemsm_debug_fieldop, whose
+    ops 5..9 the strict field refuses before it launches anything.  The other names share the same code path; nothing
+    shows their value without running a kernel."""
+    def rejected(name, value):
+        with pytest.raises(api.LemsmError) as e:
+            ctx.set_option(name, value)
+        assert e.value.status == _lib.LEMSM_ERR_BAD_ARG, (name, value)
+    names = [n for group, _, _ in OPTION_VALUES for n in group]
+    try:
+        for group, good, bad in OPTION_VALUES:
+            for name in group:
+                for v in good:
+                    ctx.set_option(name, v)
+                for v in bad:
+                    ctx.set_option(name, good[-1])
+                    rejected(name, v)
+                    ctx.set_option(name, good[0])
+        auto = ctx.msm_plan(api.GRUMPKIN, 1 << 20)[0]
+        ctx.set_option("window_bits", 8)
+        windows = ctx.msm_plan(api.GRUMPKIN, 1 << 20)[0]
+        assert windows != auto
+        rejected("window_bits", 18)
+        assert ctx.msm_plan(api.GRUMPKIN, 1 << 20)[0] == windows
+        ctx.set_option("window_bits", 0); ctx.set_option("slab_bits", 12)      # 2^12-point passes: narrower windows, more of them
+        windows = ctx.msm_plan(api.GRUMPKIN, 1 << 20)[0]
+        assert windows != auto
+        rejected("slab_bits", 25)
+        assert ctx.msm_plan(api.GRUMPKIN, 1 << 20)[0] == windows
+        ctx.set_option("slab_bits", 0)
+        one = np.array([limbs4(1)], np.uint64)
+        ctx.set_option("field", 1)
+        rejected("field", 2)
+        with pytest.raises(api.LemsmError) as e:       # still the strict field
+            ctx.debug_fieldop(api.GRUMPKIN, 5, one, one)
+        assert e.value.status == _lib.LEMSM_ERR_BAD_ARG
+        rejected("no_such_option", 0)
+    finally:
+        for name in names:
+            ctx.set_option(name, 0)
 
 
 def test_msm_all_zero_scalars_and_all_identity_points(fctx):
