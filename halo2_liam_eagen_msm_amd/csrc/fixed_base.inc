@@ -189,6 +189,9 @@ struct FixedProvider {
   }
 };
 
+// h folded windows over n * m virtual points; the group plan's W is h + 1 so that PipDec decodes every window as signed
+WinGeom fixed_geom(const FixedPlan& fp) { const u32 nb = 1u << (fp.c - 1); return {fp.c, nb, nb, ilog2(nb), fp.h + 1, 0}; }
+
 }  // namespace
 
 struct lemsm_fixed_bases { lemsm_ctx* ctx; int device; int curve; size_t n; FixedPlan plan; void* d_table; };   // `device`: as lemsm_bases
@@ -198,16 +201,14 @@ namespace {
 template <class P64, class G>
 int msm_fixed_t(lemsm_ctx* ctx, const lemsm_fixed_bases* fb, const void* d_scalars, size_t n, u64 out[12]) {
   const FixedPlan& fp = fb->plan;
-  const u32 nb = 1u << (fp.c - 1), L = ilog2(nb);
   auto make_src = [&](size_t s0, u32) {
     FixedProvider p; p.scalars = (const uint4*)d_scalars;
     memcpy(p.fa.kadd.k, fp.kadd, 32); memcpy(p.fa.kadd.order, order_of(fb->curve), 32);
     p.fa.m = fp.m; p.fa.h = fp.h; p.fa.W = fp.W; p.fa.i0 = (u32)(s0 / fp.m); p.fa.k0 = (u32)(s0 % fp.m);
     return p;
   };
-  // h folded windows over n * m virtual points; the group plan's W is h + 1 so that PipDec decodes every window as signed
   std::vector<host::pt> sums;
-  int rc = run_windows<P64, G>(ctx, make_src, n * fp.m, fp.c, nb, nb, L, fp.h + 1, 0, fp.h, 0, fb->d_table, sums, true);
+  int rc = run_windows<P64, G>(ctx, make_src, n * fp.m, fixed_geom(fp), 0, fp.h, fb->d_table, sums, true);
   if (rc == LEMSM_ERR_SCALAR_OUT_OF_RANGE) ctx->bad_index /= fp.m;   // virtual index i * m of the first offending base
   if (rc) return rc;
   msm_combine_windows<P64>(fp.c, fp.h, sums.data(), out);   // Horner over the h folded windows (nothing to shift at h = 1)

@@ -238,11 +238,13 @@ u32 logb_ceil8(const u32* x, u32 base) {   // src/argument_witness_calc.rs:32-40
 u32 next_pow2(u32 x) { u32 p = 1; while (p < x) p <<= 1; return p; }
 u32 ilog2(u32 x) { u32 l = 0; while ((1u << l) < x) l++; return l; }
 
+// The window geometry of one call, as every stage of the bucket pipeline reads it: c window bits (0: negabase digits), nb
+// buckets per window, nbp = nb padded to a power of two = 2^L, W windows or digit positions of the whole call, d the
+// negabase digit count (0 on the Pippenger path).
+struct WinGeom { u32 c, nb, nbp, L, W, d; };
+
 // ---- MSM plan (Pippenger, signed windows) ----
-struct MsmPlan {
-  u32 c, W, nb, nbp, L;
-  u32 kadd[8];
-};
+struct MsmPlan : WinGeom { u32 kadd[8]; };
 
 // window bits for an n-point MSM: 16 for large n (2-byte windows, 16 windows of 2^15 buckets
 // for 254-bit scalars: divisible by 1/2/4/8 GPUs); fewer for small n so buckets are not mostly empty.
@@ -391,13 +393,14 @@ GroupWs carve(char* base, const GroupPlan& pl, const ArenaLayout& ar, const MqLa
 // local bucket bits of a pass-1 entry: <= 256 coarse bins per window (512 at nb = 2^16) -- and 512 as well when 256 bins
 // would hold more entries each (n / bins for uniform digits) than one k_binsort block can take: at 2^24 points and
 // 16-bit windows (the window-sharded multi-GPU plan) that halves the bins to 2^15 entries and keeps pass 2 in one block
-u32 choose_lb(const lemsm_ctx* ctx, u32 nb, u32 n, u32 d) {
+u32 choose_lb(const lemsm_ctx* ctx, const WinGeom& wg, u32 n) {
+  const u32 nb = wg.nb;
   // one geometry per call: a ragged last slab must not pick MORE bins per window than the full slabs the window groups
   // were sized for (found by the fuzz soak with a 3-entry test capacity: 20 windows x 512 bins > MAX_BINS)
   if (ctx && ctx->plan_slab_n) n = ctx->plan_slab_n;
   u32 LB = 0;
   while (((nb + (1u << LB) - 1) >> LB) > 256 && LB < MAX_LB) LB++;
-  if (d == 0 && ctx && ctx->opt.binsort != 2 && LB > 0) {
+  if (wg.d == 0 && ctx && ctx->opt.binsort != 2 && LB > 0) {
     const u32 cap = ctx->opt.binsort > 2 ? std::min((u32)ctx->opt.binsort, (u32)BIN_CAP) : (u32)BIN_CAP;
     const u32 BW = (nb + (1u << LB) - 1) >> LB;
     if ((u64)n / BW > (u64)cap * 9 / 10 && 2 * BW <= BW_MAX && (u64)n / (2 * BW) <= (u64)cap * 9 / 10) LB--;
@@ -405,10 +408,11 @@ u32 choose_lb(const lemsm_ctx* ctx, u32 nb, u32 n, u32 d) {
   return LB;
 }
 
-GroupPlan make_group_plan(const lemsm_ctx* ctx, u32 n, u32 c, u32 nb, u32 W, u32 w0, u32 w1, u32 d) {
+GroupPlan make_group_plan(const lemsm_ctx* ctx, const WinGeom& wg, u32 n, u32 w0, u32 w1) {
+  const u32 nb = wg.nb, d = wg.d;
   GroupPlan g; memset(&g, 0, sizeof g);
-  g.n = n; g.c = c; g.nb = nb; g.W = W; g.w0 = w0; g.w1 = w1; g.d = d; g.nstride = n;   // run_windows sets nstride to the call's n
-  u32 LB = choose_lb(ctx, nb, n, d);
+  g.n = n; g.c = wg.c; g.nb = nb; g.W = wg.W; g.w0 = w0; g.w1 = w1; g.d = d; g.nstride = n;   // run_windows sets nstride to the call's n
+  u32 LB = choose_lb(ctx, wg, n);
   g.LB = LB;
   g.BW = (nb + (1u << LB) - 1) >> LB;
   g.nbw = g.BW << LB;
@@ -450,9 +454,9 @@ GroupPlan make_group_plan(const lemsm_ctx* ctx, u32 n, u32 c, u32 nb, u32 W, u32
 }
 
 // max windows per group: (w1-w0) * BW <= MAX_BINS
-u32 max_group_windows(const lemsm_ctx* ctx, u32 nb, u32 n, u32 d) {
-  u32 LB = choose_lb(ctx, nb, n, d);
-  u32 BW = (nb + (1u << LB) - 1) >> LB;
+u32 max_group_windows(const lemsm_ctx* ctx, const WinGeom& wg, u32 n) {
+  u32 LB = choose_lb(ctx, wg, n);
+  u32 BW = (wg.nb + (1u << LB) - 1) >> LB;
   u32 cap = MAX_BINS / BW;
   return cap == 0 ? 1 : cap;
 }
@@ -511,7 +515,7 @@ __global__ __launch_bounds__(256) void k_group_finish(const uint4* __restrict__ 
 // Runs one window group [w0,w1): sort + accumulate + reduce; results (gw x (L+1) XYZZ points)
 // are left in the arena's out area and copied to d_out (device) + gslot.
 template <class G, class Prov>
-int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u32 L, const void* d_points,
+int run_group(lemsm_ctx* ctx, const Prov& prov, const WinGeom& wg, const GroupPlan& pl, const void* d_points,
               bool abi /* d_points are in the C ABI's domain: k_accum1<.., true>, scaled outputs */,
               char* ws_base, char* d_out /* device, gw*(L+1)*PT_BYTES */, u32* d_slot /* device, this (slab, group)'s 64-byte status slot */, hipStream_t s_sort, hipStream_t s_acc,
               hipStream_t s_tail, hipEvent_t ev_sorted, hipEvent_t ev_acc0, hipEvent_t ev_acc1,
@@ -522,6 +526,7 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
   // (s_sort), the accumulate kernels of all groups run back to back (s_acc), and this group's
   // edge-record levels + pyramid overlap the next group's accumulation (s_tail).
   hipStream_t st = s_sort;
+  const u32 nbp = wg.nbp, L = wg.L;
   u32 gw = pl.w1 - pl.w0;
   u32 NBpad = pl.nbins << pl.LB;
   ArenaLayout ar = make_arena(NBpad, nbp, gw, L, nba);
@@ -704,20 +709,19 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const GroupPlan& pl, u32 nbp, u3
   return LEMSM_OK;
 }
 
-size_t group_ws_bytes(const lemsm_ctx* ctx, const GroupPlan& pl, u32 nbp, u32 L, size_t ptb, bool guard, u32 nba = 1) {
+size_t group_ws_bytes(const lemsm_ctx* ctx, const WinGeom& wg, const GroupPlan& pl, size_t ptb, bool guard, u32 nba = 1) {
   u32 gw = pl.w1 - pl.w0;
-  ArenaLayout ar = make_arena(pl.nbins << pl.LB, nbp, gw, L, nba);
+  ArenaLayout ar = make_arena(pl.nbins << pl.LB, wg.nbp, gw, wg.L, nba);
   GroupWs w = carve(nullptr, pl, ar, make_mq_layout(ctx, pl.nthr1), ptb, guard);
   return w.total + 4096;
 }
 
-// Generic windowed bucket pipeline over window range [wb,we): fills host_out with
-// (we-wb) x (L+1) XYZZ points, summed over slabs.
-
 // One call's raw per-window records on the device: nslabs blocks of out_slab bytes, block k holding the
 // records [total, U_0..U_{L-1}] of windows wb.. of slab k (nw_pad windows' worth of room, unused tail zeroed).
 struct WinRun {
-  size_t nslabs = 0, ng = 0, out_slab = 0, SLAB = 0, err_slot = 0;
+  size_t nslabs = 0, ng = 0, out_slab = 0, SLAB = 0;
+  // a status slot, one per (slab, group): err[2] of the digit pass, then k_accum1's clock stamps (4 x u64) at byte 16
+  static constexpr size_t err_slot = 96;
   size_t nrec = 0;         // record blocks: nslabs, or 1 when the slabs share one tail (shared_tail())
   size_t err_stride = 1;   // status slots per slab: nw_pad, the same on every rank whatever its own number of window groups
   size_t err_cap = 0;      // bytes of the status-slot area (nslabs x err_stride slots, rounded up)
@@ -736,17 +740,23 @@ struct WinRun {
 // per window group at c = 16); a function of the call's arguments and options alone, so every rank decides alike.
 bool shared_tail(const lemsm_ctx* ctx, size_t nslabs) { return nslabs > 1 && nslabs <= 8 && ctx->opt.slab_tail != 2 && ctx->opt.groups <= 1; }
 
-// The part of run_windows_enqueue's bookkeeping that fixes what a rank sends in the exchange (device-pointer entries):
-// a function of the call's arguments and options alone, the same on every rank.
+// Sizes a call's record area: the slabs, and with them what a rank sends in the exchange.  A function of the call's
+// arguments and options alone, the same on every rank; run_windows_enqueue takes every size from here, and so does a
+// rank that failed before the pipeline and only sends a stand-in of the agreed size.
+//
+// The slab choice is made here too.  Slabs of points: every slab runs the whole pipeline and the per-window records
+// of the slabs are added on the host.  Device-resident inputs use the largest slab the 32-bit entry format allows;
+// host-pointer entries (ctx->host_stage) use small slabs so that the PCIe upload of slab k+1 (upload queue, host
+// blocked in the copy) overlaps the kernels of slab k (main queue).
 template <class G>
-void win_sizes(const lemsm_ctx* ctx, size_t n, u32 nw_pad, u32 L, WinRun& wr) {
-  const u32 slab_log = ctx->opt.slab_bits ? (u32)ctx->opt.slab_bits : MAX_SLAB_LOG;
+void win_sizes(const lemsm_ctx* ctx, size_t n, const WinGeom& wg, u32 nw_pad, WinRun& wr) {
+  const u32 slab_log = ctx->host_stage ? host_slab_log(ctx, n) : ctx->opt.slab_bits ? (u32)ctx->opt.slab_bits : MAX_SLAB_LOG;
   wr.SLAB = (size_t)1 << slab_log;
   wr.nslabs = n ? (n + wr.SLAB - 1) / wr.SLAB : 1;
   wr.nrec = shared_tail(ctx, wr.nslabs) ? 1 : wr.nslabs;
-  wr.ptb = G::PT_BYTES; wr.L = L; wr.nw_pad = nw_pad; wr.nw = 0; wr.ng = 0;
-  wr.out_slab = align_up((size_t)std::max(nw_pad, 1u) * (L + 1) * wr.ptb, 256);
-  wr.err_slot = 96; wr.err_stride = std::max<size_t>(nw_pad, 1);
+  wr.ptb = G::PT_BYTES; wr.L = wg.L; wr.nw_pad = nw_pad; wr.nw = 0; wr.ng = 0;
+  wr.out_slab = align_up((size_t)std::max(nw_pad, 1u) * (wg.L + 1) * wr.ptb, 256);   // one slab's records
+  wr.err_stride = std::max<size_t>(nw_pad, 1);      // slot (slab k, group gi) = k * err_stride + gi, gi < ng <= nw <= nw_pad
   wr.err_cap = align_up(wr.nslabs * wr.err_stride * wr.err_slot, 256);
   wr.d_out = nullptr; wr.d_err = nullptr;
 }
@@ -765,26 +775,21 @@ void comm_abort(lemsm_ctx* ctx) {
 // raw records in the workspace (wr.d_out); nothing is read back.  nw_pad >= we - wb sizes the record area per slab
 // (multi-GPU: the same for every rank, so that the all-gather sends equal counts).
 template <class P64, class G, class MakeSrc>
-int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u32 nbp, u32 L, u32 W, u32 wb, u32 we, u32 d,
-                        const void* d_points, u32 nw_pad, WinRun& wr) {
-  u32 nw = we - wb;
+int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, const WinGeom& wg, u32 wb, u32 we, const void* d_points,
+                        u32 nw_pad, WinRun& wr) {
+  const u32 nw = we - wb, L = wg.L;
   if (nw_pad < nw) nw_pad = nw;
-  // Slabs of points: every slab runs the whole pipeline and the per-window records of the slabs
-  // are added on the host.  Device-resident inputs use the largest slab the 32-bit entry format
-  // allows; host-pointer entries (ctx->host_stage) use small slabs so that the PCIe upload of slab
-  // k+1 (upload queue, host blocked in the copy) overlaps the kernels of slab k (main queue).
+  // sizes first (a rank that fails below still has to contribute a buffer of the agreed size to the collective)
+  win_sizes<G>(ctx, n, wg, nw_pad, wr);
+  wr.nw = nw;
+  const size_t SLAB = wr.SLAB, nslabs = wr.nslabs, nrec = wr.nrec, ptb = wr.ptb;
+  const size_t out_slab = wr.out_slab, err_stride = wr.err_stride, err_bytes = wr.err_cap;
   ctx->plan_ring = false;
   const HostStage* hs = ctx->host_stage;
-  u32 slab_log = ctx->opt.slab_bits ? (u32)ctx->opt.slab_bits : MAX_SLAB_LOG;
-  if (hs) slab_log = host_slab_log(ctx, n);
-  const size_t SLAB = (size_t)1 << slab_log;
-  const size_t nslabs = n ? (n + SLAB - 1) / SLAB : 1;
-  const bool shared = shared_tail(ctx, nslabs);
+  const bool shared = nrec < nslabs;     // the slabs share one tail (shared_tail())
   const u32 nba = shared ? (u32)nslabs : 1u;
-  const size_t nrec = shared ? 1 : nslabs;
   ctx->plan_slab_n = (u32)std::min(SLAB, n);
-  u32 gmax = max_group_windows(ctx, nb, ctx->plan_slab_n, d);
-  const size_t ptb = G::PT_BYTES;
+  u32 gmax = max_group_windows(ctx, wg, ctx->plan_slab_n);
   // Window groups of this call.  Default: as few as the bin limit allows (one at c = 16).  With
   // option "groups" > 1 the sort / accumulate / tail of neighbouring groups run on three queues;
   // measured (profiles/r01/pipelined_groups_trace.txt) this does NOT pay on MI355X: k_accum1 is
@@ -801,21 +806,14 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
     u32 sn0 = (u32)std::min(SLAB, n), snl = (u32)(n - (nslabs - 1) * SLAB);
     for (u32 g0 = wb; g0 < we; g0 += gsz) {
       u32 g1 = std::min(we, g0 + gsz);
-      size_t bytes = group_ws_bytes(ctx, make_group_plan(ctx, sn0, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt.ws_canary != 0, nba);
-      if (snl != sn0) bytes = std::max(bytes, group_ws_bytes(ctx, make_group_plan(ctx, snl, c, nb, W, g0, g1, d), nbp, L, ptb, ctx->opt.ws_canary != 0, nba));
+      size_t bytes = group_ws_bytes(ctx, wg, make_group_plan(ctx, wg, sn0, g0, g1), ptb, ctx->opt.ws_canary != 0, nba);
+      if (snl != sn0) bytes = std::max(bytes, group_ws_bytes(ctx, wg, make_group_plan(ctx, wg, snl, g0, g1), ptb, ctx->opt.ws_canary != 0, nba));
       groups.push_back({g0, g1, ws_total});
       ws_total += align_up(bytes + 8192, 256);     // (+ slack for the 16-entry rounding of the accumulate chunk, see make_group_plan)
     }
   }
-  const size_t ng = groups.size();
-  const size_t out_slab = align_up((size_t)std::max(nw_pad, 1u) * (L + 1) * ptb, 256);   // one slab's records
-  const size_t ERR_SLOT = 96;   // (win_sizes: the same) per (slab, group): err[2] of the digit pass, then k_accum1's clock stamps (4 x u64) at byte 16
-  const size_t err_stride = std::max<size_t>(nw_pad, 1);      // slot (slab k, group gi) = k * err_stride + gi, gi < ng <= nw <= nw_pad
-  const size_t err_bytes = align_up(nslabs * err_stride * ERR_SLOT, 256);
+  const size_t ng = wr.ng = groups.size();
   size_t conv_bytes = G::CONVERTED_DOMAIN ? align_up(std::min(SLAB, n) * 64, 256) : 0;
-  // sizes first (a rank that fails below still has to contribute a buffer of the agreed size to the collective)
-  wr.nslabs = nslabs; wr.nrec = nrec; wr.ng = ng; wr.out_slab = out_slab; wr.SLAB = SLAB; wr.err_slot = ERR_SLOT; wr.err_stride = err_stride; wr.err_cap = err_bytes;
-  wr.nw = nw; wr.nw_pad = nw_pad; wr.L = L; wr.ptb = ptb;
   int rc = reserve(ctx, ctx->ws, ws_total + conv_bytes + out_slab * nrec + err_bytes + WinRun::STATUS_BYTES + 4096);
   if (rc) return rc;
   char* ws_base = (char*)ctx->ws.p;
@@ -858,8 +856,8 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
     hipEvent_t ev_points = nullptr;
     ctx->plan_ring = false;
     if constexpr (G::CONVERTED_DOMAIN) {
-      GroupPlan pl0 = make_group_plan(ctx, sn, c, nb, W, groups[0].g0, groups[0].g1, d);
-      double S = std::max(1.0, std::min((double)pl0.L1, (double)sn / (double)nb));
+      GroupPlan pl0 = make_group_plan(ctx, wg, sn, groups[0].g0, groups[0].g1);
+      double S = std::max(1.0, std::min((double)pl0.L1, (double)sn / (double)wg.nb));
       double P = 1.0 - std::pow(1.0 - 1.0 / S, 64.0);
       abi = P * (double)(groups[0].g1 - groups[0].g0) < 7.0 && (ctx->opt.accum_waves == 0 || ctx->opt.accum_waves == 3);
       if (ctx->opt.abi_points == 1) abi = false;
@@ -883,13 +881,13 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 n
     }
     for (size_t gi = 0; gi < ng; gi++) {
       const Grp& gr = groups[gi];
-      GroupPlan pl = make_group_plan(ctx, sn, c, nb, W, gr.g0, gr.g1, d);
+      GroupPlan pl = make_group_plan(ctx, wg, sn, gr.g0, gr.g1);
       pl.nstride = (u32)n;   // negabase digit matrix: d rows of n columns, whatever the slab (lhs_partial_t bounds n < 2^32)
       auto src = make_src(s0, sn);
       hipEvent_t* ev = ctx->evpool.data() + 3 * (k * ng + gi);
       if (gi == 0 && abi) scaled_mask |= 1u << k;
-      rc = run_group<G>(ctx, src, pl, nbp, L, pts, abi, ws_base + gr.off, d_out + (shared ? 0 : k) * out_slab + (size_t)(gr.g0 - wb) * (L + 1) * ptb,
-                        (u32*)(d_err + (k * err_stride + gi) * ERR_SLOT), s_sort, s_acc, s_tail, ev[0], ev[1], ev[2], gi == 0 ? ev_points : nullptr,
+      rc = run_group<G>(ctx, src, wg, pl, pts, abi, ws_base + gr.off, d_out + (shared ? 0 : k) * out_slab + (size_t)(gr.g0 - wb) * (L + 1) * ptb,
+                        (u32*)(d_err + (k * err_stride + gi) * WinRun::err_slot), s_sort, s_acc, s_tail, ev[0], ev[1], ev[2], gi == 0 ? ev_points : nullptr,
                         shared ? (u32)k : 0u, nba, scaled_mask);
       if (rc) return rc;
     }
@@ -976,10 +974,6 @@ int run_windows_finish(lemsm_ctx* ctx, const WinRun& wr, const char* d_raw, size
   return collect_local_stats(ctx, wr, slots.data());
 }
 
-
-template <class P64, class G>
-void from_device_records(const char* raw, size_t n, host::pt* out) { from_device_records_t<P64, G::CONVERTED_DOMAIN, G::PT_BYTES>(raw, n, out); }
-
 // host: records of nw windows = sum over the slabs of one rank's record area (raw: nslabs blocks of out_slab bytes)
 template <class P64, class G>
 void sum_slab_records(lemsm_ctx* ctx, const char* raw, size_t out_slab, size_t nslabs, u32 nw, u32 L, std::vector<host::pt>& host_out,
@@ -992,7 +986,7 @@ void sum_slab_records(lemsm_ctx* ctx, const char* raw, size_t out_slab, size_t n
     std::vector<host::pt> tmp(L + 1), acc(L + 1);
     host::pt* dst = fold ? acc.data() : host_out.data() + (size_t)w * (L + 1);
     for (size_t k = 0; k < nslabs; k++) {
-      from_device_records<P64, G>(raw + k * out_slab + (size_t)w * (L + 1) * ptb, L + 1, tmp.data());
+      from_device_records_t<P64, G::CONVERTED_DOMAIN, G::PT_BYTES>(raw + k * out_slab + (size_t)w * (L + 1) * ptb, L + 1, tmp.data());
       if (k == 0) memcpy(dst, tmp.data(), (L + 1) * sizeof(host::pt));
       else for (u32 i = 0; i <= L; i++) dst[i] = HGp::add(dst[i], tmp[i]);
     }
@@ -1003,14 +997,14 @@ void sum_slab_records(lemsm_ctx* ctx, const char* raw, size_t out_slab, size_t n
 // Generic windowed bucket pipeline over window range [wb,we): fills host_out with
 // (we-wb) x (L+1) XYZZ points, summed over slabs.
 template <class P64, class G, class MakeSrc>
-int run_windows(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u32 nbp, u32 L, u32 W, u32 wb, u32 we, u32 d,
-                const void* d_points, std::vector<host::pt>& host_out, bool fold = false /* window sums instead of records */) {
+int run_windows(lemsm_ctx* ctx, MakeSrc make_src, size_t n, const WinGeom& wg, u32 wb, u32 we, const void* d_points,
+                std::vector<host::pt>& host_out, bool fold = false /* window sums instead of records */) {
   typedef host::HG<P64> HGp;
-  u32 nw = we - wb;
+  const u32 nw = we - wb, L = wg.L;
   host_out.assign(fold ? (size_t)nw : (size_t)nw * (L + 1), HGp::identity());
   if (n == 0 || nw == 0) return LEMSM_OK;
   WinRun wr;
-  int rc = run_windows_enqueue<P64, G>(ctx, make_src, n, c, nb, nbp, L, W, wb, we, d, d_points, nw, wr);
+  int rc = run_windows_enqueue<P64, G>(ctx, make_src, n, wg, wb, we, d_points, nw, wr);
   if (rc) return rc;
   std::vector<char> raw;
   rc = run_windows_finish(ctx, wr, wr.d_out, wr.send_bytes(), raw);
@@ -1028,22 +1022,21 @@ void window_sums_par(lemsm_ctx* ctx, const host::pt* recs /* nw x (L+1) */, u32 
   host_parallel(ctx, (int)nw, [&](int w) { out[w] = window_sum<P64>(recs + (size_t)w * (L + 1), L); });
 }
 
-template <class P64>
-void msm_combine_t(const MsmPlan& mp, const host::pt* sums /* W window sums */, u64 out[12]) { msm_combine_windows<P64>(mp.c, mp.W, sums, out); }
+// the Pippenger digit source of the slab that starts at pair s0: its scalars, the plan's window offsets, the curve's order
+auto pip_source(const void* d_scalars, const MsmPlan& mp, int curve) {
+  PipProvider p; p.scalars = (const uint4*)d_scalars;
+  memcpy(p.kadd.k, mp.kadd, 32); memcpy(p.kadd.order, order_of(curve), 32);
+  return [p](size_t s0, u32) { PipProvider s = p; s.scalars += 2 * s0; return s; };
+}
 
 template <class P64, class G>
 int msm_partial_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, u32 wb, u32 we,
                   std::vector<host::pt>& out) {
   MsmPlan mp = make_msm_plan(ctx, curve, n);
   if (wb > we || we > mp.W) return fail(ctx, LEMSM_ERR_BAD_ARG, "window range out of bounds");
-  auto make_src = [&](size_t s0, u32) {
-    PipProvider s; s.scalars = (const uint4*)((const char*)d_scalars + s0 * 32);
-    memcpy(s.kadd.k, mp.kadd, 32); memcpy(s.kadd.order, order_of(curve), 32); return s;
-  };
   // conversion of the raw records and this rank's share of the host tail (S_w = total + sum_l 2^l U_l for its own
   // windows) in one pool job per window
-  int rc = run_windows<P64, G>(ctx, make_src, n, mp.c, mp.nb, mp.nbp, mp.L, mp.W, wb, we, 0, d_points, out, true);
-  return rc;
+  return run_windows<P64, G>(ctx, pip_source(d_scalars, mp, curve), n, mp, wb, we, d_points, out, true);
 }
 
 // K MSMs over the same points, pipelined over two lanes (the context and its peer: own queues, workspace, pinned buffer):
@@ -1068,10 +1061,6 @@ int msm_batch_t(lemsm_ctx* ctx, int curve, const void* const* d_scalars, const v
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_batch_up, 0));
       sc = c->in_s.p;
     }
-    auto make_src = [&](size_t s0, u32) {
-      PipProvider s; s.scalars = (const uint4*)((const char*)sc + s0 * 32);
-      memcpy(s.kadd.k, mp.kadd, 32); memcpy(s.kadd.order, order_of(curve), 32); return s;
-    };
     c->wait_accum = nullptr;
     if (k > 0) {
       lemsm_ctx* o = lane[(k - 1) & 1]; const WinRun& w = wr[(k - 1) & 1];
@@ -1082,7 +1071,7 @@ int msm_batch_t(lemsm_ctx* ctx, int curve, const void* const* d_scalars, const v
       if (h_scalars) c->wait_accum = o->ev_call_done;
       else if (w.ng && w.nslabs && o->evpool.size() >= 3 * w.ng * w.nslabs) c->wait_accum = o->evpool[3 * (w.ng * w.nslabs - 1) + 2];
     }
-    int rce = run_windows_enqueue<P64, G>(c, make_src, n, mp.c, mp.nb, mp.nbp, mp.L, mp.W, 0, mp.W, 0, d_points, mp.W, wr[k & 1]);
+    int rce = run_windows_enqueue<P64, G>(c, pip_source(sc, mp, curve), n, mp, 0, mp.W, d_points, mp.W, wr[k & 1]);
     c->wait_accum = nullptr;
     if (!rce && h_scalars) {
       if (!c->ev_call_done) HIPCHK(c, hipEventCreateWithFlags(&c->ev_call_done, hipEventDisableTiming));
@@ -1097,7 +1086,7 @@ int msm_batch_t(lemsm_ctx* ctx, int curve, const void* const* d_scalars, const v
     if (rc) { ctx->last_error = c->last_error; ctx->bad_index = c->bad_index; return rc; }
     std::vector<host::pt> sums;
     sum_slab_records<P64, G>(ctx, raw.data(), wr[k & 1].out_slab, wr[k & 1].nrec, mp.W, mp.L, sums, true);
-    msm_combine_t<P64>(mp, sums.data(), outs + 12 * k);
+    msm_combine_windows<P64>(mp.c, mp.W, sums.data(), outs + 12 * k);
     return LEMSM_OK;
   };
   int rc = LEMSM_OK; size_t enq = 0;
@@ -1131,10 +1120,10 @@ int stage(lemsm_ctx* ctx, DevBuf& b, const void* host, size_t bytes) {
 }
 
 // ---- lhs (negabase) plan ----
-struct LhsPlan { u32 base, d, nb, nbp, L; };
+struct LhsPlan : WinGeom { u32 base; };     // (c = 0; every digit position is a window: W = d)
 int make_lhs_plan(int curve, u32 base, LhsPlan& lp) {
   if (base < 3) return LEMSM_ERR_BAD_BASE;
-  lp.base = base; lp.d = logb_ceil8(bound_of(curve), base) + 1;
+  lp.base = base; lp.c = 0; lp.W = lp.d = logb_ceil8(bound_of(curve), base) + 1;
   lp.nb = base - 1; lp.nbp = next_pow2(lp.nb); if (lp.nbp < 2) lp.nbp = 2;
   lp.L = ilog2(lp.nbp);
   return LEMSM_OK;
@@ -1146,12 +1135,19 @@ struct Words12 { u32 w[12]; };
 __global__ void k_set_words12(u32* __restrict__ dst, Words12 v) { if (threadIdx.x < 12) dst[threadIdx.x] = v.w[threadIdx.x]; }
 
 // the range-check words of the digit pass (first offending index, truncation count) travel to the context's small
-// pinned buffer right behind the digit kernel; lhs_err_words waits for that copy (long done when the MSM core returns)
-int lhs_err_words(lemsm_ctx* ctx, size_t n, u32 err[2]) {
-  err[0] = 0xffffffffu; err[1] = 0;
-  if (!n) return LEMSM_OK;
-  HIPCHK(ctx, hipEventSynchronize(ctx->ev[4]));
-  err[0] = ctx->h_small[0]; err[1] = ctx->h_small[1];
+// pinned buffer right behind the digit kernel; lhs_range_check, the tail of both lhs paths, waits for that copy (long
+// done when the MSM core returns)
+int lhs_range_check(lemsm_ctx* ctx, size_t n, size_t* bad_index) {
+  u32 err[2] = {0xffffffffu, 0};
+  if (n) {
+    HIPCHK(ctx, hipEventSynchronize(ctx->ev[4]));
+    err[0] = ctx->h_small[0]; err[1] = ctx->h_small[1];
+  }
+  ctx->truncated = err[1];
+  if (err[0] != 0xffffffffu) {
+    if (bad_index) *bad_index = err[0];
+    return fail(ctx, LEMSM_ERR_SCALAR_OUT_OF_RANGE, "scalar out of range (>= isqrt(order)+2)");
+  }
   return LEMSM_OK;
 }
 
@@ -1187,20 +1183,10 @@ int lhs_partial_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* 
   if (rc) return rc;
   // the digit matrix is position-major over the whole n; slabs index it with an offset
   auto make_src = [&](size_t s0, u32) { NegProvider s; s.digitsT = dg.digitsT + s0; return s; };
-  rc = run_windows<P64, G>(ctx, make_src, n, 0, lp.nb, lp.nbp, lp.L, lp.d, pb, pe, lp.d, d_points, out, true);
+  rc = run_windows<P64, G>(ctx, make_src, n, lp, pb, pe, d_points, out, true);
   if (rc) return rc;
-  u32 err[2];
-  { int rce = lhs_err_words(ctx, n, err); if (rce) return rce; }
-  ctx->truncated = err[1];
-  if (err[0] != 0xffffffffu) {
-    if (bad_index) *bad_index = err[0];
-    return fail(ctx, LEMSM_ERR_SCALAR_OUT_OF_RANGE, "scalar out of range (>= isqrt(order)+2)");
-  }
-  return LEMSM_OK;
+  return lhs_range_check(ctx, n, bad_index);
 }
-
-template <class P64>
-void lhs_combine_t(const LhsPlan& lp, const host::pt* sums, u64 out_carry[12], u64* out_carries) { lhs_combine_positions<P64>(lp.base, lp.d, sums, out_carry, out_carries); }
 
 int msm_partial_dispatch(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, u32 wb, u32 we,
                          std::vector<host::pt>& out) {
@@ -1239,8 +1225,9 @@ int validate_points(lemsm_ctx* ctx, int curve, const void* d_points, size_t n); 
 // shared by the MSM and the lhs path: runs the rank's (or, simulated, every rank's) windows and returns the records of
 // ALL W windows (W x (L+1) host points, slabs summed)
 template <class P64, class G, class MakeSrc>
-int sharded_records(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u32 nbp, u32 L, u32 W, u32 d, const void* d_points,
+int sharded_records(lemsm_ctx* ctx, MakeSrc make_src, size_t n, const WinGeom& wg, const void* d_points,
                     const Exchange& ex, std::vector<host::pt>& all, int rc_pre = LEMSM_OK /* a failure of this rank before the pipeline */) {
+  const u32 W = wg.W, L = wg.L;
   u32 max_nw = 0;
   for (int r = 0; r < ex.world; r++) { u32 a, b; shard_range(W, ex.world, r, a, b); max_nw = std::max(max_nw, b - a); }
   WinRun wr; std::vector<char> raw;
@@ -1254,8 +1241,8 @@ int sharded_records(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u
     // return the same status -- also a rank without windows of its own (world > W), which runs no digit pass.
     u32 a, b; shard_range(W, ex.world, ex.rank, a, b);
     int rc_local = rc_pre;
-    if (!rc_local) rc_local = run_windows_enqueue<P64, G>(ctx, make_src, n, c, nb, nbp, L, W, a, b, d, d_points, max_nw, wr);
-    else win_sizes<G>(ctx, n, max_nw, L, wr);      // the sizes every rank agrees on, without touching the device
+    if (!rc_local) rc_local = run_windows_enqueue<P64, G>(ctx, make_src, n, wg, a, b, d_points, max_nw, wr);
+    else win_sizes<G>(ctx, n, wg, max_nw, wr);      // the sizes every rank agrees on, without touching the device
     sb = wr.send_total();
     hipStream_t st = records_stream(ctx);
     const char* send = wr.d_out;
@@ -1298,7 +1285,7 @@ int sharded_records(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u
     double t_total = 0, t_acc = 0; int n_acc = 0;
     for (int r = 0; r < ex.world; r++) {
       u32 a, b; shard_range(W, ex.world, r, a, b);
-      int rc = run_windows_enqueue<P64, G>(ctx, make_src, n, c, nb, nbp, L, W, a, b, d, d_points, max_nw, wr);
+      int rc = run_windows_enqueue<P64, G>(ctx, make_src, n, wg, a, b, d_points, max_nw, wr);
       if (rc) return rc;
       sb = wr.send_total();      // records + status slots + rank status, as the collective moves them
       if (r == 0) { rc = reserve(ctx, ctx->gather, sb * ex.world); if (rc) return rc; }
@@ -1326,18 +1313,14 @@ int sharded_records(lemsm_ctx* ctx, MakeSrc make_src, size_t n, u32 c, u32 nb, u
 template <class P64, class G>
 int msm_sharded_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_points, size_t n, const Exchange& ex, u64 out[12]) {
   MsmPlan mp = make_msm_plan(ctx, curve, n);
-  auto make_src = [&](size_t s0, u32) {
-    PipProvider s; s.scalars = (const uint4*)((const char*)d_scalars + s0 * 32);
-    memcpy(s.kadd.k, mp.kadd, 32); memcpy(s.kadd.order, order_of(curve), 32); return s;
-  };
   std::vector<host::pt> all;
   // (a rank whose input check fails still enters the exchange: sharded_records carries rc_pre to every rank)
   const int rc_pre = validate_points(ctx, curve, d_points, n);
-  int rc = sharded_records<P64, G>(ctx, make_src, n, mp.c, mp.nb, mp.nbp, mp.L, mp.W, 0, d_points, ex, all, rc_pre);
+  int rc = sharded_records<P64, G>(ctx, pip_source(d_scalars, mp, curve), n, mp, d_points, ex, all, rc_pre);
   if (rc) return rc;
   std::vector<host::pt> sums;
   window_sums_par<P64>(ctx, all.data(), mp.W, mp.L, sums);
-  msm_combine_t<P64>(mp, sums.data(), out);
+  msm_combine_windows<P64>(mp.c, mp.W, sums.data(), out);
   return LEMSM_OK;
 }
 
@@ -1353,18 +1336,13 @@ int lhs_sharded_t(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* 
   if (!rc_pre) rc_pre = lhs_digits(ctx, curve, d_scalars, n, lp, ctx->in_aux, dg, pb, pe);   // every rank range-checks every scalar; it stores its own rows only
   auto make_src = [&](size_t s0, u32) { NegProvider s; s.digitsT = dg.digitsT + s0; return s; };
   std::vector<host::pt> all;
-  int rc = sharded_records<P64, G>(ctx, make_src, n, 0, lp.nb, lp.nbp, lp.L, lp.d, lp.d, d_points, ex, all, rc_pre);
+  int rc = sharded_records<P64, G>(ctx, make_src, n, lp, d_points, ex, all, rc_pre);
   if (rc) return rc;
-  u32 err[2];
-  { int rce = lhs_err_words(ctx, n, err); if (rce) return rce; }
-  ctx->truncated = err[1];
-  if (err[0] != 0xffffffffu) {
-    if (bad_index) *bad_index = err[0];
-    return fail(ctx, LEMSM_ERR_SCALAR_OUT_OF_RANGE, "scalar out of range (>= isqrt(order)+2)");
-  }
+  rc = lhs_range_check(ctx, n, bad_index);
+  if (rc) return rc;
   std::vector<host::pt> sums;
   window_sums_par<P64>(ctx, all.data(), lp.d, lp.L, sums);
-  lhs_combine_t<P64>(lp, sums.data(), out_carry, out_carries);
+  lhs_combine_positions<P64>(lp.base, lp.d, sums.data(), out_carry, out_carries);
   return LEMSM_OK;
 }
 
@@ -1852,7 +1830,7 @@ int lemsm_msm_combine(const lemsm_ctx* ctx, int curve, size_t n, const uint8_t* 
   MsmPlan mp = make_msm_plan(ctx, curve, n);
   std::vector<host::pt> recs((size_t)mp.W);
   memcpy(recs.data(), partials, recs.size() * sizeof(host::pt));
-  with_curve(curve, [&](auto cv) { msm_combine_t<typename decltype(cv)::P64>(mp, recs.data(), out); });
+  with_curve(curve, [&](auto cv) { msm_combine_windows<typename decltype(cv)::P64>(mp.c, mp.W, recs.data(), out); });
   return LEMSM_OK;
 }
 
@@ -1869,7 +1847,7 @@ int lemsm_msm_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const voi
   rc = msm_partial_dispatch(ctx, curve, d_scalars, d_points, n, 0, mp.W, sums);
   if (rc) return rc;
   const auto th0 = std::chrono::steady_clock::now();
-  with_curve(curve, [&](auto cv) { msm_combine_t<typename decltype(cv)::P64>(mp, sums.data(), out); });
+  with_curve(curve, [&](auto cv) { msm_combine_windows<typename decltype(cv)::P64>(mp.c, mp.W, sums.data(), out); });
   ctx->host_us[3] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - th0).count();
   if (getenv("LEMSM_DEBUG_STAMPS")) fprintf(stderr, "[lemsm] host tail (us): device wait %.1f, records + window sums %.1f, (unused) %.1f, Horner %.1f\n", ctx->host_us[0], ctx->host_us[1], ctx->host_us[2], ctx->host_us[3]);
   return LEMSM_OK;
@@ -2061,7 +2039,7 @@ int lemsm_lhs_combine(int curve, uint8_t base, const uint8_t* partials, uint64_t
   LhsPlan lp; int rc = make_lhs_plan(curve, base, lp); if (rc) return rc;
   std::vector<host::pt> recs((size_t)lp.d);
   memcpy(recs.data(), partials, recs.size() * sizeof(host::pt));
-  with_curve(curve, [&](auto cv) { lhs_combine_t<typename decltype(cv)::P64>(lp, recs.data(), out_carry, out_carries); });
+  with_curve(curve, [&](auto cv) { lhs_combine_positions<typename decltype(cv)::P64>(lp.base, lp.d, recs.data(), out_carry, out_carries); });
   return LEMSM_OK;
 }
 
@@ -2075,7 +2053,7 @@ int lemsm_lhs_msm_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const
   std::vector<host::pt> recs;
   rc = lhs_partial_dispatch(ctx, curve, d_scalars, d_points, n, lp, 0, lp.d, recs, bad_index);
   if (rc) return rc;
-  with_curve(curve, [&](auto cv) { lhs_combine_t<typename decltype(cv)::P64>(lp, recs.data(), out_carry, out_carries); });
+  with_curve(curve, [&](auto cv) { lhs_combine_positions<typename decltype(cv)::P64>(lp.base, lp.d, recs.data(), out_carry, out_carries); });
   return LEMSM_OK;
 }
 

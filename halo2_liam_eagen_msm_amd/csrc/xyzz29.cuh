@@ -315,7 +315,7 @@ struct XYZZ29 {
   // + 4 pad words = 160 bytes, NOT canonicalised: storing is ten 16-byte stores.  (Canonical
   // packing costs ~900 instructions per point and the flush branch of k_accum1 is taken by some
   // lane in a third of all iterations.)  The host reduces the few hundred result points
-  // (lemsm.hip: from_device_records).  Identity = all zero.
+  // (hosttail.hpp: from_device_records_t).  Identity = all zero.
   static constexpr u32 PT_BYTES = 160;
   static __device__ __forceinline__ void load(pt& p, const void* mem) {
     const uint4* q = reinterpret_cast<const uint4*>(mem);
