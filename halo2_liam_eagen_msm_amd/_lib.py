@@ -57,7 +57,7 @@ SYMBOLS = [
     "lemsm_msm_fixed_device",
     "lemsm_debug_msm_sharded_sim", "lemsm_debug_lhs_sharded_sim",
     "lemsm_prepare_scalar_witness_batch", "lemsm_table_entries",
-    "lemsm_divisor_witness", "lemsm_divisor_witness_device", "lemsm_divisor_witness_batch", "lemsm_divisor_last_ntt", "lemsm_lhs_witness", "lemsm_lhs_witness_device", "lemsm_lhs_witness_device_range", "lemsm_lhs_witness_last_phases", "lemsm_debug_ntt",
+    "lemsm_divisor_witness", "lemsm_divisor_witness_device", "lemsm_divisor_witness_batch", "lemsm_divisor_last_ntt", "lemsm_lhs_witness", "lemsm_lhs_witness_device", "lemsm_lhs_witness_device_range", "lemsm_lhs_witness_last_phases", "lemsm_debug_ntt", "lemsm_debug_arena_selftest",
     "lemsm_to_curve_x", "lemsm_y_from_x", "lemsm_slope",
     "lemsm_regfn_eval_plan", "lemsm_regfn_eval_device", "lemsm_regfn_eval", "lemsm_regfn_eval_last",
     "lemsm_regfn_logderiv_plan", "lemsm_regfn_logderiv_device", "lemsm_regfn_logderiv", "lemsm_regfn_logderiv_last",
@@ -176,6 +176,7 @@ def load() -> ctypes.CDLL:
         "lemsm_lhs_witness_device": (i, [vp, i, vp, vp, sz, ctypes.c_uint8, u64p, vp, sz, szp, i, szp]),
         "lemsm_lhs_witness_device_range": (i, [vp, i, vp, vp, sz, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint32, u64p, vp, sz, szp, i, szp]),
         "lemsm_debug_ntt": (i, [vp, u64p, u64p, sz, ctypes.c_uint32, i]),
+        "lemsm_debug_arena_selftest": (i, [vp, i, ctypes.c_uint32]),
         "lemsm_to_curve_x": (i, [i, u64p, u64p]),
         "lemsm_y_from_x": (i, [i, u64p, u64p, ctypes.POINTER(i)]),
         "lemsm_slope": (i, [i, u64p, u64p]),

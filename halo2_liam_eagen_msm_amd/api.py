@@ -701,6 +701,12 @@ class Context:
         self._check(self.lib.lemsm_debug_ntt(self.h, _ptr(a), _ptr(out), a.shape[0] >> logn, logn, int(inverse)))
         return out
 
+    def debug_arena_selftest(self, which: int = -1, byte: int = 0) -> Tuple[int, str]:
+        """lemsm_debug_arena_selftest: (status, message) of the guard check of a three-block arena ("first", "second",
+        "third") after byte `byte` of the zone behind block `which` was overwritten (-1: none).  Does not raise."""
+        rc = self.lib.lemsm_debug_arena_selftest(self.h, int(which), int(byte))
+        return rc, (self.lib.lemsm_last_error(self.h).decode() if rc else "")
+
     # ---- prepare_scalar_witness / table_entry_by_id ---------------------------------------
     def prepare_scalar_witness_batch(self, scalars, negative, base: int, num_digits: int, logtable: int) -> np.ndarray:
         """(n, base, num_limbs+1) array of ENTRY_DTYPE: prepare_scalar_witness (src/negbase_utils.rs:79-124) of every

@@ -47,10 +47,18 @@ int dw_ensure_tables(lemsm_ctx* ctx, u32 logn, u32 gexp) {
   if (!need_g) return LEMSM_OK;
   const size_t nmax = (size_t)1 << logn;
   hipStream_t st = ctx->stream;
-  int rc = reserve(ctx, ctx->dw_tab, (nmax / 2 + 2 * nmax) * 32 + 4096 + nmax / 2 * 32 + 1024); if (rc) return rc;   // W, GP, GI, the 96 powers, W32
+  // W, GP, GI, the 96 powers, W32 (nmax >= 4096: every size is a multiple of 256).  Slack nobody reads: 1024 bytes
+  // behind the 96 powers and 1024 at the end.
+  Arena ar("dw_tab", ctx->opt.ws_canary != 0);
+  const size_t oW = ar.take("W", nmax / 2 * 32), oGP = ar.take("GP", nmax * 32), oGI = ar.take("GI", nmax * 32);
+  const size_t oP2 = ar.take("powers", 96 * 32, 1024), oW32 = ar.take("W32", nmax / 2 * 32, 1024);
+  int rc = reserve(ctx, ctx->dw_tab, ar.end()); if (rc) return rc;
   char* base = (char*)ctx->dw_tab.p;
-  u32* W = (u32*)base; u32* GP = (u32*)(base + nmax / 2 * 32); u32* GI = (u32*)(base + (nmax / 2 + nmax) * 32);
-  u32* P2 = (u32*)(base + (nmax / 2 + 2 * nmax) * 32);
+  ctx->dw_tab_off[0] = oW; ctx->dw_tab_off[1] = oGP; ctx->dw_tab_off[2] = oGI; ctx->dw_tab_off[3] = oW32;
+  ctx->dw_logn = 0;   // (the old tables are gone whatever happens below)
+  rc = arena_fill(ctx, ar, base, st); if (rc) return rc;
+  u32* W = (u32*)(base + oW); u32* GP = (u32*)(base + oGP); u32* GI = (u32*)(base + oGI);
+  u32* P2 = (u32*)(base + oP2);
   std::vector<host::fe> p2(3 * 32);
   host::fe w = fr_root_of_unity_2_28();
   for (u32 k = 28; k > logn; k--) w = HFr::sqr(w);               // omega_{2^logn}
@@ -64,18 +72,19 @@ int dw_ensure_tables(lemsm_ctx* ctx, u32 logn, u32 gexp) {
   HIPCHK(ctx, hipMemcpyAsync(P2, p2.data(), p2.size() * 32, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)P2, logn - 1, (u32)(nmax / 2), W);
-  hipLaunchKernelGGL(lemsm::dw::k_times32, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)W, (u32)(nmax / 2), (u32*)(base + (nmax / 2 + 2 * nmax) * 32 + 4096));
+  hipLaunchKernelGGL(lemsm::dw::k_times32, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)W, (u32)(nmax / 2), (u32*)(base + oW32));
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax + 255) / 256)), dim3(256), 0, st, (const u32*)(P2 + 32 * 8), logn, (u32)nmax, GP);
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax + 255) / 256)), dim3(256), 0, st, (const u32*)(P2 + 64 * 8), logn, (u32)nmax, GI);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));
+  rc = arena_check(ctx, ar, base, st); if (rc) return rc;   // (the tables are only read from here on)
   ctx->dw_logn = logn; ctx->dw_gexp = gexp;
   return LEMSM_OK;
 }
-u32* dw_W(lemsm_ctx* ctx) { return (u32*)ctx->dw_tab.p; }
-u32* dw_W32(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + (((size_t)1 << ctx->dw_logn) / 2 + 2 * ((size_t)1 << ctx->dw_logn)) * 32 + 4096); }   // 32 W: the twiddles of the lazy-field passes
-u32* dw_GP(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + ((size_t)1 << ctx->dw_logn) / 2 * 32); }
-u32* dw_GI(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + (((size_t)1 << ctx->dw_logn) / 2 + ((size_t)1 << ctx->dw_logn)) * 32); }
+u32* dw_W(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + ctx->dw_tab_off[0]); }
+u32* dw_W32(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + ctx->dw_tab_off[3]); }   // 32 W: the twiddles of the lazy-field passes
+u32* dw_GP(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + ctx->dw_tab_off[1]); }
+u32* dw_GI(lemsm_ctx* ctx) { return (u32*)((char*)ctx->dw_tab.p + ctx->dw_tab_off[2]); }
 
 u32 ceil_log2_u32(u32 x) { u32 l = 0; while (((u64)1 << l) < x) l++; return l; }
 
@@ -157,7 +166,10 @@ struct DwForest {
   const uint2* d_lens = nullptr; u32* dA = nullptr; u32* dB = nullptr; u32* d_scratch = nullptr;
   u32 reuse_levels = 0;                                   // levels whose forward transforms covered the odd half of the domain only (child-evaluation reuse)
   double ntt_ms = 0; u64 ntt_bytes = 0, ntt_bflies = 0;   // device time, algorithmic bytes (one read + one write of every element per pass) and butterflies of the transforms
+  Arena arena; char* base = nullptr;                      // the carve of ctx->dw_arena (option ws_canary: its guard zones)
 };
+// the status of a return behind the forest's kernels: its guard zones first (option ws_canary)
+int dw_forest_done(lemsm_ctx* ctx, const DwForest& fo, int rc) { return fo.base ? arena_done(ctx, fo.arena, fo.base, ctx->stream, rc) : rc; }
 
 // compute_divisor_witness_partial (:453-467) of T point lists at once: list t = counts[t] affine points, concatenated at
 // d_pts.  One forest costs the launches of one tree (levels = those of the longest list).  Results stay in the arena.
@@ -194,13 +206,15 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
     node_max = std::max<size_t>(node_max, lv[l].nodes);
     if (l) fbuf_bytes = std::max(fbuf_bytes, (size_t)4 * lv[l].nodes * ((size_t)1 << ceil_log2_u32(lv[l].cap)) * 32);
   }
-  size_t offp = 0;
-  auto take = [&](size_t b) { size_t o = offp; offp = align_up(offp + b, 256); return o; };
-  const size_t oA0 = take(coef_bytes), oB0 = take(coef_bytes), oA1 = take(coef_bytes), oB1 = take(coef_bytes);
-  const size_t oL0 = take(node_max * 8), oL1 = take(node_max * 8);
-  const size_t oX0 = take(node_max * 128), oX1 = take(node_max * 128);
-  const size_t oP = take((node_max + 2) * sizeof(Plan));
-  const size_t oOff = take(off.size() * (size_t)(T + 1) * 4);
+  // The carve.  take(name, bytes, slack): `bytes` is what the kernels touch; `slack` is room the request has always
+  // carried and no kernel reads (with option ws_canary a guard zone takes its place, directly behind the bytes).
+  Arena& ar = fo.arena; ar = Arena("dw_arena", ctx->opt.ws_canary != 0);
+  auto take = [&](const char* name, size_t b, size_t slack = 0) { return ar.take(name, b, slack); };
+  const size_t oA0 = take("coefA0", coef_bytes), oB0 = take("coefB0", coef_bytes), oA1 = take("coefA1", coef_bytes), oB1 = take("coefB1", coef_bytes);
+  const size_t oL0 = take("lens0", node_max * 8), oL1 = take("lens1", node_max * 8);
+  const size_t oX0 = take("xyzz0", node_max * 128), oX1 = take("xyzz1", node_max * 128);
+  const size_t oP = take("plan0", node_max * sizeof(Plan), 2 * sizeof(Plan));
+  const size_t oOff = take("offsets", off.size() * (size_t)(T + 1) * 4);
   size_t xs_bytes = 0;
   for (size_t l = 1; l < lv.size(); l++) xs_bytes = std::max(xs_bytes, ((size_t)1 << ceil_log2_u32(lv[l].cap)) * 128);   // x, x^3 + b, and both times 32
   // child-evaluation reuse (divisor.cuh): a second transform buffer (the level below's quotient values stay while this
@@ -210,15 +224,21 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
   for (size_t l = 1; l < lv.size(); l++) half_max = std::max(half_max, ((size_t)1 << ceil_log2_u32(lv[l].cap)) / 2);
   const size_t feven_bytes = (size_t)2 * T * half_max * 32;
   const bool reuse_opt = ctx->opt.dw_reuse != 2 && ctx->opt.dw_fuse != 2 && ctx->opt.ntt_tiled != 2 && lv.size() > 2 && feven_bytes <= ((size_t)16 << 30);   // (the bound is 4x what a wrap-mode level needs; beyond 16 GB -- many trees beside a huge one -- whole transforms)
-  const size_t oFb = take(fbuf_bytes + 256), oSt = take(256), oC = take(256 + (size_t)T * 32), oXS = take(xs_bytes + 256);
-  const size_t oFb2 = reuse_opt ? take(fbuf_bytes + 256) : oFb, oFinv = reuse_opt ? take(fbuf_bytes / 2 + 256) : oFb, oFodd = reuse_opt ? take(fbuf_bytes / 2 + 256) : oFb;
-  const size_t oFev = reuse_opt ? take(feven_bytes + 256) : oFb, oGo = reuse_opt ? take(half_max * 32 + 256) : oFb, oExc = take((size_t)T * 4 + 256);
-  const size_t oP2 = take((node_max + 2) * sizeof(Plan));
-  const size_t oC0i = take(node_max * 4 * 32), oC0o = take(node_max * 2 * 32);
-  const size_t root_bytes = (fbuf_bytes / 128 / DW_KB_MIN + node_max + 256) * 32;     // one root per thread of k_pw_prefix: at most elements / DW_KB_MIN + one per node
-  const size_t oRt = take(root_bytes), oRp = take(root_bytes);   // wrap mode: constant terms of the children, of the results
-  int rc = reserve(ctx, ctx->dw_arena, offp + 4096); if (rc) return rc;
+  static_assert(STAT_WORDS * 4 <= 256, "the statistics words have 256 bytes");
+  const size_t oFb = take("fbuf0", fbuf_bytes, 256), oSt = take("stats", STAT_WORDS * 4, 256 - STAT_WORDS * 4);
+  const size_t oC = take("consts", 256 + (size_t)T * 32);   // the 8 level constants, then one scale per tree (dw_normalise_forest)
+  const size_t oXS = take("xs", xs_bytes, 256);
+  const size_t oFb2 = reuse_opt ? take("fbuf1", fbuf_bytes, 256) : oFb, oFinv = reuse_opt ? take("finv", fbuf_bytes / 2, 256) : oFb, oFodd = reuse_opt ? take("fodd", fbuf_bytes / 2, 256) : oFb;
+  const size_t oFev = reuse_opt ? take("feven", feven_bytes, 256) : oFb, oGo = reuse_opt ? take("go", half_max * 32, 256) : oFb, oExc = take("exc", (size_t)T * 4, 256);
+  const size_t oP2 = take("plan1", node_max * sizeof(Plan), 2 * sizeof(Plan));
+  const size_t oC0i = take("c0in", node_max * 4 * 32), oC0o = take("c0out", node_max * 2 * 32);   // wrap mode: constant terms of the children, of the results
+  const size_t root_bytes = (fbuf_bytes / 128 / DW_KB_MIN + node_max) * 32;     // one root per thread of k_pw_prefix: at most elements / DW_KB_MIN + one per node
+  const size_t oRt = take("pw_roots", root_bytes, 256 * 32), oRp = take("pw_rpre", root_bytes, 256 * 32);
+  int rc = reserve(ctx, ctx->dw_arena, ar.total() + 4096); if (rc) return rc;   // (+ 4096: slack behind the whole arena)
   char* base = (char*)ctx->dw_arena.p;
+  fo.base = base;
+  rc = arena_fill(ctx, ar, base, st); if (rc) return rc;
+  auto done = [&](int status) { return dw_forest_done(ctx, fo, status); };   // returns behind a synchronised launch
   u32* cA[2] = {(u32*)(base + oA0), (u32*)(base + oA1)}; u32* cB[2] = {(u32*)(base + oB0), (u32*)(base + oB1)};
   uint2* lens[2] = {(uint2*)(base + oL0), (uint2*)(base + oL1)};
   char* xyzz[2] = {base + oX0, base + oX1}; Plan* plan = (Plan*)(base + oP);
@@ -262,9 +282,9 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
     u32 hs[STAT_WORDS];
     HIPCHK(ctx, hipMemcpyAsync(hs, stats, STAT_WORDS * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (hs[STAT_PANIC]) return fail(ctx, LEMSM_ERR_ARITH_OVERFLOW, "divisor witness: product of two empty polynomials (usize underflow at src/regular_functions_utils.rs:55 / kate_division of an empty vector: a panic in the reference)");
+    if (hs[STAT_PANIC]) return done(fail(ctx, LEMSM_ERR_ARITH_OVERFLOW, "divisor witness: product of two empty polynomials (usize underflow at src/regular_functions_utils.rs:55 / kate_division of an empty vector: a panic in the reference)"));
     const u32 maxlen = std::max(hs[STAT_MAXLEN], 2u);
-    if (maxlen > cap) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal length bound exceeded");
+    if (maxlen > cap) return done(fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal length bound exceeded"));
     // wrap mode (k_pw_num, k_pw_inv): when the longest part has 2^k + 1 coefficients (a node over 2^(k+1) points) and every
     // child fits 2^k, transforms of 2^k do: the top coefficient comes back folded onto the constant term and is unfolded
     // with the value at x = 0
@@ -272,7 +292,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
     bool fused = false; TileIO tio;
     bool wrap = ctx->opt.dw_wrap != 2 && maxlen >= 3 && ((maxlen - 1) & (maxlen - 2)) == 0 && maxchild <= maxlen - 1;
     u32 logN = wrap ? ceil_log2_u32(maxlen - 1) : ceil_log2_u32(maxlen);
-    if (((size_t)4 * nn << logN) * 32 > fbuf_bytes + 256) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal transform buffer bound exceeded");
+    if (((size_t)4 * nn << logN) * 32 > fbuf_bytes) return done(fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal transform buffer bound exceeded"));
     // reuse mode for this level: the level below left its quotient values on exactly the even half of this level's domain
     bool can_reuse = reuse_opt && prev_valid && logN == prev_logN + 1 && logN >= 2;
     u32 n_exc = 0;
@@ -384,13 +404,13 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
       if (hs[STAT_ZERO0]) {     // an output with x = 0 (not a curve point): this level at the full transform size
         wrap = false; logN = ceil_log2_u32(maxlen); can_reuse = false;
         HIPCHK(ctx, hipMemsetAsync(stats + STAT_ZERODEN, 0, 4, st)); HIPCHK(ctx, hipMemsetAsync(stats + STAT_ZERO0, 0, 4, st));
-        if (((size_t)4 * nn << logN) * 32 > fbuf_bytes + 256) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal transform buffer bound exceeded");
+        if (((size_t)4 * nn << logN) * 32 > fbuf_bytes) return done(fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: internal transform buffer bound exceeded"));
         continue;
       }
       if (!hs[STAT_ZERODEN]) break;
       // some x_i equals an output's x: move the coset (next power of 7) and redo this level (on the new coset the level
       // below's values are of no use: whole transforms)
-      if (attempt >= 6) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: no coset without a zero denominator");
+      if (attempt >= 6) return done(fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: no coset without a zero denominator"));
       HIPCHK(ctx, hipMemsetAsync(stats + STAT_ZERODEN, 0, 4, st));
       ctx->dw_gexp = gexp + 1; ctx->dw_logn = 0;   // force a rebuild of the tables with the new generator
       can_reuse = false;
@@ -481,7 +501,10 @@ int dw_normalise_forest(lemsm_ctx* ctx, DwForest& fo) {
 int dw_output(lemsm_ctx* ctx, const DwResult& res, uint64_t* out_a, size_t cap_a, size_t* len_a, uint64_t* out_b, size_t cap_b, size_t* len_b) {
   if (len_a) *len_a = res.la;
   if (len_b) *len_b = res.lb;
-  if (res.la > cap_a || res.lb > cap_b) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: output capacity too small (n + 2 coefficients per part always suffice)");
+  if (res.la > cap_a || res.lb > cap_b) {   // nothing is copied; the call's kernels (dw_normalise_forest) have ended when this returns
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness: output capacity too small (n + 2 coefficients per part always suffice)");
+  }
   if (res.la) HIPCHK(ctx, hipMemcpyAsync(out_a, res.A, (size_t)res.la * 32, hipMemcpyDeviceToHost, ctx->stream));
   if (res.lb) HIPCHK(ctx, hipMemcpyAsync(out_b, res.B, (size_t)res.lb * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -505,10 +528,10 @@ int lemsm_divisor_witness_device(lemsm_ctx* ctx, int curve, const void* d_points
   if (out_point_affine) memcpy(out_point_affine, res.out_aff, 64);
   if (require_zero_sum) {
     u64 o = 0; for (int i = 0; i < 8; i++) o |= res.out_aff[i];
-    if (o) return fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)");
+    if (o) return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)"));
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
-  return dw_output(ctx, res, out_a, cap_a, len_a, out_b, cap_b, len_b);
+  return dw_forest_done(ctx, fo, dw_output(ctx, res, out_a, cap_a, len_a, out_b, cap_b, len_b));
 }
 
 int lemsm_divisor_witness(lemsm_ctx* ctx, int curve, const uint64_t* points_affine, size_t n, int require_zero_sum, int normalise,
@@ -543,22 +566,31 @@ int lemsm_divisor_witness_batch(lemsm_ctx* ctx, int curve, const uint64_t* point
     if (out_points_affine) memcpy(out_points_affine + 8 * t, fo.trees[t].out_aff, 64);
     if (require_zero_sum) {
       u64 o = 0; for (int i = 0; i < 8; i++) o |= fo.trees[t].out_aff[i];
-      if (o) { ctx->bad_index = t; return fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: a list does not sum to the identity (panic at src/regular_functions_utils.rs:478)"); }
+      if (o) { ctx->bad_index = t; return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: a list does not sum to the identity (panic at src/regular_functions_utils.rs:478)")); }
     }
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
+  // the whole layout first, the capacity once, the copies last: a capacity error leaves out_index complete (the last
+  // row gives the size the call needs), out_coeffs untouched and nothing queued
   size_t used = 0;
   for (size_t t = 0; t < T; t++) {
     const DwResult& res = fo.trees[t];
     size_t* ix = out_index + 4 * t;
     ix[0] = used; ix[1] = res.la; ix[2] = used + res.la; ix[3] = res.lb;
-    if (used + res.la + res.lb > cap_coeffs) return fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness batch: coefficient capacity too small");
-    if (res.la) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[0], res.A, (size_t)res.la * 32, hipMemcpyDeviceToHost, ctx->stream));
-    if (res.lb) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[2], res.B, (size_t)res.lb * 32, hipMemcpyDeviceToHost, ctx->stream));
     used += (size_t)res.la + res.lb;
   }
+  if (used > cap_coeffs) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness batch: coefficient capacity too small"));
+  }
+  for (size_t t = 0; t < T; t++) {
+    const DwResult& res = fo.trees[t];
+    const size_t* ix = out_index + 4 * t;
+    if (res.la) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[0], res.A, (size_t)res.la * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (res.lb) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[2], res.B, (size_t)res.lb * 32, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  return dw_forest_done(ctx, fo, LEMSM_OK);
 }
 
 int lemsm_debug_divisor_last_reuse_levels(const lemsm_ctx* ctx, uint32_t* levels) {
@@ -582,8 +614,11 @@ int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t ns
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = dw_ensure_tables(ctx, logn, std::max(ctx->dw_gexp, 1u)); if (rc) return rc;
   const size_t cnt = nseq << logn, bytes = cnt * 32;
-  rc = reserve(ctx, ctx->ws, 2 * bytes + 512); if (rc) return rc;
-  u32* a = (u32*)ctx->ws.p; u32* b = (u32*)((char*)ctx->ws.p + align_up(bytes, 256));
+  Arena ar("debug_ntt", ctx->opt.ws_canary != 0);
+  const size_t o_a = ar.take("a", bytes), o_b = ar.take("b", bytes);
+  rc = reserve(ctx, ctx->ws, std::max(ar.total(), 2 * bytes + 512)); if (rc) return rc;   // (guards off: 2 bytes + 512, the larger)
+  rc = arena_fill(ctx, ar, ctx->ws.p, ctx->stream); if (rc) return rc;
+  u32* a = (u32*)((char*)ctx->ws.p + o_a); u32* b = (u32*)((char*)ctx->ws.p + o_b);
   HIPCHK(ctx, hipMemcpyAsync(a, in, bytes, hipMemcpyHostToDevice, ctx->stream));
   const dim3 grid((u32)((cnt + 255) / 256)), blk(256);
   u32* resbuf;
@@ -604,7 +639,20 @@ int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t ns
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, resbuf, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  return arena_done(ctx, ar, ctx->ws.p, ctx->stream, LEMSM_OK);
+}
+
+// Proof that a damaged guard zone is reported, with no kernel overrunning anything: a three-block arena with guards in the
+// context's own workspace, one byte of zone `which` overwritten by a memset (inside the allocation), then the check.
+int lemsm_debug_arena_selftest(lemsm_ctx* ctx, int which, uint32_t byte) {
+  if (!ctx || which < -1 || which > 2 || byte >= lemsm::arena::WS_GUARD_BYTES) return LEMSM_ERR_BAD_ARG;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Arena ar("selftest", true);
+  ar.take("first", 1000); ar.take("second", 4096, 256); ar.take("third", 17);
+  int rc = reserve(ctx, ctx->ws, ar.total()); if (rc) return rc;
+  rc = arena_fill(ctx, ar, ctx->ws.p, ctx->stream); if (rc) return rc;
+  if (which >= 0) HIPCHK(ctx, hipMemsetAsync((char*)ctx->ws.p + ar.zones()[which].off + byte, 0x5A, 1, ctx->stream));
+  return arena_check(ctx, ar, ctx->ws.p, ctx->stream);
 }
 
 // compute_lhs_witness in full (src/argument_witness_calc.rs:87-136): the MSM core (lemsm_lhs_msm) and the d divisor
@@ -640,15 +688,20 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   // the digit matrix (position-major, d x n) is what lemsm_lhs_msm left in in_aux; the table of affine multiples goes to ws
   const uint8_t* digitsT = (const uint8_t*)ctx->in_aux.p;
   const size_t nm = n * (size_t)(base - 1);
-  const size_t in_bytes = align_up(n * 96 + 16, 256), tab_bytes = align_up(nm * 64 + 16, 256), scr_bytes = nm * 160 + 256;
-  rc = reserve(ctx, ctx->ws, in_bytes + tab_bytes + scr_bytes + 256); if (rc) return rc;
+  // (slack no kernel reads: 16 bytes behind the copy and the table, 256 behind the scratch and behind the arena)
+  const bool guard = ctx->opt.ws_canary != 0;
+  Arena ar_ws("lhs_ws", guard), ar_tmp("lhs_tmp", guard), ar_lists("lhs_lists", guard);
+  const size_t o_jac = ar_ws.take("jacobian", n * 96, 16), o_tab = ar_ws.take("table", nm * 64, 16);
+  const size_t o_scr = ar_ws.take("scratch", nm * 160, 256);                         // k_precompute_mult_affine: 160 B per multiple
+  rc = reserve(ctx, ctx->ws, ar_ws.end() + 256); if (rc) return rc;
   char* wb = (char*)ctx->ws.p;
-  const uint4* table = (const uint4*)(wb + in_bytes);
+  rc = arena_fill(ctx, ar_ws, wb, st); if (rc) return rc;
+  const uint4* table = (const uint4*)(wb + o_tab);
   if (n) {
-    if (on_device) hipLaunchKernelGGL(lemsm::dw::k_aff_to_jac, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, (uint4*)wb);
-    else HIPCHK(ctx, hipMemcpyAsync(wb, points, n * 96, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)wb, (u32)n, (u32)base,
-                       (uint4*)(wb + in_bytes), wb + in_bytes + tab_bytes);
+    if (on_device) hipLaunchKernelGGL(lemsm::dw::k_aff_to_jac, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, (uint4*)(wb + o_jac));
+    else HIPCHK(ctx, hipMemcpyAsync(wb + o_jac, points, n * 96, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)(wb + o_jac), (u32)n, (u32)base,
+                       (uint4*)(wb + o_tab), wb + o_scr);
     HIPCHK(ctx, hipGetLastError());
   }
   // all d point lists of :110-127 side by side (one forest): counts first, then flags -> scan -> gather per position
@@ -656,13 +709,17 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   { hipError_t e = rocprim::exclusive_scan(nullptr, scan_tmp, (u32*)nullptr, (u32*)nullptr, 0u, std::max<size_t>(n, 1), rocprim::plus<u32>(), st);
     if (e != hipSuccess) return fail(ctx, LEMSM_ERR_HIP, "rocprim::exclusive_scan size query failed"); }
   std::vector<u32> nnz(d, 0);
-  rc = reserve(ctx, ctx->dw_tmp, 2 * align_up((n + 1) * 4, 256) + align_up(scan_tmp, 256) + align_up((size_t)d * 64, 256) + align_up((size_t)d * 4, 256) + 1024); if (rc) return rc;
+  // (slack: one word behind the n flags and the n offsets, 1024 bytes behind the arena)
+  const size_t o_flags = ar_tmp.take("flags", n * 4, 4), o_offs = ar_tmp.take("offsets", n * 4, 4), o_scan = ar_tmp.take("scan", scan_tmp);
+  const size_t o_negc = ar_tmp.take("negcarry", (size_t)d * 64), o_nnz = ar_tmp.take("counts", (size_t)d * 4);
+  rc = reserve(ctx, ctx->dw_tmp, ar_tmp.total() + 1024); if (rc) return rc;
   char* tb = (char*)ctx->dw_tmp.p;
-  u32* d_flags = (u32*)tb;
-  u32* d_offs = (u32*)((char*)d_flags + align_up((n + 1) * 4, 256));
-  void* d_scan = (char*)d_offs + align_up((n + 1) * 4, 256);
-  uint4* d_negc = (uint4*)((char*)d_scan + align_up(scan_tmp, 256));
-  u32* d_nnz = (u32*)((char*)d_negc + align_up((size_t)d * 64, 256));
+  rc = arena_fill(ctx, ar_tmp, tb, st); if (rc) return rc;
+  u32* d_flags = (u32*)(tb + o_flags);
+  u32* d_offs = (u32*)(tb + o_offs);
+  void* d_scan = tb + o_scan;
+  uint4* d_negc = (uint4*)(tb + o_negc);
+  u32* d_nnz = (u32*)(tb + o_nnz);
   HIPCHK(ctx, hipMemcpyAsync(d_negc, negc.data(), (size_t)d * 64, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemsetAsync(d_nnz, 0, (size_t)d * 4, st));
   if (n) hipLaunchKernelGGL(lemsm::dw::k_lhs_count, dim3((u32)((n + 4095) / 4096), d), dim3(256), 0, st, digitsT, (u32)n, d_nnz);
@@ -680,8 +737,16 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
     leads[s_] = prev_nonid ? (u32)base : 0u;                                         // `base` copies of -carry (:112-116)
     counts[s_] = (size_t)leads[s_] + nnz[pos] + 1; starts[s_] = total; total += counts[s_];
   }
-  rc = reserve(ctx, ctx->gather, total * 64 + 256); if (rc) return rc;              // (the multi-GPU record buffer doubles as the list buffer)
-  uint4* d_tmp = (uint4*)ctx->gather.p;
+  const size_t o_lists = ar_lists.take("lists", total * 64, 256);
+  rc = reserve(ctx, ctx->gather, ar_lists.end()); if (rc) return rc;                // (the multi-GPU record buffer doubles as the list buffer)
+  uint4* d_tmp = (uint4*)((char*)ctx->gather.p + o_lists);
+  rc = arena_fill(ctx, ar_lists, ctx->gather.p, st); if (rc) return rc;
+  // returns behind the (synchronised) list kernels: the three arenas' guard zones first
+  auto lists_done = [&](int status) {
+    status = arena_done(ctx, ar_ws, wb, st, status);
+    status = arena_done(ctx, ar_tmp, tb, st, status);
+    return arena_done(ctx, ar_lists, ctx->gather.p, st, status);
+  };
   for (u32 i = i_begin; i < i_end; i++) {
     const u32 pos = d - 1 - i, s_ = i - i_begin;
     uint4* lst = d_tmp + starts[s_] * 4;
@@ -699,31 +764,37 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   HIPCHK(ctx, hipStreamSynchronize(st));
   ctx->dw_phase_ms[1] = ms_since(t_phase); t_phase = Clk::now();
   DwForest fo;
-  rc = dw_run_forest(ctx, d_tmp, counts, fo); if (rc) return rc;
+  rc = dw_run_forest(ctx, d_tmp, counts, fo); if (rc) return lists_done(rc);
   for (u32 i = 0; i < nt; i++) {
     u64 o = 0; for (int q = 0; q < 8; q++) o |= fo.trees[i].out_aff[q];
-    if (o) return fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)");
+    if (o) return lists_done(dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)")));
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
   HIPCHK(ctx, hipStreamSynchronize(st));
   ctx->dw_phase_ms[2] = ms_since(t_phase); t_phase = Clk::now();
+  // the whole layout first, the capacity once, the copies last: a capacity error leaves out_index complete (the last
+  // row gives the size the call needs), out_coeffs untouched and nothing queued (the stream has just been synchronised)
   size_t used = 0;
   for (u32 f = 0; f < d; f++) {                                                      // ret.reverse() (:132): function f = iteration d - 1 - f
     size_t* ix = out_index + 4 * (size_t)f;
     if (f < f_begin || f >= f_end) { ix[0] = used; ix[1] = 0; ix[2] = used; ix[3] = 0; continue; }   // another rank's function
     const DwResult& res = fo.trees[(d - 1 - f) - i_begin];
     ix[0] = used; ix[1] = res.la; ix[2] = used + res.la; ix[3] = res.lb;
-    if (used + res.la + res.lb > cap_coeffs) return fail(ctx, LEMSM_ERR_BAD_ARG, "lhs witness: coefficient capacity too small (2 d (n + base + 3) always suffices)");
+    used += (size_t)res.la + res.lb;
+  }
+  if (used > cap_coeffs) return lists_done(dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_BAD_ARG, "lhs witness: coefficient capacity too small (2 d (n + base + 3) always suffices)")));
+  for (u32 f = f_begin; f < f_end; f++) {
+    const size_t* ix = out_index + 4 * (size_t)f;
+    const DwResult& res = fo.trees[(d - 1 - f) - i_begin];
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (res.la) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[0], res.A, (size_t)res.la * 32, kind, st));
     if (res.lb) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[2], res.B, (size_t)res.lb * 32, kind, st));
-    used += (size_t)res.la + res.lb;
   }
   HIPCHK(ctx, hipStreamSynchronize(st));
   ctx->dw_phase_ms[3] = ms_since(t_phase);
   const double ntt_ms = fo.ntt_ms; const u64 ntt_bytes = fo.ntt_bytes; ctx->dw_ntt_bflies = fo.ntt_bflies; ctx->dw_reuse_levels = fo.reuse_levels;
   ctx->dw_ntt_ms = ntt_ms; ctx->dw_ntt_bytes = ntt_bytes;
-  return LEMSM_OK;
+  return lists_done(dw_forest_done(ctx, fo, LEMSM_OK));
 }
 
 int lemsm_lhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n, uint8_t base,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/lemsm.h"
+#include "arena.hpp"
 #include "hostmath.hpp"
 #include "hostpool.hpp"
 #include "hosttail.hpp"
@@ -141,6 +142,7 @@ struct lemsm_ctx {
   DevBuf fail_buf;  // multi-GPU: the zeroed stand-in a rank sends when its own pipeline failed before the exchange
   DevBuf dw_tab, dw_arena, dw_tmp;   // divisor witness: twiddle / coset tables, level workspace, tmp point list
   u32 dw_logn = 0, dw_gexp = 0;      // tables hold transforms up to 2^dw_logn with coset generator 7^dw_gexp
+  size_t dw_tab_off[4] = {0, 0, 0, 0};   // ... at these offsets of dw_tab: W, GP, GI, W32 (dw_ensure_tables)
   double dw_ntt_ms = 0; u64 dw_ntt_bytes = 0, dw_ntt_bflies = 0; u32 dw_reuse_levels = 0;
   DevBuf rf_coef, rf_ws;             // regular-function evaluation: staged coefficients (host entry), tables / partials / values
   double rf_ms = 0; u64 rf_bytes = 0, rf_mults = 0;   // lemsm_regfn_eval_last
@@ -193,6 +195,39 @@ int reserve(lemsm_ctx* ctx, DevBuf& b, size_t bytes) {
   if (e != hipSuccess) { b.p = nullptr; return fail(ctx, LEMSM_ERR_NOMEM, "hipMalloc failed: " + std::string(hipGetErrorString(e))); }
   b.cap = want;
   return LEMSM_OK;
+}
+
+// Workspace arenas (arena.hpp) on a stream.  Every hand-carved workspace outside the MSM window group goes through these:
+// option ws_canary puts a guard zone behind each sub-buffer, arena_fill patterns the zones before the arena's first launch,
+// arena_done checks them once the arena's kernels have run.
+using lemsm::arena::Arena;
+struct ArenaHipMem {
+  hipStream_t st; hipError_t err = hipSuccess;
+  bool set(void* p, unsigned char v, size_t n) { err = hipMemsetAsync(p, v, n, st); return err == hipSuccess; }
+  bool get(void* dst, const void* src, size_t n) { err = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st); return err == hipSuccess; }
+  bool sync() { err = hipStreamSynchronize(st); return err == hipSuccess; }
+};
+int arena_fill(lemsm_ctx* ctx, const Arena& a, void* base, hipStream_t st) {
+  if (!a.guards()) return LEMSM_OK;
+  ArenaHipMem m{st};
+  if (!a.fill(m, (char*)base)) return fail(ctx, LEMSM_ERR_HIP, "workspace guard " + a.name() + ": hipMemsetAsync: " + hipGetErrorString(m.err));
+  return LEMSM_OK;
+}
+int arena_check(lemsm_ctx* ctx, const Arena& a, const void* base, hipStream_t st) {
+  if (!a.guards()) return LEMSM_OK;
+  ArenaHipMem m{st}; std::string msg;
+  const int r = a.check(m, (const char*)base, msg);
+  if (r < 0) return fail(ctx, LEMSM_ERR_HIP, "workspace guard " + a.name() + ": read-back: " + hipGetErrorString(m.err));
+  return r ? fail(ctx, LEMSM_ERR_HIP, msg) : LEMSM_OK;
+}
+// the status of a return that comes after the arena's kernels have run: a damaged guard outranks `rc` (and its message)
+int arena_done(lemsm_ctx* ctx, const Arena& a, const void* base, hipStream_t st, int rc) {
+  if (!a.guards() || rc == LEMSM_ERR_HIP || rc == LEMSM_ERR_NOMEM) return rc;   // (a failed runtime call stands as it is)
+  const std::string keep = ctx->last_error;
+  const int g = arena_check(ctx, a, base, st);
+  if (g) return g;
+  ctx->last_error = keep;
+  return rc;
 }
 
 // pinned host staging buffer of the context

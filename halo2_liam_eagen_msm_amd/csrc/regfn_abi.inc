@@ -123,19 +123,23 @@ int lemsm_regfn_eval_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, siz
 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t b_pts = align_up(K * 64, 256), b_pw = align_up(K * (size_t)rf::RF_PW * 32, 256), b_pwy = ymax ? b_pw : 0,
-               b_items = align_up(items.size() * sizeof(rf::Item), 256), b_fns = align_up(T * sizeof(rf::Fn), 256),
-               b_fov = align_up(fn_of_val.size() * 4, 256), b_part = align_up((size_t)npart * 32, 256), b_val = align_up(pl.num_values * 32, 256);
-  rc = reserve(ctx, ctx->rf_ws, b_pts + b_pw + b_pwy + b_items + b_fns + b_fov + b_part + b_val + 256); if (rc) return rc;
+  Arena ar("rf_ws", ctx->opt.ws_canary != 0);
+  const size_t b_pw = K * (size_t)rf::RF_PW * 32;
+  auto take = [&](const char* name, size_t bytes) { return ar.take(name, bytes); };
+  const size_t o_pts = take("points", K * 64), o_pw = take("powers", b_pw), o_pwy = ymax ? take("ypowers", b_pw) : ar.total();
+  const size_t o_items = take("items", items.size() * sizeof(rf::Item)), o_fns = take("functions", T * sizeof(rf::Fn));
+  const size_t o_fov = take("fn_of_value", fn_of_val.size() * 4), o_part = take("partials", (size_t)npart * 32), o_val = take("values", pl.num_values * 32);
+  rc = reserve(ctx, ctx->rf_ws, ar.total() + 256); if (rc) return rc;   // (+ 256 nobody reads)
   char* w = (char*)ctx->rf_ws.p;
-  uint4* d_pts = (uint4*)w; w += b_pts;
-  uint4* d_pw = (uint4*)w; w += b_pw;
-  uint4* d_pwy = (uint4*)w; w += b_pwy;
-  rf::Item* d_items = (rf::Item*)w; w += b_items;
-  rf::Fn* d_fns = (rf::Fn*)w; w += b_fns;
-  u32* d_fov = (u32*)w; w += b_fov;
-  uint4* d_part = (uint4*)w; w += b_part;
-  uint4* d_val = (uint4*)w;
+  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
+  uint4* d_pts = (uint4*)(w + o_pts);
+  uint4* d_pw = (uint4*)(w + o_pw);
+  uint4* d_pwy = (uint4*)(w + o_pwy);
+  rf::Item* d_items = (rf::Item*)(w + o_items);
+  rf::Fn* d_fns = (rf::Fn*)(w + o_fns);
+  u32* d_fov = (u32*)(w + o_fov);
+  uint4* d_part = (uint4*)(w + o_part);
+  uint4* d_val = (uint4*)(w + o_val);
   HIPCHK(ctx, hipMemcpyAsync(d_pts, aff.data(), K * 64, hipMemcpyHostToDevice, st));
   if (!items.empty()) HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(rf::Item), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(d_fns, fns.data(), T * sizeof(rf::Fn), hipMemcpyHostToDevice, st));
@@ -155,7 +159,7 @@ int lemsm_regfn_eval_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, siz
   HIPCHK(ctx, hipStreamSynchronize(st));
   float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
   ctx->rf_ms = ms;
-  return LEMSM_OK;
+  return arena_done(ctx, ar, w, st, LEMSM_OK);
 }
 
 int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,

@@ -66,25 +66,32 @@ int ld_run(lemsm_ctx* ctx, const void* d_coeffs, const size_t* index, size_t T, 
 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t b_pts = align_up(rows * 64, 256), b_tab = align_up(rows * (size_t)rf::RF_PW * 32, 256), b_dydx = align_up(rows * 32, 256),
-               b_chal = align_up(rows * sizeof(rf::LdChal), 256), b_items = align_up(items.size() * sizeof(rf::Item), 256),
-               b_fns = align_up(T * sizeof(rf::Fn), 256), b_part = align_up((size_t)npart * 32, 256), b_frac = align_up(2 * npairs * 32, 256),
-               b_L = align_up(npairs * 32, 256), b_sum = align_up(K * 32, 256), b_pd = want_pd ? align_up(8 * npairs * 32, 256) : 0;
-  int rc = reserve(ctx, ctx->rf_ws, b_pts + 4 * b_tab + b_dydx + b_chal + b_items + b_fns + b_part + 3 * b_frac + b_L + b_sum + b_pd + 256 + 256);
+  const size_t b_tab = rows * (size_t)rf::RF_PW * 32, b_frac = 2 * npairs * 32;
+  Arena ar("ld_ws", ctx->opt.ws_canary != 0);
+  const size_t o_pts = ar.take("abscissae", rows * 64);
+  const size_t o_pw = ar.take("powers", b_tab), o_dpw = ar.take("dpowers", b_tab), o_pwy = ar.take("ypowers", b_tab), o_dpwy = ar.take("dypowers", b_tab);
+  const size_t o_dydx = ar.take("dydx", rows * 32), o_chal = ar.take("challenges", rows * sizeof(rf::LdChal));
+  const size_t o_items = ar.take("items", items.size() * sizeof(rf::Item)), o_fns = ar.take("functions", T * sizeof(rf::Fn));
+  const size_t o_part = ar.take("partials", (size_t)npart * 32);
+  const size_t o_num = ar.take("numerators", b_frac), o_den = ar.take("denominators", b_frac), o_pre = ar.take("prefixes", b_frac);
+  const size_t o_L = ar.take("leaves", npairs * 32), o_sum = ar.take("sums", K * 32);
+  const size_t o_pd = want_pd ? ar.take("poly_values", 8 * npairs * 32) : 0;
+  const size_t o_err = ar.take("error_word", 8, 248);   // the kernels' error word lives in the 256 bytes behind the last block
+  int rc = reserve(ctx, ctx->rf_ws, ar.total() + 256);   // (+ 256 nobody reads)
   if (rc) return rc;
   char* w = (char*)ctx->rf_ws.p;
-  auto take = [&](size_t bytes) { char* p = w; w += bytes; return p; };
-  uint4* d_pts = (uint4*)take(b_pts);
-  uint4* d_pw = (uint4*)take(b_tab); uint4* d_dpw = (uint4*)take(b_tab); uint4* d_pwy = (uint4*)take(b_tab); uint4* d_dpwy = (uint4*)take(b_tab);
-  uint4* d_dydx = (uint4*)take(b_dydx);
-  rf::LdChal* d_chal = (rf::LdChal*)take(b_chal);
-  rf::Item* d_items = (rf::Item*)take(b_items);
-  rf::Fn* d_fns = (rf::Fn*)take(b_fns);
-  uint4* d_part = (uint4*)take(b_part);
-  uint4* d_num = (uint4*)take(b_frac); uint4* d_den = (uint4*)take(b_frac); uint4* d_pre = (uint4*)take(b_frac);
-  o.L = (uint4*)take(b_L); o.sum = (uint4*)take(b_sum);
-  o.pd = want_pd ? (uint4*)take(b_pd) : nullptr;
-  unsigned long long* d_err = (unsigned long long*)take(256);
+  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
+  uint4* d_pts = (uint4*)(w + o_pts);
+  uint4* d_pw = (uint4*)(w + o_pw); uint4* d_dpw = (uint4*)(w + o_dpw); uint4* d_pwy = (uint4*)(w + o_pwy); uint4* d_dpwy = (uint4*)(w + o_dpwy);
+  uint4* d_dydx = (uint4*)(w + o_dydx);
+  rf::LdChal* d_chal = (rf::LdChal*)(w + o_chal);
+  rf::Item* d_items = (rf::Item*)(w + o_items);
+  rf::Fn* d_fns = (rf::Fn*)(w + o_fns);
+  uint4* d_part = (uint4*)(w + o_part);
+  uint4* d_num = (uint4*)(w + o_num); uint4* d_den = (uint4*)(w + o_den); uint4* d_pre = (uint4*)(w + o_pre);
+  o.L = (uint4*)(w + o_L); o.sum = (uint4*)(w + o_sum);
+  o.pd = want_pd ? (uint4*)(w + o_pd) : nullptr;
+  unsigned long long* d_err = (unsigned long long*)(w + o_err);
   HIPCHK(ctx, hipMemcpyAsync(d_pts, absc.data(), rows * 64, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(d_chal, chal.data(), rows * sizeof(rf::LdChal), hipMemcpyHostToDevice, st));
   if (!items.empty()) HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(rf::Item), hipMemcpyHostToDevice, st));
@@ -114,7 +121,7 @@ int ld_run(lemsm_ctx* ctx, const void* d_coeffs, const size_t* index, size_t T, 
   float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
   ctx->ld_ms = ms;
   *err = errw;
-  return LEMSM_OK;
+  return arena_check(ctx, ar, w, st);   // (before the caller turns the error word into a status: a damaged guard outranks it)
 }
 
 const char* const LD_CURVE_MSG = "RegularFunction::ev: only Grumpkin (C::Base = bn256::Fr is the one FftPrecomp field, src/precomputed_fft_data.rs:3)";

@@ -29,8 +29,16 @@ FsGeom fs_geom(u64 N, u64 chains) {
 // k_fs_rootinv one inversion counted as FS_INV_MULTS = 384 products
 u64 fs_mults(const FsGeom& g, u32 src_mults) { return g.N * (u64)(src_mults + 4) + 3 * g.R + (u64)fs::FS_INV_MULTS * g.nthreads_inv; }
 
-size_t fs_ws_bytes(const FsGeom& g) {
-  return 3 * align_up(g.N * 32, 256) + 2 * align_up(g.R * 32, 256) + align_up(g.nseg * g.chains * 32, 256) + 2 * align_up(g.chains * 32, 256) + 256;
+// the engine's carve of ctx->rhs_ws
+struct FsWs { Arena ar; size_t bufN, bufD, bufP, roots, rpre, segsum, init, tot, err; };
+FsWs fs_carve(const FsGeom& g, bool guard) {
+  FsWs w; w.ar = Arena("rhs_ws", guard);
+  w.bufN = w.ar.take("numerators", g.N * 32); w.bufD = w.ar.take("denominators", g.N * 32); w.bufP = w.ar.take("prefixes", g.N * 32);
+  w.roots = w.ar.take("roots", g.R * 32); w.rpre = w.ar.take("root_prefixes", g.R * 32);
+  w.segsum = w.ar.take("segment_sums", g.nseg * g.chains * 32);
+  w.init = w.ar.take("init", g.chains * 32); w.tot = w.ar.take("totals", g.chains * 32);
+  w.err = w.ar.take("error_words", 2 * sizeof(fs::ErrWord), 256 - 2 * sizeof(fs::ErrWord));   // the 256 bytes behind the last block: the kernels' error words live here
+  return w;
 }
 
 // the engine: terms from `src`, running sums into d_out (may be null), totals (chains x 4 limbs) to the host.
@@ -38,17 +46,15 @@ size_t fs_ws_bytes(const FsGeom& g) {
 template <class F, class Src>
 int fs_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const uint64_t* init, void* d_out, uint64_t* out_totals, u64* err_den, u64* err_range) {
   hipStream_t st = ctx->stream;
-  int rc = reserve(ctx, ctx->rhs_ws, fs_ws_bytes(g)); if (rc) return rc;
+  const FsWs ws = fs_carve(g, ctx->opt.ws_canary != 0);
+  int rc = reserve(ctx, ctx->rhs_ws, ws.ar.total()); if (rc) return rc;
   char* w = (char*)ctx->rhs_ws.p;
-  uint4* bufN = (uint4*)w; w += align_up(g.N * 32, 256);
-  uint4* bufD = (uint4*)w; w += align_up(g.N * 32, 256);
-  uint4* bufP = (uint4*)w; w += align_up(g.N * 32, 256);
-  uint4* roots = (uint4*)w; w += align_up(g.R * 32, 256);
-  uint4* rpre = (uint4*)w; w += align_up(g.R * 32, 256);
-  uint4* segsum = (uint4*)w; w += align_up(g.nseg * g.chains * 32, 256);
-  uint4* d_init = (uint4*)w; w += align_up(g.chains * 32, 256);
-  uint4* d_tot = (uint4*)w; w += align_up(g.chains * 32, 256);
-  fs::ErrWord* d_err = (fs::ErrWord*)w;
+  rc = arena_fill(ctx, ws.ar, w, st); if (rc) return rc;
+  uint4* bufN = (uint4*)(w + ws.bufN); uint4* bufD = (uint4*)(w + ws.bufD); uint4* bufP = (uint4*)(w + ws.bufP);
+  uint4* roots = (uint4*)(w + ws.roots); uint4* rpre = (uint4*)(w + ws.rpre);
+  uint4* segsum = (uint4*)(w + ws.segsum);
+  uint4* d_init = (uint4*)(w + ws.init); uint4* d_tot = (uint4*)(w + ws.tot);
+  fs::ErrWord* d_err = (fs::ErrWord*)(w + ws.err);
   if (init) HIPCHK(ctx, hipMemcpyAsync(d_init, init, g.chains * 32, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemsetAsync(d_err, 0xff, 16, st));
   HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
@@ -69,7 +75,7 @@ int fs_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const uint64_t* init
   float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
   ctx->rhs_ms = ms;
   *err_den = errw[0]; *err_range = errw[1];
-  return LEMSM_OK;
+  return arena_check(ctx, ws.ar, w, st);   // (before the caller turns the error words into a status: a damaged guard outranks them)
 }
 
 int fs_div_by_zero(lemsm_ctx* ctx, u64 index, size_t* bad_index, const char* what) {
@@ -122,7 +128,10 @@ int rhs_device_t(lemsm_ctx* ctx, const void* d_scalars, const void* d_table, con
   const size_t nb = (size_t)base - 1;
   const FsGeom g = fs_geom(pl.num_terms, nb);
   std::vector<u32> pw; rhs_power_table(base, pl.d, pw);
-  int rc = reserve(ctx, ctx->rhs_pw, pw.size() * 4 + 256); if (rc) return rc;
+  Arena ar_pw("rhs_pw", ctx->opt.ws_canary != 0);
+  ar_pw.take("powers", pw.size() * 4, 256);
+  int rc = reserve(ctx, ctx->rhs_pw, ar_pw.end()); if (rc) return rc;
+  rc = arena_fill(ctx, ar_pw, ctx->rhs_pw.p, ctx->stream); if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->rhs_pw.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   fs::RhsSrc<F, typename C::P> src;
   src.scalars = (const uint4*)d_scalars; src.table = (const uint4*)d_table; src.pw = (const u32*)ctx->rhs_pw.p;
@@ -135,6 +144,7 @@ int rhs_device_t(lemsm_ctx* ctx, const void* d_scalars, const void* d_table, con
   if (!totals) { totals_tmp.resize(nb * 4); totals = totals_tmp.data(); }
   u64 err_den = ~0ull, err_range = ~0ull;
   rc = fs_run<F>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range); if (rc) return rc;   // (pw stays valid: the call has synchronised)
+  rc = arena_check(ctx, ar_pw, ctx->rhs_pw.p, ctx->stream); if (rc) return rc;
   if (err_range != ~0ull) {
     if (bad_index) *bad_index = (size_t)err_range;
     ctx->bad_index = (size_t)err_range;
@@ -168,9 +178,11 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   if (!d_points_affine || !d_out_table) return LEMSM_ERR_BAD_ARG;
   if (n >= ((size_t)1 << 28)) return fail(ctx, LEMSM_ERR_BAD_ARG, "n too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t in_bytes = align_up(n * 96, 256), scr_bytes = pl.num_terms * 160;   // k_precompute_mult_affine: 160 B of scratch per multiple
-  rc = reserve(ctx, ctx->ws, in_bytes + scr_bytes + 256); if (rc) return rc;
-  char* b = (char*)ctx->ws.p;
+  Arena ar("multiples_ws", ctx->opt.ws_canary != 0);
+  const size_t o_jac = ar.take("jacobian", n * 96), in_bytes = ar.take("scratch", pl.num_terms * 160, 256);   // k_precompute_mult_affine: 160 B of scratch per multiple (+ 256 nobody reads)
+  rc = reserve(ctx, ctx->ws, ar.end()); if (rc) return rc;
+  char* b = (char*)ctx->ws.p + o_jac;
+  rc = arena_fill(ctx, ar, ctx->ws.p, ctx->stream); if (rc) return rc;
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
   with_curve(curve, [&](auto cv) {
     typedef typename decltype(cv)::F F;
@@ -179,7 +191,7 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return LEMSM_OK;
+  return arena_done(ctx, ar, ctx->ws.p, ctx->stream, LEMSM_OK);
 }
 
 int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, size_t n, uint8_t base,
@@ -219,23 +231,30 @@ int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const u
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = stage(ctx, ctx->in_s, scalars, n * 32); if (rc) return rc;
   rc = stage(ctx, ctx->in_aux, pts_jacobian, n * 96); if (rc) return rc;
-  const size_t tab_bytes = align_up(pl.num_terms * 64, 256);
-  rc = reserve(ctx, ctx->rhs_tab, tab_bytes + (out_running ? pl.num_terms * 32 : 0) + 256); if (rc) return rc;
-  rc = reserve(ctx, ctx->ws, pl.num_terms * 160 + 256); if (rc) return rc;
-  char* tab = (char*)ctx->rhs_tab.p;
-  char* d_run = out_running ? tab + tab_bytes : nullptr;
+  const bool guard = ctx->opt.ws_canary != 0;
+  Arena ar_tab("rhs_tab", guard), ar_scr("rhs_scratch", guard);
+  const size_t o_tab = ar_tab.take("table", pl.num_terms * 64);
+  const size_t o_run = out_running ? ar_tab.take("running", pl.num_terms * 32, 256) : 0;
+  rc = reserve(ctx, ctx->rhs_tab, out_running ? ar_tab.end() : ar_tab.total() + 256); if (rc) return rc;   // (+ 256 nobody reads behind the last block)
+  ar_scr.take("scratch", pl.num_terms * 160, 256);                                                           // (the same)
+  rc = reserve(ctx, ctx->ws, ar_scr.end()); if (rc) return rc;
+  rc = arena_fill(ctx, ar_tab, ctx->rhs_tab.p, ctx->stream); if (rc) return rc;
+  rc = arena_fill(ctx, ar_scr, ctx->ws.p, ctx->stream); if (rc) return rc;
+  char* tab = (char*)ctx->rhs_tab.p + o_tab;
+  char* d_run = out_running ? (char*)ctx->rhs_tab.p + o_run : nullptr;
+  auto staged_done = [&](int status) { return arena_done(ctx, ar_scr, ctx->ws.p, ctx->stream, arena_done(ctx, ar_tab, ctx->rhs_tab.p, ctx->stream, status)); };
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
   with_curve(curve, [&](auto cv) {
     hipLaunchKernelGGL((k_precompute_mult_affine<typename decltype(cv)::F>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
   });
   HIPCHK(ctx, hipGetLastError());
   rc = lemsm_rhs_witness_device(ctx, curve, ctx->in_s.p, tab, n, base, a_xy, t, init, d_run, out_totals, out_sum, bad_index);
-  if (rc) return rc;
+  if (rc) return staged_done(rc);
   if (out_running) {
     HIPCHK(ctx, hipMemcpyAsync(out_running, d_run, pl.num_terms * 32, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
-  return LEMSM_OK;
+  return staged_done(LEMSM_OK);
 }
 
 int lemsm_fraction_sums_device(lemsm_ctx* ctx, int curve, const void* d_num, const void* d_den, size_t n, size_t chains,
@@ -273,19 +292,21 @@ int lemsm_fraction_sums(lemsm_ctx* ctx, int curve, const uint64_t* num, const ui
   if (n == 0) return lemsm_fraction_sums_device(ctx, curve, nullptr, nullptr, 0, chains, init, nullptr, out_totals, bad_index);
   if (n > (size_t)-1 / 128) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t col = align_up(n * 32, 256);
-  rc = reserve(ctx, ctx->rhs_tab, 3 * col + 256); if (rc) return rc;
+  Arena ar("fs_staged", ctx->opt.ws_canary != 0);
+  const size_t o_num = ar.take("numerators", n * 32), o_den = ar.take("denominators", n * 32), o_run = ar.take("running", n * 32);
+  rc = reserve(ctx, ctx->rhs_tab, ar.total() + 256); if (rc) return rc;   // (+ 256 nobody reads)
   char* b = (char*)ctx->rhs_tab.p;
-  char* d_num = num ? b : nullptr; char* d_den = b + col; char* d_run = out_running ? b + 2 * col : nullptr;
+  rc = arena_fill(ctx, ar, b, ctx->stream); if (rc) return rc;
+  char* d_num = num ? b + o_num : nullptr; char* d_den = b + o_den; char* d_run = out_running ? b + o_run : nullptr;
   if (num) HIPCHK(ctx, hipMemcpyAsync(d_num, num, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_den, den, n * 32, hipMemcpyHostToDevice, ctx->stream));
   rc = lemsm_fraction_sums_device(ctx, curve, d_num, d_den, n, chains, init, d_run, out_totals, bad_index);
-  if (rc) return rc;
+  if (rc) return arena_done(ctx, ar, b, ctx->stream, rc);
   if (out_running) {
     HIPCHK(ctx, hipMemcpyAsync(out_running, d_run, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
-  return LEMSM_OK;
+  return arena_done(ctx, ar, b, ctx->stream, LEMSM_OK);
 }
 
 int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) {

@@ -310,7 +310,9 @@ int lemsm_lhs_combine(int curve, uint8_t base, const uint8_t* partials_all_posit
    require_zero_sum != 0: LEMSM_ERR_SUM_NOT_IDENTITY when the points do not sum to the identity (panic at :478).
    out_point_affine (optional): the tree's output = minus the sum of the points (the `.1` of _partial).
    LEMSM_ERR_ARITH_OVERFLOW: two empty polynomials meet in a product (usize underflow at :55, a panic in the reference:
-   four identity points in an aligned group of four). */
+   four identity points in an aligned group of four).
+   LEMSM_ERR_BAD_ARG when cap_a < *len_a or cap_b < *len_b: both lengths are set, out_a and out_b are untouched and no
+   work of the call is left queued. */
 int lemsm_divisor_witness(lemsm_ctx* ctx, int curve, const uint64_t* points_affine, size_t n, int require_zero_sum,
                           int normalise, uint64_t* out_a, size_t cap_a, size_t* len_a, uint64_t* out_b, size_t cap_b,
                           size_t* len_b, uint64_t out_point_affine[8]);
@@ -321,7 +323,9 @@ int lemsm_divisor_witness_device(lemsm_ctx* ctx, int curve, const void* d_points
    count of a single tree).  list t = counts[t] affine points, lists concatenated.  out_index: T x 4 entries
    {offset_a, len_a, offset_b, len_b} in elements of 4 limbs into out_coeffs (a list of n points gives n + 1 coefficients in
    all unless identities or P / -P pairs make the reference carry zero padding: 2 sum(counts) + 4 T elements always suffice);
-   out_points_affine (optional): T x 8 limbs.  With require_zero_sum the first offending list is in lemsm_last_bad_index. */
+   out_points_affine (optional): T x 8 limbs.  With require_zero_sum the first offending list is in lemsm_last_bad_index.
+   LEMSM_ERR_BAD_ARG when cap_coeffs is too small: out_index then holds the complete layout (the elements the call needs
+   are offset_b + len_b of its last row), out_coeffs is untouched and no work of the call is left queued. */
 int lemsm_divisor_witness_batch(lemsm_ctx* ctx, int curve, const uint64_t* points_affine, const size_t* counts, size_t T,
                                 int require_zero_sum, int normalise, uint64_t* out_coeffs, size_t cap_coeffs,
                                 size_t* out_index, uint64_t* out_points_affine);
@@ -337,7 +341,10 @@ int lemsm_divisor_last_ntt(const lemsm_ctx* ctx, double* ms, uint64_t* algorithm
    witnesses of :129 (function f = digit iteration d - 1 - f, the reference's `ret.reverse()` order).
    out_coeffs: cap_coeffs field elements (4 limbs each); out_index: d x 4 entries {offset_a, len_a, offset_b, len_b} in
    elements; a function over a list of c points has c + 1 coefficients in all (up to 2 c + 2 when identities or
-   opposite points make the reference carry zero padding): 2 d (n + base + 3) elements always suffice. */
+   opposite points make the reference carry zero padding): 2 d (n + base + 3) elements always suffice.
+   LEMSM_ERR_BAD_ARG when cap_coeffs is too small (this entry, _device and _device_range alike): out_carry and the
+   complete out_index are set (the elements the call needs are offset_b + len_b of its last row), out_coeffs is
+   untouched -- nothing has been copied into it -- and no work of the call is left queued. */
 int lemsm_lhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n,
                       uint8_t base, uint64_t out_carry[12], uint64_t* out_coeffs, size_t cap_coeffs, size_t* out_index,
                       int normalise, size_t* bad_index);
@@ -603,6 +610,14 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 /* Plain transform over bn256::Fr of nseq sequences of 2^logn elements, natural order in and out, with the reference's
    omega = FftPrecomp::omega_pow(S - logn) (src/regular_functions_utils.rs:111-124); the inverse is scaled by 1/N. */
 int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, int inverse);
+/* Self-test of the workspace guards (option "ws_canary": a 256-byte pattern behind every sub-buffer the library carves
+   out of its device workspaces -- the MSM window group, the divisor-witness forest and its tables, the lhs / rhs witness
+   and fraction-sum engines, the regular-function entries, lemsm_debug_ntt -- checked when the call's kernels have run; a
+   damaged zone is LEMSM_ERR_HIP with "workspace guard <arena>/<block> overwritten at byte <k> (option ws_canary)" in
+   lemsm_last_error).  Carves the blocks "first", "second", "third" of an arena "selftest" in the context's workspace,
+   overwrites byte `byte` (< 256) of the zone behind block `which` (0..2; -1: none) with a memset and runs the check:
+   LEMSM_ERR_HIP naming block and byte, LEMSM_OK for -1.  No kernel runs and nothing outside the workspace is written. */
+int lemsm_debug_arena_selftest(lemsm_ctx* ctx, int which, uint32_t byte);
 /* One-GPU rehearsal of the sharded entries: the pipelines of all `world` ranks run one after the other on this
    context and their record areas are placed where the all-gather would put them; everything but the ncclAllGather
    call itself is the code of lemsm_*_sharded_device. */

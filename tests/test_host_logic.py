@@ -190,6 +190,20 @@ def test_host_tail_under_asan_ubsan(tmp_path):
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_arena_helper_on_a_host_buffer(tmp_path, sanitize):
+    """the workspace carving helper (csrc/arena.hpp) alone on a host buffer (tests/arena_check.cpp): guard-off offsets equal
+    the plain align_up chain, every guarded sub-buffer is followed by 256 pattern bytes of its own, and one flipped byte is
+    reported with its sub-buffer's name and offset"""
+    import subprocess
+    exe = tmp_path / "arena_check"
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] if sanitize else []
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", *flags, "-o", str(exe), os.path.join(ROOT, "tests", "arena_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "arena ok" in out.stdout, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
 def test_oracle_c_under_asan_ubsan():
     """the C oracle (test infrastructure) rebuilt with -fsanitize=address,undefined (`make -C oracle asan`) and the golden-vector
     tests of tests/test_oracle_golden.py run against that build in a child interpreter with libasan preloaded"""
