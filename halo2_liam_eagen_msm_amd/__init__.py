@@ -13,4 +13,5 @@ from .api import (  # noqa: F401
     to_curve_x, y_from_x, slope, WouldNotTerminate,
     RefDivisionByZero, regfn_eval_plan, regular_function_ev, regular_function_ev_unchecked,
     regfn_logderiv_plan, argument_residual, compute_lhs_logderiv,
+    column_plan, assemble_column_a, compute_poly_rlc,
 )

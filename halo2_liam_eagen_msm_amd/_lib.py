@@ -29,6 +29,8 @@ LEMSM_ERR_SUM_NOT_IDENTITY = 12
 LEMSM_ERR_WOULD_NOT_TERMINATE = 13
 LEMSM_ERR_DIVISION_BY_ZERO = 14
 LEMSM_COMM_ID_BYTES = 128
+LEMSM_FORM_MONTGOMERY = 0
+LEMSM_FORM_CANONICAL = 1
 
 BN254_G1 = 0
 GRUMPKIN = 1
@@ -64,6 +66,7 @@ SYMBOLS = [
     "lemsm_debug_regfn_deriv", "lemsm_argument_residual",
     "lemsm_rhs_plan", "lemsm_multiples_table_device", "lemsm_rhs_witness_device", "lemsm_rhs_witness",
     "lemsm_fraction_sums_device", "lemsm_fraction_sums", "lemsm_rhs_last",
+    "lemsm_column_plan", "lemsm_column_a_device", "lemsm_column_a", "lemsm_poly_rlc_device", "lemsm_poly_rlc", "lemsm_column_last",
 ]
 
 
@@ -197,6 +200,12 @@ def load() -> ctypes.CDLL:
         "lemsm_fraction_sums_device": (i, [vp, i, vp, vp, sz, sz, u64p, vp, u64p, szp]),
         "lemsm_fraction_sums": (i, [vp, i, u64p, u64p, sz, sz, u64p, u64p, u64p, szp]),
         "lemsm_rhs_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_column_plan": (i, [vp, sz, sz, sz, sz, sz, szp, szp, szp, szp, szp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
+        "lemsm_column_a_device": (i, [vp, i, vp, sz, vp, sz, sz, sz, i, vp, sz, szp]),
+        "lemsm_column_a": (i, [vp, i, u64p, sz, vp, sz, sz, sz, i, u64p, sz, szp]),
+        "lemsm_poly_rlc_device": (i, [vp, i, vp, i, sz, sz, sz, sz, u64p, vp, sz]),
+        "lemsm_poly_rlc": (i, [vp, i, u64p, i, sz, sz, sz, sz, u64p, u64p, sz]),
+        "lemsm_column_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

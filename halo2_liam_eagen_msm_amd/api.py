@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BN254_G1, GRUMPKIN
+from ._lib import LEMSM_FORM_CANONICAL as FORM_CANONICAL, LEMSM_FORM_MONTGOMERY as FORM_MONTGOMERY
 
 ORDER = {
     BN254_G1: 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
@@ -694,6 +695,72 @@ class Context:
         self._check(self.lib.lemsm_rhs_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- advice column a and the "polynomials random linear combination" gate (src/layout.md:7, src/config.rs:246-283) ----
+    def column_a_device(self, curve, d_coeffs: int, cap: int, index, batch_offset: int = 0, num_batches: int = 0,
+                        form: int = _lib.LEMSM_FORM_MONTGOMERY, out: Optional[DeviceBuffer] = None):
+        """advice column a (include/lemsm.h) of the functions `index` describes -- (T, 4) rows into the `cap`
+        32-byte coefficients at device pointer d_coeffs, what lhs_witness_device returns -- without a coefficient leaving HBM:
+        (DeviceBuffer of num_batches (T + batch_offset) rows of 32 B, num_batches).  form: FORM_MONTGOMERY (the cells as
+        halo2 holds them) or FORM_CANONICAL (the scalars msm_device("bn254_g1", ...) takes).  num_batches 0: the minimum."""
+        index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+        plan = column_plan(index, cap, batch_offset, 1, num_batches)
+        if out is None:
+            out = DeviceBuffer(self, max(plan["rows"] * 32, 16))
+        nb = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_column_a_device(self.h, _curve_id(curve), d_coeffs, cap, _ptr(index) if index.size else None, index.shape[0],
+                                            batch_offset, num_batches, int(form), out.ptr, out.nbytes // 32, ctypes.byref(nb))
+        self._check(rc)
+        return out, nb.value
+
+    def column_a(self, curve, fns, batch_offset: int = 0, num_batches: int = 0, form: int = _lib.LEMSM_FORM_MONTGOMERY):
+        """the same for fns = [(a, b), ...] coefficient arrays in host memory, as lhs_witness returns them:
+        (column (num_batches, T + batch_offset, 4) uint64, num_batches)"""
+        coeffs, index, used = _pack_fns(fns)
+        plan = column_plan(index, used, batch_offset, 1, num_batches)
+        out = np.zeros((plan["num_batches"], plan["batch_size"], 4), np.uint64)
+        nb = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_column_a(self.h, _curve_id(curve), _ptr(coeffs) if used else None, used, _ptr(index) if index.size else None,
+                                     index.shape[0], batch_offset, num_batches, int(form), _ptr(out) if out.size else None, plan["rows"],
+                                     ctypes.byref(nb))
+        self._check(rc)
+        return out, nb.value
+
+    def poly_rlc_device(self, curve, d_column: int, T: int, batch_offset: int, poly_fan_in: int, num_batches: int, r,
+                        form: int = _lib.LEMSM_FORM_MONTGOMERY, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """the column-c cells of the "polynomials random linear combination" gate (src/config.rs:246-283) from a column a
+        resident at device pointer d_column (num_batches (T + batch_offset) rows in `form`): DeviceBuffer of
+        num_batches c_skip cells, raw Montgomery, cell (j, t) at j c_skip + t.  r: 4 raw Montgomery limbs."""
+        plan = column_plan(np.zeros((0, 4), np.uintp), 0, T + batch_offset, poly_fan_in, num_batches)
+        rr = np.ascontiguousarray(r, np.uint64).reshape(4)
+        if out is None:
+            out = DeviceBuffer(self, max(plan["cells"] * 32, 16))
+        rc = self.lib.lemsm_poly_rlc_device(self.h, _curve_id(curve), d_column, int(form), T, batch_offset, poly_fan_in, num_batches, _ptr(rr),
+                                            out.ptr, out.nbytes // 32)
+        self._check(rc)
+        return out
+
+    def poly_rlc(self, curve, column, T: int, batch_offset: int, poly_fan_in: int, r, form: int = _lib.LEMSM_FORM_MONTGOMERY) -> np.ndarray:
+        """the same for a column in host memory ((num_batches, T + batch_offset, 4) or flat): (num_batches, c_skip, 4) cells"""
+        col = _limbs(column, 4) if np.size(column) else np.zeros((0, 4), np.uint64)
+        bs = T + batch_offset
+        if bs == 0 or col.shape[0] % bs:
+            if col.shape[0]:
+                raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the column is not a whole number of batches")
+        nb = col.shape[0] // bs if bs else 0
+        plan = column_plan(np.zeros((0, 4), np.uintp), 0, bs, poly_fan_in, nb)
+        rr = np.ascontiguousarray(r, np.uint64).reshape(4)
+        out = np.zeros((nb, plan["c_skip"], 4), np.uint64)
+        rc = self.lib.lemsm_poly_rlc(self.h, _curve_id(curve), _ptr(col) if col.size else None, int(form), T, batch_offset, poly_fan_in, nb,
+                                     _ptr(rr), _ptr(out) if out.size else None, plan["cells"])
+        self._check(rc)
+        return out
+
+    def column_last(self) -> Tuple[float, int, int]:
+        """(device ms, bytes, field_mults) of the last column_a* / poly_rlc* call"""
+        ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_column_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
+        return ms.value, by.value, fm.value
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -982,6 +1049,34 @@ def rhs_plan(curve, base: int, n: int) -> dict:
     return {"num_terms": nt.value, "table_bytes": tb.value, "out_bytes": ob.value, "field_mults": fm.value}
 
 
+def _pack_fns(fns):
+    """[(a, b), ...] -> (coefficients (used, 4), index (T, 4), used): the layout the witness entries write"""
+    parts, rows, used = [], [], 0
+    for f in fns:
+        a = _limbs(f[0], 4) if np.size(f[0]) else np.zeros((0, 4), np.uint64)
+        b = _limbs(f[1], 4) if np.size(f[1]) else np.zeros((0, 4), np.uint64)
+        rows.append((used, a.shape[0], used + a.shape[0], b.shape[0]))
+        parts += [a, b]; used += a.shape[0] + b.shape[0]
+    coeffs = np.concatenate(parts) if used else np.zeros((0, 4), np.uint64)
+    return coeffs, np.array(rows, np.uintp).reshape(-1, 4), used
+
+
+def column_plan(index, cap: int, batch_offset: int = 0, poly_fan_in: int = 1, num_batches: int = 0) -> dict:
+    """the layout of advice column a and of its RLC cells (pure host: lemsm_column_plan): {"batch_size", "c_skip",
+    "num_batches", "rows", "cells", "coeff_bytes", "column_bytes", "assembly_field_mults", "rlc_field_mults"}; raises
+    LemsmError (LEMSM_ERR_BAD_ARG) where the device entries would"""
+    lib = _lib.load()
+    index = np.ascontiguousarray(index, np.uintp).reshape(-1, 4)
+    s = [ctypes.c_size_t() for _ in range(5)]
+    u = [ctypes.c_uint64() for _ in range(4)]
+    rc = lib.lemsm_column_plan(_ptr(index) if index.size else None, index.shape[0], cap, batch_offset, poly_fan_in, num_batches,
+                               *[ctypes.byref(x) for x in s], *[ctypes.byref(x) for x in u])
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    keys = ("batch_size", "c_skip", "num_batches", "rows", "cells", "coeff_bytes", "column_bytes", "assembly_field_mults", "rlc_field_mults")
+    return dict(zip(keys, [x.value for x in s + u]))
+
+
 def comm_unique_id() -> bytes:
     """rank 0: the 128-byte RCCL unique id every rank passes to Context.comm_init"""
     buf = np.zeros(_lib.LEMSM_COMM_ID_BYTES, np.uint8)
@@ -1137,6 +1232,25 @@ def compute_rhs_witness(scalars, pts, base: int, A, t=None, curve="grumpkin", ct
     stub): (running (n, base-1, 4), totals (base-1, 4), sum (4,)) for scalars (n, 32), Jacobian pts (n, 12), the challenge
     point A (8 limbs) and t (4 limbs; None: the tangent slope at A, src/config.rs:184-187)."""
     return (ctx or default_context()).rhs_witness(curve, scalars, pts, base, A, t, init)
+
+
+def assemble_column_a(fns, batch_offset: int = 0, num_batches: int = 0, canonical: bool = False, curve="grumpkin",
+                      ctx: Optional[Context] = None):
+    """Advice column a of the reference's circuit (src/layout.md:7; upstream's synthesize is a stub, src/config.rs:635-683) from
+    the functions compute_lhs_witness returns: (column (num_batches, len(fns) + batch_offset, 4), num_batches) -- batch j holds
+    monomial j (pole order) of every function, row f of a batch belongs to function f.  canonical=True: 32-byte standard-form
+    scalars, what best_multiexp over BN254 G1 commits to."""
+    form = _lib.LEMSM_FORM_CANONICAL if canonical else _lib.LEMSM_FORM_MONTGOMERY
+    return (ctx or default_context()).column_a(curve, fns, batch_offset, num_batches, form)
+
+
+def compute_poly_rlc(column, T: int, batch_offset: int, poly_fan_in: int, r, canonical: bool = False, curve="grumpkin",
+                     ctx: Optional[Context] = None) -> np.ndarray:
+    """The advice cells of column c that the reference's "polynomials random linear combination" gate fixes
+    (src/config.rs:246-283): (num_batches, c_skip, 4) raw Montgomery limbs for a column a of batches of T + batch_offset rows
+    and the challenge r (4 raw Montgomery limbs); canonical=True: the column holds standard-form scalars."""
+    form = _lib.LEMSM_FORM_CANONICAL if canonical else _lib.LEMSM_FORM_MONTGOMERY
+    return (ctx or default_context()).poly_rlc(curve, column, T, batch_offset, poly_fan_in, r, form)
 
 
 def compute_lhs_logderiv(fns, A, base: int, curve="grumpkin", ctx: Optional[Context] = None):

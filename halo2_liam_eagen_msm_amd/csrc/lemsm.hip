@@ -26,6 +26,7 @@
 #include "regfn_eval.cuh"
 #include "regfn_logderiv.cuh"
 #include "rhs.cuh"
+#include "column.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -149,6 +150,8 @@ struct lemsm_ctx {
   double ld_ms = 0; u64 ld_bytes = 0, ld_mults = 0;   // lemsm_regfn_logderiv_last
   DevBuf rhs_ws, rhs_tab, rhs_pw;    // rhs witness / fraction sums: engine workspace, table + staged columns (host entries), powers of -base
   double rhs_ms = 0; u64 rhs_bytes = 0, rhs_mults = 0;   // lemsm_rhs_last
+  DevBuf col_ws, col_stage;          // column a / poly rlc: function and power tables, staged inputs + outputs (host entries)
+  double col_ms = 0; u64 col_bytes = 0, col_mults = 0;   // lemsm_column_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
   int plan_world = 1;   // ranks sharing the current call's windows: > 1 pins 16-bit windows (16 split evenly over 2/4/8 ranks, 15 do not)
@@ -1756,7 +1759,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);
@@ -2660,3 +2663,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "regfn_abi.inc"
 #include "regfn_logderiv_abi.inc"
 #include "rhs_abi.inc"
+#include "column_abi.inc"

@@ -509,6 +509,65 @@ int lemsm_fraction_sums(lemsm_ctx* ctx, int curve, const uint64_t* num, const ui
    (src/config.rs:504-538, :402-437) */
 int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
 
+/* ---- advice column a and its polynomial-RLC cells (src/layout.md:7, src/config.rs:246-283) ---- */
+/* In the reference's circuit the coefficients of the d divisor witnesses ARE advice column a: one batch of batch_size rows
+   holds the same coefficient of each function (src/layout.md:7, src/layout.md.bac:30-34), batch_size = T + batch_offset
+   (params_check, src/config.rs:45) with T the number of index rows -- the functions lemsm_lhs_witness* actually returns, not
+   params_check's num_digits (:42), which is one short of compute_lhs_witness's d and overflows its u8 for base >= 16.
+   Row f < T of a batch belongs to function f (index row f); rows T .. batch_size - 1 are zero.  "The same coefficient" is the
+   same monomial, the monomials in pole order (x^i: 2 i, y x^i: 2 i + 3, as `normalise` orders them; order 1 does not exist):
+     batch 0 = a_0,  batch 2 i - 1 = a_i (i >= 1),  batch 2 i + 2 = b_i;   row j batch_size + f = monomial j of function f.
+   A function needs max(row(a_{len_a - 1}), row(b_{len_b - 1})) + 1 batches (0 when empty); batches with no coefficient of a
+   function hold zero in its row; num_batches = the largest such count, or a larger caller-given value (upstream pads to
+   N + B + 1, src/layout.md.bac:19): the surplus batches are zero.
+   The "polynomials random linear combination" gate (src/config.rs:246-283; synthesize is a stub, :635-683) fixes the last
+   c_skip = ceil(batch_size / poly_fan_in) rows (:46) of each batch in column c: with F = poly_fan_in, for t < c_skip
+     c_0 = sum_i r^i a[j][i c_skip],   c_t = c_{t-1} r^F + sum_i r^i a[j][t + i c_skip]   (t >= 1),
+   term i < F present exactly when t + i c_skip < batch_size (the gate's full form where its last operand is a row of the
+   batch, its truncated form :273-276 where it is not; the selectors as written, :299-325, never enable the full form and can
+   reach into the next batch -- DESIGN 7b).  Every row of the batch enters exactly once: the last cell is
+   sum_i r^e(i) a[j][i], e(i) = floor(i / c_skip) + F (c_skip - 1 - i mod c_skip).
+   Grumpkin only (LEMSM_ERR_BAD_CURVE otherwise), like the witness entries: the cells lie in bn256::Fr. */
+enum lemsm_form {
+  LEMSM_FORM_MONTGOMERY = 0,   /* 4 raw Montgomery limbs: the cells as halo2 holds advice values, what every field kernel reads */
+  LEMSM_FORM_CANONICAL = 1     /* 32-byte little-endian standard form: what the MSM entries take as scalars */
+};
+/* Pure host: validates a layout and prices it.  index: T x 4 rows as lemsm_regfn_eval_plan validates them (offset + len
+   past cap_coeffs or wrapping: LEMSM_ERR_BAD_ARG); poly_fan_in == 0, num_batches != 0 but smaller than the functions need,
+   or a row count whose bytes overflow size_t: LEMSM_ERR_BAD_ARG.  num_batches == 0: the minimum.  T == 0 is allowed.
+   rows = num_batches batch_size, cells = num_batches c_skip.  The floor's ingredients: the assembly reads coeff_bytes =
+   32 sum (len_a + len_b) and writes column_bytes = 32 rows, with assembly_field_mults = sum (len_a + len_b) products for
+   the canonical form (none for the Montgomery form); the RLC reads column_bytes, writes 32 cells and takes
+   rlc_field_mults products: per batch one per row plus the scan's (per 64 cells sum over off = 1, 2, 4 .. < n of n - off,
+   n the cells of that group, and n more for every group after the first).  (src/config.rs:39-48, :246-283) */
+int lemsm_column_plan(const size_t* index, size_t T, size_t cap_coeffs, size_t batch_offset, size_t poly_fan_in, size_t num_batches,
+                      size_t* out_batch_size, size_t* out_c_skip, size_t* out_num_batches, size_t* out_rows, size_t* out_cells,
+                      uint64_t* coeff_bytes, uint64_t* column_bytes, uint64_t* assembly_field_mults, uint64_t* rlc_field_mults);
+/* Column a from coefficients resident in HBM (d_coeffs, cap_coeffs, index, T: as lemsm_regfn_eval_device takes them, e.g.
+   what lemsm_lhs_witness_device left there) into d_out_column: rows x 32 B in HBM, in `form`.  The canonical form is exactly
+   what lemsm_msm_device(LEMSM_BN254_G1, ...) takes as scalars: bn256::Fr is the scalar field of BN254 G1, so the first-phase
+   commitment to the column is that MSM.  num_batches: 0 = minimal; *out_num_batches (optional) = the count laid out.
+   cap_rows < rows: LEMSM_ERR_BAD_ARG, the output is untouched and no work is left queued (as the witness entries).
+   (src/layout.md:7, src/layout.md.bac:30-34) */
+int lemsm_column_a_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                          size_t batch_offset, size_t num_batches, int form, void* d_out_column, size_t cap_rows, size_t* out_num_batches);
+/* The same with the coefficients and the column in host memory (uploaded, the device path, downloaded).  (src/layout.md:7) */
+int lemsm_column_a(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,
+                   size_t batch_offset, size_t num_batches, int form, uint64_t* out_column, size_t cap_rows, size_t* out_num_batches);
+/* The gate's cells from a column a resident in HBM (d_column: num_batches (T + batch_offset) x 32 B in `form`; a canonical
+   column costs nothing extra, the factor is folded into the power table).  r: the challenge, 4 raw Montgomery limbs
+   (not canonical: LEMSM_ERR_BAD_ARG).  d_out_cells: num_batches c_skip x 32 B, raw Montgomery like every other cell entry,
+   cell (j, t) at j c_skip + t.  Sums run in a fixed order: repeated calls, and the host and the device entry, give the same
+   bytes.  cap_cells too small: LEMSM_ERR_BAD_ARG, output untouched.  (src/config.rs:246-283) */
+int lemsm_poly_rlc_device(lemsm_ctx* ctx, int curve, const void* d_column, int form, size_t T, size_t batch_offset, size_t poly_fan_in,
+                          size_t num_batches, const uint64_t r[4], void* d_out_cells, size_t cap_cells);
+/* The same with the column and the cells in host memory.  (src/config.rs:246-283) */
+int lemsm_poly_rlc(lemsm_ctx* ctx, int curve, const uint64_t* column, int form, size_t T, size_t batch_offset, size_t poly_fan_in,
+                   size_t num_batches, const uint64_t r[4], uint64_t* out_cells, size_t cap_cells);
+/* Device time (ms, HIP events around the launch on the context's stream) of the last lemsm_column_a* / lemsm_poly_rlc* call,
+   and the bytes (read + written) and field multiplications its plan prices it with.  (src/config.rs:246-283) */
+int lemsm_column_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
