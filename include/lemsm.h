@@ -72,6 +72,15 @@ enum lemsm_status {
 };
 
 /* ---- context ------------------------------------------------------------------------- */
+/* Threading.  Any host thread may call any entry; a context is not tied to the thread that created it, and every entry
+   is synchronous (results are final on return).  A context -- together with its host worker pool (option "host_threads"),
+   its options (lemsm_set_option), its last_* state (lemsm_last_error, lemsm_last_bad_index, lemsm_last_truncated_count, the
+   *_last telemetry getters) and the resident objects made through it (lemsm_device_alloc buffers, bases, fixed-base tables)
+   -- serves ONE call at a time: the caller serialises the calls on one context, lemsm_destroy included; the pool is not
+   reentrant.  Distinct contexts may be used concurrently from different threads, including several contexts on one
+   device; lemsm_create / lemsm_destroy may run beside calls on other contexts.  Device pointers are only read by the
+   entries that take them as inputs, so several contexts may read the same resident scalars / points at once.
+   (tests/test_gpu_concurrency.py, tests/hostpool_race_check.cpp) */
 int lemsm_create(int device, lemsm_ctx** out);
 void lemsm_destroy(lemsm_ctx* ctx);
 const char* lemsm_strerror(int status);

@@ -1,0 +1,570 @@
+"""Child process of tests/test_gpu_concurrency.py: one scenario of the per-context threading contract (include/lemsm.h,
+"Threading") on device 0.  Usage: python concurrency_child.py ROOT SCENARIO.  Not a test module.
+
+Every expected value comes from the oracle (oracle/cref.py, tests/rhs_ref.py, tests/column_ref.py, oracle/divisor.py) and is
+computed single-threaded before any thread starts.  The threads are threading.Thread; ctypes releases the GIL for the
+duration of a CDLL call, so the library calls of different threads do overlap; all threads leave one threading.Barrier
+before their first call and every call's (start, end) on time.perf_counter() is kept.  Every context has ws_canary = 1.
+
+Scenarios 1-4 first make every thread's call list serially, on the same contexts and for the same number of rounds; the
+first serial output of every call is checked against the oracle, every later output -- serial or concurrent -- must equal it
+limb for limb (raw Jacobian limbs, raw coefficient arrays).  The Jacobian outputs of an entry named in CANON_ONLY are compared
+in canonical form instead: two serial runs of it already differ in raw limbs (profiles/concurrency/NOTES.md says why); its
+other outputs stay limb-exact.  The last line printed is "RESULT <json>": rounds, calls, the share of
+calls that overlapped a call of another thread, and the wall time of the concurrent phase and of the serial one.
+
+Exit status 0 and the RESULT line: the scenario held.  Anything else: the first failure's message on stderr."""
+import json
+import os
+import sys
+import threading
+import time
+
+ROOT = sys.argv[1]
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np                                             # noqa: E402
+
+from halo2_liam_eagen_msm_amd import Context, _lib, api       # noqa: E402
+from oracle import cref, pyref                                 # noqa: E402
+from oracle import divisor as dv                               # noqa: E402
+import column_ref                                              # noqa: E402
+import rhs_ref                                                 # noqa: E402
+
+BN, GR = pyref.BN254_G1, pyref.GRUMPKIN
+P = GR.fp
+R = 1 << 256
+RI = pow(R, -1, P)
+THREADS = 8                      # of the C oracle
+# entry family -> why the group elements among its outputs are compared in canonical form only, between runs as against the
+# oracle: two SERIAL runs of the same call on the same context already differ in raw Jacobian limbs (profiles/concurrency/NOTES.md)
+SORT_ORDER = ("the bucket sort claims a block's run inside a bin and ranks entries with atomics (kernels.cuh k_pip_digits / k_count1 / "
+              "k_scatter1 / k_binsort), so the order of a bucket's entries, hence the projective representative of its sum, varies from run to run")
+CANON_ONLY = {"msm_device": SORT_ORDER, "lhs_msm_device": SORT_ORDER, "msm_fixed_device": SORT_ORDER,
+              "lhs_witness": SORT_ORDER + " (the carry, its only Jacobian output; the coefficients are compared limb for limb)"}
+KEEP = []                        # device buffers stay referenced until the scenario is over: nothing is freed by a collector
+                                 # run on some other thread while the owning context is inside a call
+
+
+class Failure(Exception):
+    pass
+
+
+def need(cond, *what):
+    if not cond:
+        raise Failure(" ".join(str(w) for w in what))
+
+
+def new_ctx():
+    c = Context(0)
+    c.set_option("ws_canary", 1)
+    return c
+
+
+def dev(ctx, arr):
+    b = ctx.to_device(arr); KEEP.append(b)
+    return b
+
+
+def omega0():
+    with open(os.path.join(ROOT, "tests", "golden", "fr_mont_chains.json")) as f:
+        return np.frombuffer(bytes.fromhex(json.load(f)["omega_pow"]["head"]), np.uint64).copy()
+
+
+def ints(arr):
+    b = np.ascontiguousarray(arr, np.uint64).tobytes()
+    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
+
+
+def std(arr, p=P):
+    ri = pow(R, -1, p)
+    return [v * ri % p for v in ints(arr)]
+
+
+def fe(v, p=P):
+    return np.frombuffer((v * R % p).to_bytes(32, "little"), np.uint64).copy()
+
+
+def normalise(f):
+    return dv.DivisorOracle(GR).normalise(f)
+
+
+def canon_points(cid, rows):
+    rows = np.ascontiguousarray(rows, np.uint64).reshape(-1, 12)
+    return b"".join(cref.jac_to_canonical(cid, r) for r in rows)
+
+
+class Call:
+    """one library call of a thread's list: fn() -> list of numpy arrays (the raw outputs); verify(raw) compares them with
+    the oracle"""
+
+    def __init__(self, name, family, fn, verify, group=None, after=None):
+        self.name, self.family, self.fn, self.verify, self.after = name, family, fn, verify, after
+        self.group = group or {}           # position in the output list -> curve id, for the outputs that are Jacobian points
+        self.ref = None
+
+    def differs_from_ref(self, raw):
+        """None, or which output differs from the first serial run's"""
+        if len(raw) != len(self.ref):
+            return "the number of outputs"
+        for k, (a, b) in enumerate(zip(raw, self.ref)):
+            if a.shape != b.shape:
+                return "the shape of output %d" % k
+            if k in self.group and self.family in CANON_ONLY:
+                if canon_points(self.group[k], a) != canon_points(self.group[k], b):
+                    return "output %d (Jacobian, compared in canonical form)" % k
+            elif not np.array_equal(a, b):
+                return "output %d (raw limbs)" % k
+        return None
+
+
+# ---- call builders: inputs uploaded through `ctx`, expectation from the oracle ---------------------------------------------
+def points(cid, seed, n):
+    """n distinct affine points: k_i G for random k_i up to 5000 points, beyond that the walk Q, 2 Q, ... of a random Q (the
+    oracle spends a scalar multiplication per random point)"""
+    return cref.gen_points(cid, seed, n) if n <= 5000 else cref.gen_walk(cid, cref.gen_points(cid, seed, 1)[0], n)
+
+
+def msm_inputs(cid, n, seed):
+    pts = points(cid, seed, n); sc = cref.gen_scalars(cid, seed + 1, n)
+    return sc, pts, cref.jac_to_canonical(cid, cref.best_multiexp(cid, sc, pts, THREADS))
+
+
+def msm_call(ctx, cid, n, inputs, d_sc=None, d_pts=None, name=None):
+    sc, pts, exp = inputs
+    ds = d_sc or dev(ctx, sc); dp = d_pts or dev(ctx, pts)
+
+    def verify(raw):
+        need(raw[0].shape == (12,) and cref.jac_to_canonical(cid, raw[0]) == exp, "msm_device differs from the oracle")
+    return Call(name or "msm_device n=%d" % n, "msm_device", lambda: [ctx.msm_device(cid, ds.ptr, dp.ptr, n)], verify, {0: cid})
+
+
+def lhs_inputs(cid, n, base, seed):
+    pts = cref.gen_points(cid, seed, n); sc = cref.gen_scalars(cid, seed + 1, n, half=True)
+    carry, carries = cref.lhs_msm(cid, sc, cref.aff_to_jac(cid, pts), base)
+    return sc, pts, (cref.jac_to_canonical(cid, carry), canon_points(cid, carries))
+
+
+def lhs_call(ctx, cid, n, base, inputs, d_sc=None, d_pts=None):
+    sc, pts, (ecarry, ecarries) = inputs
+    ds = d_sc or dev(ctx, sc); dp = d_pts or dev(ctx, pts)
+
+    def verify(raw):
+        need(cref.jac_to_canonical(cid, raw[0]) == ecarry, "lhs_msm_device carry differs from the oracle")
+        need(canon_points(cid, raw[1]) == ecarries, "lhs_msm_device per-digit carries differ from the oracle")
+    return Call("lhs_msm_device n=%d base=%d" % (n, base), "lhs_msm_device", lambda: list(ctx.lhs_msm_device(cid, ds.ptr, dp.ptr, n, base)), verify,
+                {0: cid, 1: cid})
+
+
+def witness_inputs(n, base, seed):
+    """Grumpkin compute_lhs_witness: the oracle's carry and normalised functions"""
+    sc = cref.gen_scalars(1, seed, n, half=True).reshape(-1, 32).copy()
+    aff = cref.gen_points(1, seed + 1, n).reshape(-1, 8).copy()
+    if n >= 37:
+        aff[3] = 0; sc[5] = 0                                  # an identity among the points, a zero scalar
+    jac = cref.aff_to_jac(1, aff)
+    st, ecarry, efns = cref.lhs_witness(sc, jac, base, omega0(), THREADS)
+    need(st == 0, "oracle lhs_witness status", st)
+    return sc, aff, jac, cref.jac_to_canonical(1, ecarry), [normalise(f) for f in efns]
+
+
+def check_fns(fns, efns, what):
+    """tests/test_gpu_parity.py::_check_witness: lengths exactly, coefficients after normalisation"""
+    need(len(fns) == len(efns), what, "number of functions")
+    for f, ((a, b), (ea, eb)) in enumerate(zip(fns, efns)):
+        need((a.shape[0], b.shape[0]) == (len(ea), len(eb)), what, "lengths of function", f)
+        need(std(a) == ea and std(b) == eb, what, "coefficients of function", f)
+
+
+def lhs_witness_call(ctx, n, base, inputs):
+    sc, aff, jac, ecarry, efns = inputs
+    d = len(efns)
+
+    def fn():
+        carry, fns = ctx.lhs_witness(1, sc, jac, base, True)
+        return [carry] + [np.array(x) for f in fns for x in f]
+
+    def verify(raw):
+        need(cref.jac_to_canonical(1, raw[0]) == ecarry, "lhs_witness carry differs from the oracle")
+        need(len(raw) == 1 + 2 * d, "lhs_witness: number of functions")
+        check_fns([(raw[1 + 2 * f], raw[2 + 2 * f]) for f in range(d)], efns, "lhs_witness n=%d base=%d:" % (n, base))
+    return Call("lhs_witness n=%d base=%d" % (n, base), "lhs_witness", fn, verify, {0: 1})
+
+
+def zero_sum_rows(n, seed):
+    """n Grumpkin affine rows that sum to the identity (n - 1 points and minus their sum; an identity row, a repeated point
+    and a P / -P pair among them)"""
+    rows = cref.gen_points(1, seed, n - 1).reshape(-1, 8).copy()
+    neg = lambda r: np.concatenate([r[:4], np.frombuffer(((P - int.from_bytes(r[4:8].tobytes(), "little")) % P).to_bytes(32, "little"), np.uint64)])
+    rows[2] = 0; rows[5] = rows[4]; rows[7] = neg(rows[6])
+    acc = np.zeros(12, np.uint64)
+    for j in cref.aff_to_jac(1, rows):
+        acc = cref.jac_add(1, acc, j)
+    last = np.zeros(8, np.uint64) if not acc[8:12].any() else neg(np.asarray(cref.jac_to_aff_raw(1, acc), np.uint64).reshape(8))
+    return np.vstack([rows, last.reshape(1, 8)])
+
+
+def divisor_call(ctx, n, seed):
+    rows = zero_sum_rows(n, seed)
+    st, a, b = cref.divisor_witness(cref.aff_to_jac(1, rows), omega0(), THREADS)
+    need(st == 0, "oracle divisor_witness status", st)
+    want = normalise((a, b))
+
+    def verify(raw):
+        check_fns([(raw[0], raw[1])], [want], "divisor_witness n=%d:" % n)
+        need(not raw[2].any(), "divisor_witness: output point is not the identity")
+    return Call("divisor_witness n=%d" % n, "divisor_witness", lambda: list(ctx.divisor_witness(1, rows, True, True)), verify)
+
+
+# ---- running the lists ----------------------------------------------------------------------------------------------------
+class Lane:
+    """one thread: its call list, how many rounds of it, and what it recorded"""
+
+    def __init__(self, name, calls, rounds):
+        self.name, self.calls, self.rounds = name, calls, rounds
+        self.times, self.error = [], None
+
+    def run(self, barrier=None):
+        try:
+            if barrier is not None:
+                barrier.wait(timeout=60)
+            for r in range(self.rounds):
+                for c in self.calls:
+                    t0 = time.perf_counter()
+                    raw = c.fn()
+                    self.times.append((t0, time.perf_counter()))
+                    if c.ref is None:                                  # first serial output: against the oracle
+                        c.verify(raw); c.ref = raw
+                    elif c.ref is not False:
+                        bad = c.differs_from_ref(raw)                  # (equal to an output the oracle confirmed: no second look needed)
+                        need(bad is None, "%s, round %d, %s phase: %s differs from the first serial run's"
+                             % (c.name, r, "concurrent" if barrier is not None else "serial", bad))
+                    if c.after:
+                        c.after(raw, r)
+        except Exception as e:                                         # noqa: BLE001  (reported by the main thread)
+            self.error = "%s: %s: %s" % (self.name, type(e).__name__, e)
+
+
+def overlap_stats(lanes):
+    """(calls, calls that overlapped a call of another lane, per-lane overlapped counts)"""
+    total = hit = 0; per = []
+    for i, a in enumerate(lanes):
+        others = [iv for j, b in enumerate(lanes) if j != i for iv in b.times]
+        k = sum(1 for s, e in a.times if any(s < e2 and s2 < e for s2, e2 in others))
+        total += len(a.times); hit += k; per.append(k)
+    return total, hit, per
+
+
+def run_concurrent(lanes):
+    barrier = threading.Barrier(len(lanes))
+    for ln in lanes:
+        ln.times = []
+    th = [threading.Thread(target=ln.run, args=(barrier,), name=ln.name) for ln in lanes]
+    t0 = time.perf_counter()
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    wall = time.perf_counter() - t0
+    for ln in lanes:
+        need(ln.error is None, ln.error)
+    return wall
+
+
+def finish(scenario, lanes, wall, serial_wall=None, need_overlap=True):
+    total, hit, per = overlap_stats(lanes)
+    if need_overlap:
+        need(hit > 0 and all(per), "vacuous: no call of one thread overlapped a call of another (per thread: %s of %s calls)"
+             % (per, [len(ln.times) for ln in lanes]))
+    print("RESULT " + json.dumps({"scenario": scenario, "threads": len(lanes), "rounds": [ln.rounds for ln in lanes],
+                                  "calls": [len(ln.times) for ln in lanes], "overlapped": per,
+                                  "overlap_share": round(hit / max(total, 1), 3), "concurrent_s": round(wall, 3),
+                                  "serial_s": None if serial_wall is None else round(serial_wall, 3),
+                                  "canonical_only": sorted(CANON_ONLY)}))
+
+
+def serial_then_concurrent(scenario, lanes):
+    t0 = time.perf_counter()
+    for ln in lanes:
+        ln.run(None)
+        need(ln.error is None, ln.error)
+    serial_wall = time.perf_counter() - t0
+    wall = run_concurrent(lanes)
+    finish(scenario, lanes, wall, serial_wall)
+
+
+# ---- scenario 1: different families side by side ---------------------------------------------------------------------------
+def lane_a_calls(ctx):
+    return [msm_call(ctx, 0, n, msm_inputs(0, n, 100 + i)) for i, n in enumerate([1, 300, 4097, 1 << 14, 1 << 16])]
+
+
+def scenario1():
+    a, b = new_ctx(), new_ctx()
+    calls_b = [lhs_witness_call(b, n, base, witness_inputs(n, base, 200 + 10 * base + i)) for base in (16, 5) for i, n in enumerate([7, 300, 1000])]
+    calls_b += [divisor_call(b, n, 300 + n) for n in (33, 1025)]
+    serial_then_concurrent(1, [Lane("A: BN254 G1 msm_device", lane_a_calls(a), ROUNDS[1][0]), Lane("B: Grumpkin witnesses", calls_b, ROUNDS[1][1])])
+    a.close(); b.close()
+
+
+# ---- scenario 2: the same family under different options --------------------------------------------------------------------
+def scenario2():
+    opts = [{"field": 1, "window_bits": 13}, {"abi_points": 2, "entry_ring": 1, "chunk": 8, "merge_slice": 33}]
+    # scalars from a two-letter alphabet: buckets of thousands of entries, so that the edge-record merge queues every class
+    n = 6000
+    rng = np.random.default_rng(2)
+    sc = cref.gen_scalars(0, 902, 2)[rng.integers(0, 2, n)]
+    pts = np.tile(cref.gen_points(0, 901, 128), (n // 128 + 1, 1))[:n]
+    m_in = (sc, pts, cref.jac_to_canonical(0, cref.best_multiexp(0, sc, pts, THREADS)))
+    l_in = lhs_inputs(1, 5000, 5, 910)
+    lanes, msm_alone = [], []
+    for k, o in enumerate(opts):
+        c = new_ctx()
+        for name, v in o.items():
+            c.set_option(name, v)
+        calls = [msm_call(c, 0, n, m_in), lhs_call(c, 1, 5000, 5, l_in)]
+        for call in calls:                                             # the counts of this context's own geometry, call made alone
+            call.fn()
+            alone = c.last_merge_counts()
+            if call.family == "msm_device":
+                need(sum(alone) > 0, "the merge queues stayed empty:", call.name, alone)
+                msm_alone.append(alone)
+
+            def after(raw, r, c=c, alone=alone, call=call):
+                got = c.last_merge_counts()
+                need(got == alone, "%s: merge counts %s are not this context's own %s" % (call.name, got, alone))
+            call.after = after
+        lanes.append(Lane("context %d %s" % (k, o), calls, ROUNDS[2][k]))
+    need(msm_alone[0] != msm_alone[1], "the two geometries queue the same merge counts: the check could not tell them apart", msm_alone)
+    serial_then_concurrent(2, lanes)
+
+
+# ---- scenario 3: more contexts than hardware queues ---------------------------------------------------------------------------
+def rhs_call(ctx, k):
+    base, n = 5, 257
+    rng = pyref.SplitMix64(3300 + k)
+    scalars = pyref.gen_scalars_half(rng, n, GR.order)
+    aff = cref.gen_points(1, 3310 + k, n)
+    pts = [GR.raw_to_affine(r.tobytes()) for r in aff]
+    A = pyref.gen_points(GR, rng, 1)[0]; t = rhs_ref.slope(A, P)
+    table = [rhs_ref.multiples(GR, q, base) for q in pts]
+    rows, totals, total = rhs_ref.running(rhs_ref.terms(scalars, table, base, pyref.num_digits(GR.order, base), A, t, P), base - 1, P, None)
+    e_run = [v * R % P for r in rows for v in r]; e_tot = [v * R % P for v in totals]; e_sum = total * R % P
+    s = np.frombuffer(pyref.scalars_to_bytes(scalars), np.uint8).reshape(-1, 32).copy()
+    ds, dp = dev(ctx, s), dev(ctx, aff)
+    tab = ctx.multiples_table_device(1, dp.ptr, n, base); KEEP.append(tab)
+    out = ctx.alloc(n * (base - 1) * 32); KEEP.append(out)
+    Araw = np.concatenate([fe(A[0]), fe(A[1])]); traw = fe(t)
+
+    def fn():
+        _, tot, sm = ctx.rhs_witness_device(1, ds.ptr, tab.ptr, n, base, Araw, traw, None, out)
+        return [out.download(np.uint64).reshape(n, base - 1, 4), tot, sm]
+
+    def verify(raw):
+        need(ints(raw[0]) == e_run and ints(raw[1]) == e_tot and ints(raw[2]) == [e_sum], "rhs_witness_device differs from the reference")
+    return Call("rhs_witness_device n=%d base=%d" % (n, base), "rhs_witness_device", fn, verify)
+
+
+def resident_witness_calls(ctx, k):
+    """regfn_eval_device and column_a_device over the context's own resident witnesses (lhs_witness_device, n = 300, base 5)"""
+    n, base = 300, 5
+    sc, aff, jac, ecarry, efns = witness_inputs(n, base, 3400 + 10 * k)
+    ds, dp = dev(ctx, sc), dev(ctx, aff)
+    carry, index, out = ctx.lhs_witness_device(1, ds.ptr, dp.ptr, n, base, True); KEEP.append(out)
+    cap = out.nbytes // 32
+    flat = out.download(np.uint64).reshape(-1, 4)
+    need(cref.jac_to_canonical(1, carry) == ecarry, "resident witnesses: carry differs from the oracle")
+    check_fns([(flat[int(oa): int(oa + la)], flat[int(ob): int(ob + lb)]) for oa, la, ob, lb in index], efns, "resident witnesses:")
+    O = dv.DivisorOracle(GR)
+    rng = pyref.SplitMix64(3450 + k)
+    xy = [(rng.next256() % P, rng.next256() % P) for _ in range(3)]
+    rows = np.stack([np.concatenate([fe(x), fe(y)]) for x, y in xy])
+    e_vals = [O.rf_ev(f, (x, y, 1)) for f in efns for x, y in xy]
+
+    def v_regfn(raw):
+        need(std(raw[0]) == e_vals, "regfn_eval_device differs from the oracle")
+    regfn = Call("regfn_eval_device T=%d K=3" % len(efns), "regfn_eval_device", lambda: [ctx.regfn_eval_device(1, out.ptr, cap, index, rows)], v_regfn)
+    want = column_ref.column_a(efns, 0)
+    e_col = b"".join((v * R % P).to_bytes(32, "little") for b_ in want for v in b_)
+    plan = api.column_plan(index, cap)
+    col = ctx.alloc(max(plan["rows"] * 32, 16)); KEEP.append(col)
+
+    def f_col():
+        _, nb = ctx.column_a_device(1, out.ptr, cap, index, 0, 0, _lib.LEMSM_FORM_MONTGOMERY, col)
+        return [col.download(np.uint8, plan["rows"] * 32), np.array([nb])]
+
+    def v_col(raw):
+        need(int(raw[1][0]) == len(want) and raw[0].tobytes() == e_col, "column_a_device differs from the reference")
+    return [regfn, Call("column_a_device T=%d" % len(efns), "column_a_device", f_col, v_col)]
+
+
+def fixed_call(ctx, k):
+    n = 4097
+    pts = cref.gen_points(0, 3500 + k, n); sc = cref.gen_scalars(0, 3510 + k, n)
+    exp = cref.jac_to_canonical(0, cref.best_multiexp(0, sc, pts, THREADS))
+    bases = ctx.bases_upload(0, pts); fb = ctx.fixed_bases(bases); KEEP.extend([bases, fb])
+    ds = dev(ctx, sc)
+
+    def verify(raw):
+        need(cref.jac_to_canonical(0, raw[0]) == exp, "msm_fixed_device differs from the oracle")
+    return Call("msm_fixed_device n=%d" % n, "msm_fixed_device", lambda: [ctx.msm_fixed_device(fb, ds.ptr, n)], verify, {0: 0})
+
+
+def scenario3():
+    lanes = []
+    for k in range(4):
+        c = new_ctx()
+        regfn, column = resident_witness_calls(c, k)
+        fam = [msm_call(c, 0, 1000, msm_inputs(0, 1000, 3100 + 10 * k)), lhs_call(c, 1, 400, 5, lhs_inputs(1, 400, 5, 3200 + 10 * k)),
+               fixed_call(c, k), rhs_call(c, k), regfn, column]
+        lanes.append(Lane("context %d" % k, fam[k:] + fam[:k], ROUNDS[3][k]))
+    serial_then_concurrent(3, lanes)
+
+
+# ---- scenario 4: shared read-only residents --------------------------------------------------------------------------------------
+def scenario4():
+    a, b = new_ctx(), new_ctx()
+    n = 5000
+    pts = cref.gen_points(1, 4001, n); sc = cref.gen_scalars(1, 4002, n, half=True)
+    ds, dp = dev(a, sc), dev(a, pts)                                   # uploaded once; both contexts read the same pointers
+    jac = cref.aff_to_jac(1, pts)
+    m_in = (sc, pts, cref.jac_to_canonical(1, cref.best_multiexp(1, sc, pts, THREADS)))
+    l_in = {}
+    for base in (16, 5):
+        carry, carries = cref.lhs_msm(1, sc, jac, base)
+        l_in[base] = (sc, pts, (cref.jac_to_canonical(1, carry), canon_points(1, carries)))
+    lanes = []
+    for k, c in enumerate((a, b)):
+        calls = [msm_call(c, 1, n, m_in, ds, dp), lhs_call(c, 1, n, 16, l_in[16], ds, dp), lhs_call(c, 1, n, 5, l_in[5], ds, dp)]
+        lanes.append(Lane("context %d" % k, calls[k:] + calls[:k], ROUNDS[4][k]))
+    serial_then_concurrent(4, lanes)
+    need(np.array_equal(ds.download(np.uint8), sc.reshape(-1)) and np.array_equal(dp.download(np.uint64), pts.reshape(-1)), "the shared inputs were written")
+    b.close(); a.close()
+
+
+# ---- scenario 5: errors stay where they happen ------------------------------------------------------------------------------------
+def state_of(ctx):
+    return (ctx.lib.lemsm_last_error(ctx.h).decode(), int(ctx.lib.lemsm_last_bad_index(ctx.h)), ctx.last_truncated_count())
+
+
+def scenario5():
+    a, b = new_ctx(), new_ctx()
+    a.set_option("host_slab_bits", 12)
+    n = 3 * 4096 + 17; bad_at = 2 * 4096 + 9                           # a non-canonical scalar in the third slab of the host entry
+    pts = np.tile(cref.gen_points(0, 5001, 8), (n // 8 + 1, 1))[:n]
+    sc = cref.gen_scalars(0, 5002, n)
+    good_exp = cref.jac_to_canonical(0, cref.best_multiexp(0, sc, pts, THREADS))
+    bad_sc = sc.copy(); bad_sc[bad_at] = np.frombuffer(int(BN.order).to_bytes(32, "little"), np.uint8)
+    two = cref.gen_points(1, 5003, 2)                                  # two points that do not sum to the identity
+    hs = cref.gen_scalars(1, 5004, 500, half=True)
+    d_short = 20                                                       # fewer digits than a half-size scalar has in base 5: truncation is counted
+    e_digits = cref.negbase_decompose_batch(hs, 5, d_short)
+
+    def status(thunk):
+        try:
+            thunk()
+            return 0
+        except api.LemsmError as e:
+            return e.status
+
+    def good_msm():
+        need(cref.jac_to_canonical(0, a.msm(0, sc, pts)) == good_exp, "A: good msm differs from the oracle")
+
+    def good_digits():
+        need(np.array_equal(a.negbase_decompose_batch(hs, 5, d_short), e_digits), "A: digits differ from the oracle")
+    steps = [("good msm", good_msm, _lib.LEMSM_OK), ("non-canonical scalar", lambda: a.msm(0, bad_sc, pts), _lib.LEMSM_ERR_SCALAR_OUT_OF_RANGE),
+             ("good truncating digits", good_digits, _lib.LEMSM_OK), ("sum not identity", lambda: a.divisor_witness(1, two, True, True), _lib.LEMSM_ERR_SUM_NOT_IDENTITY),
+             ("good msm", good_msm, _lib.LEMSM_OK), ("bad curve", lambda: a.msm(7, sc[:8], pts[:8]), _lib.LEMSM_ERR_BAD_CURVE)]
+    # what each step leaves in A's context when A is alone: two rounds, the second being the steady state of the loop
+    alone = []
+    for rnd in range(2):
+        alone = []
+        for name, thunk, want in steps:
+            st = status(thunk)
+            need(st == want, "alone:", name, "status", st)
+            alone.append(state_of(a))
+    need(alone[1][1] == bad_at, "alone: last_bad_index", alone[1][1])
+    need(alone[2][2] > 0, "alone: the truncating call truncated nothing")
+    need(len({s[0] for s in alone}) >= 3, "alone: the failing calls leave the same message", alone)
+
+    def a_fn(k):
+        def fn():
+            name, thunk, want = steps[k]
+            st = status(thunk)
+            need(st == want, "A:", name, "returned status", st)
+            got = state_of(a)
+            need(got == alone[k], "A: after '%s' the context holds %s, alone it held %s" % (name, got, alone[k]))
+            return []
+        return fn
+    calls_a = [Call("A step %d" % k, "errors", a_fn(k), None) for k in range(len(steps))]
+    calls_b = [msm_call(b, 0, 4097, msm_inputs(0, 4097, 5100)), lhs_call(b, 1, 400, 5, lhs_inputs(1, 400, 5, 5200)),
+               msm_call(b, 0, 300, msm_inputs(0, 300, 5300))]
+    for c in calls_b:
+        def after(raw, r, c=c):
+            c.verify(raw)                                              # every one of B's results against the oracle
+            got = state_of(b)
+            need(got == ("", 0, 0), "B: a context that only made good calls holds", got)
+        c.after = after
+    for c in calls_a:
+        c.ref = False                                                  # (nothing to compare: the step checks itself)
+    lanes = [Lane("A: good and failing calls", calls_a, ROUNDS[5][0]), Lane("B: good calls", calls_b, ROUNDS[5][1])]
+    wall = run_concurrent(lanes)
+    finish(5, lanes, wall)
+    a.close(); b.close()
+
+
+# ---- scenario 6: lifetime calls beside running calls ---------------------------------------------------------------------------------
+def scenario6():
+    a = new_ctx()
+    calls_a = lane_a_calls(a)
+    for c in calls_a:                                                  # (first output against the oracle, as in scenario 1)
+        raw = c.fn(); c.verify(raw); c.ref = raw
+    sc, pts, exp = msm_inputs(0, 300, 6001)
+    box = {}
+
+    def create():
+        box["ctx"] = new_ctx(); return []
+
+    def small():
+        need(cref.jac_to_canonical(0, box["ctx"].msm(0, sc, pts)) == exp, "short-lived context: msm differs from the oracle"); return []
+
+    def destroy():
+        box.pop("ctx").close(); return []
+    calls_l = [Call(nm, "lifetime", f, None) for nm, f in (("lemsm_create", create), ("msm n=300", small), ("lemsm_destroy", destroy))]
+    for c in calls_l:
+        c.ref = False
+    lanes = [Lane("L: create, msm, destroy", calls_l, ROUNDS[6][0]), Lane("A: BN254 G1 msm_device", calls_a, ROUNDS[6][1])]
+    wall = run_concurrent(lanes)
+    finish(6, lanes, wall)
+    a.close()
+
+
+# ---- scenario 7: hand-off ---------------------------------------------------------------------------------------------------------------
+def scenario7():
+    ctx = new_ctx()                                                    # created on the main thread
+    calls = [msm_call(ctx, 0, 4097, msm_inputs(0, 4097, 7001)), divisor_call(ctx, 1025, 7002), lhs_call(ctx, 1, 400, 5, lhs_inputs(1, 400, 5, 7003))]
+    lanes = []
+    t0 = time.perf_counter()
+    for c in calls:                                                    # each call from a thread of its own, one after the other
+        ln = Lane("thread for " + c.name, [c], 1)
+        t = threading.Thread(target=ln.run, args=(None,)); t.start(); t.join()
+        need(ln.error is None, ln.error)
+        lanes.append(ln)
+    closer = Lane("closing thread", [Call("lemsm_destroy", "lifetime", lambda: [ctx.close()][:0], lambda raw: None)], 1)
+    t = threading.Thread(target=closer.run, args=(None,)); t.start(); t.join()
+    need(closer.error is None, closer.error)
+    need(ctx.h is None, "the context was not closed")
+    finish(7, lanes + [closer], time.perf_counter() - t0, need_overlap=False)
+
+
+# rounds of each thread's list (chosen so that the threads of a scenario run about equally long: profiles/concurrency/NOTES.md)
+ROUNDS = {1: (40, 3), 2: (25, 25), 3: (10, 10, 10, 10), 4: (25, 25), 5: (12, 60), 6: (10, 30)}
+SCENARIOS = {1: scenario1, 2: scenario2, 3: scenario3, 4: scenario4, 5: scenario5, 6: scenario6, 7: scenario7}
+
+if __name__ == "__main__":
+    which = int(sys.argv[2])
+    _lib.load(); cref.lib()                                            # both libraries are loaded before any thread exists
+    try:
+        SCENARIOS[which]()
+    except Failure as e:
+        sys.stderr.write("FAILED scenario %d: %s\n" % (which, e))
+        sys.exit(1)

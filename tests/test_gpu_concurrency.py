@@ -1,0 +1,108 @@
+"""The per-context threading contract of the C ABI (include/lemsm.h, "Threading") on one GPU: any host thread may call, a
+context serves one call at a time, distinct contexts may be used concurrently -- several of them on device 0, more of them
+than the process has hardware queues -- and device pointers may be read by several contexts at once.
+
+Each scenario runs in a fresh child interpreter (tests/concurrency_child.py, which documents how a scenario is run and what
+it compares): contexts on device 0, every expected value from the oracle before a thread starts, threading.Thread workers
+that leave one barrier together, ws_canary = 1 on every context, exit status non-zero with a message on the first mismatch.
+A scenario whose threads' calls never overlapped fails as vacuous.  If a child is killed by the time limit, dies on a signal
+or prints a HIP fault, every later scenario of the module fails at once without starting a child."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD = os.path.join(ROOT, "tests", "concurrency_child.py")
+LIMIT_S = 180
+FAULT_TEXT = ("illegal memory access", "Memory access fault", "HSA_STATUS_ERROR", "hipErrorLaunchFailure", "hipErrorIllegalAddress",
+              "unspecified launch failure", "GPU core dump", "Aborted", "Segmentation fault")
+_gpu_trouble = []          # why no further child is started
+
+
+def _run(scenario):
+    """the RESULT record of one scenario"""
+    assert not _gpu_trouble, "not started: an earlier scenario of this module ended in GPU trouble (%s)" % _gpu_trouble[0]
+    try:
+        r = subprocess.run([sys.executable, CHILD, ROOT, str(scenario)], capture_output=True, text=True, timeout=LIMIT_S)
+    except subprocess.TimeoutExpired as e:
+        _gpu_trouble.append("scenario %d was killed by the %d s limit" % (scenario, LIMIT_S))
+        pytest.fail(_gpu_trouble[0] + "\n" + str(e.stdout)[-3000:] + str(e.stderr)[-3000:])
+    text = r.stdout + r.stderr
+    if r.returncode < 0:
+        _gpu_trouble.append("scenario %d died on signal %d" % (scenario, -r.returncode))
+    elif any(t in text for t in FAULT_TEXT):
+        _gpu_trouble.append("scenario %d printed a HIP fault" % scenario)
+    assert not _gpu_trouble, _gpu_trouble[0] + "\n" + text[-6000:]
+    assert r.returncode == 0, text[-6000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+    assert len(lines) == 1, text[-6000:]
+    res = json.loads(lines[0][len("RESULT "):])
+    assert res["scenario"] == scenario
+    print(lines[0])
+    return res
+
+
+def _overlapped(res):
+    assert all(k > 0 for k in res["overlapped"]) and all(c >= 20 for c in res["calls"]), res
+
+
+def test_1_different_families_side_by_side():
+    """thread A: BN254 G1 msm_device at n = 1, 300, 4097, 2^14, 2^16 on resident inputs; thread B: Grumpkin lhs_witness (base 16
+    and 5, n = 7, 300, 1000) and divisor_witness (n = 33, 1025); canonical bytes / normalised coefficients against the oracle,
+    raw limbs against the same lists made serially"""
+    res = _run(1)
+    assert res["threads"] == 2 and res["serial_s"] is not None
+    _overlapped(res)
+
+
+def test_2_same_family_under_different_options():
+    """two contexts, the same MSM and lhs inputs: one with field = 1 and window_bits = 13, the other with abi_points = 2,
+    entry_ring = 1, chunk = 8, merge_slice = 33; both match the oracle and every call leaves the merge counts of its own
+    context's geometry (those of the same call made alone)"""
+    res = _run(2)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_3_more_contexts_than_hardware_queues():
+    """four contexts on four threads, each running a different cyclic shift of MSM, lhs MSM, fixed-base MSM over its own
+    table, rhs_witness, regfn_eval and column_a over its own resident witnesses"""
+    res = _run(3)
+    assert res["threads"] == 4
+    _overlapped(res)
+
+
+def test_4_shared_read_only_residents():
+    """one resident point set and scalar vector, two contexts running msm_device and lhs_msm_device on the same pointers"""
+    res = _run(4)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_5_errors_stay_where_they_happen():
+    """thread A alternates good calls with a non-canonical scalar in a later slab, a list that does not sum to the identity
+    and a bad curve: its status, last_error, last_bad_index and last_truncated_count are its own call's after every call;
+    thread B, good calls only, never sees a status, a message or an index"""
+    res = _run(5)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_6_lifetime_calls_beside_running_calls():
+    """one thread creates a context, runs a small MSM against the oracle and destroys the context, 10 times, while another
+    runs scenario 1's MSM loop on a long-lived context"""
+    res = _run(6)
+    assert res["threads"] == 2 and res["rounds"][0] == 10
+    _overlapped(res)
+
+
+def test_7_hand_off_between_threads():
+    """a context created on the main thread; MSM, divisor witness and lhs each from a freshly started thread, one after the
+    other; closed from yet another thread"""
+    res = _run(7)
+    assert res["threads"] == 4 and res["calls"] == [1, 1, 1, 1]

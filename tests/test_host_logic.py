@@ -190,6 +190,20 @@ def test_host_tail_under_asan_ubsan(tmp_path):
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
+def test_host_pool_per_thread_under_tsan(tmp_path):
+    """the worker pool (csrc/hostpool.hpp) used as contexts use it -- one pool per host thread, several threads at once,
+    job counts 0, 1 and more than the workers, the per-window fold of csrc/hosttail.hpp through two such pools -- compiled
+    alone with -fsanitize=thread (tests/hostpool_race_check.cpp): every index once, the jobs' plain writes visible after
+    run(), the parallel fold equal to the serial one, and no report from ThreadSanitizer"""
+    import subprocess
+    exe = tmp_path / "hostpool_race_check"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", "-o", str(exe),
+                           os.path.join(ROOT, "tests", "hostpool_race_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "hostpool race check ok" in out.stdout, out.stdout + out.stderr
+    assert "ThreadSanitizer" not in out.stderr, out.stderr
+
+
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_arena_helper_on_a_host_buffer(tmp_path, sanitize):
     """the workspace carving helper (csrc/arena.hpp) alone on a host buffer (tests/arena_check.cpp): guard-off offsets equal
