@@ -1,7 +1,7 @@
 // Advice column a from the resident divisor witnesses and the cells of the "polynomials random linear combination" gate
 // (include/lemsm.h: lemsm_column_plan, lemsm_column_a*, lemsm_poly_rlc*, lemsm_column_last; src/layout.md:7,
-// src/config.rs:39-48, :246-283).  Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, HIPCHK, fail, Arena,
-// arena_fill, arena_done); the kernels are column.cuh's.
+// src/config.rs:39-48, :246-283).  Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, timed_run, LastStats /
+// last_stats, index_rows_ok, HIPCHK, fail); the kernels are column.cuh's.
 
 namespace {
 
@@ -38,12 +38,9 @@ int col_plan(const size_t* index, size_t T, size_t cap_coeffs, size_t batch_offs
   p.T = T; p.bs = T + batch_offset;
   size_t need = 0;
   if (index) {
+    if (!index_rows_ok(index, T, cap_coeffs)) return LEMSM_ERR_BAD_ARG;
     for (size_t t = 0; t < T; t++) {
       const size_t* ix = index + 4 * t;
-      for (int h = 0; h < 2; h++) {
-        const size_t end = ix[2 * h] + ix[2 * h + 1];
-        if (end < ix[2 * h] || end > cap_coeffs) return LEMSM_ERR_BAD_ARG;   // past the buffer, or offset + length wraps
-      }
       if (ix[1] > (size_t)-1 / 4 || ix[3] > (size_t)-1 / 4) return LEMSM_ERR_BAD_ARG;
       need = std::max(need, col_batches_of(ix[1], ix[3]));
       p.coeffs += ix[1] + ix[3];
@@ -85,22 +82,18 @@ int col_assemble(lemsm_ctx* ctx, const void* d_coeffs, const size_t* index, cons
   hipStream_t st = ctx->stream;
   Arena ar("column_ws", ctx->opt.ws_canary != 0);
   const size_t o_fns = ar.take("functions", std::max<size_t>(pl.T, 1) * sizeof(cl::Fn));
-  int rc = reserve(ctx, ctx->col_ws, ar.total()); if (rc) return rc;
-  char* w = (char*)ctx->col_ws.p;
-  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
-  if (pl.T) HIPCHK(ctx, hipMemcpyAsync(w + o_fns, fns.data(), pl.T * sizeof(cl::Fn), hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
+  Workspace ws;   // (behind fns: the stream has read it when it goes)
+  int rc = ws.open(ctx, std::move(ar), ctx->col_ws, ar.total(), st); if (rc) return rc;
+  cl::Fn* d_fns = ws.at<cl::Fn>(o_fns);
+  if (pl.T) HIPCHK(ctx, hipMemcpyAsync(d_fns, fns.data(), pl.T * sizeof(cl::Fn), hipMemcpyHostToDevice, st));
   const dim3 grid((u32)(ntile * nch)), blk(256);
-  if (form == LEMSM_FORM_CANONICAL)
-    hipLaunchKernelGGL((cl::k_column_a<true>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)(w + o_fns), (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
-  else
-    hipLaunchKernelGGL((cl::k_column_a<false>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)(w + o_fns), (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-  HIPCHK(ctx, hipStreamSynchronize(st));   // (fns stays valid until here)
-  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->col_ms = ms;
-  return arena_done(ctx, ar, w, st, LEMSM_OK);
+  rc = timed_run(ctx, st, ctx->col_last, [&] {
+    if (form == LEMSM_FORM_CANONICAL)
+      hipLaunchKernelGGL((cl::k_column_a<true>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)d_fns, (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
+    else
+      hipLaunchKernelGGL((cl::k_column_a<false>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)d_fns, (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
+  }, [] { return LEMSM_OK; });
+  return ws.done(rc);
 }
 
 // r^e by squaring (raw Montgomery limbs)
@@ -130,22 +123,18 @@ int col_rlc(lemsm_ctx* ctx, const void* d_column, int form, const ColPlan& pl, s
   hipStream_t st = ctx->stream;
   Arena ar("column_ws", ctx->opt.ws_canary != 0);
   const size_t o_pw = ar.take("powers", ni * 32), o_rho = ar.take("rho_powers", (size_t)cl::RLC_RHO * 32);
-  int rc = reserve(ctx, ctx->col_ws, ar.total()); if (rc) return rc;
-  char* w = (char*)ctx->col_ws.p;
-  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(w + o_pw, tab.data(), ni * 32, hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipMemcpyAsync(w + o_rho, tab.data() + ni, (size_t)cl::RLC_RHO * 32, hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-  if (staged)
-    hipLaunchKernelGGL((cl::k_poly_rlc<true>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)(w + o_pw), (const uint4*)(w + o_rho), (uint4*)d_cells);
-  else
-    hipLaunchKernelGGL((cl::k_poly_rlc<false>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)(w + o_pw), (const uint4*)(w + o_rho), (uint4*)d_cells);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-  HIPCHK(ctx, hipStreamSynchronize(st));   // (tab stays valid until here)
-  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->col_ms = ms;
-  return arena_done(ctx, ar, w, st, LEMSM_OK);
+  Workspace ws;   // (behind tab: the stream has read it when it goes)
+  int rc = ws.open(ctx, std::move(ar), ctx->col_ws, ar.total(), st); if (rc) return rc;
+  uint4* d_pw = ws.at<uint4>(o_pw); uint4* d_rho = ws.at<uint4>(o_rho);
+  HIPCHK(ctx, hipMemcpyAsync(d_pw, tab.data(), ni * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(ctx, hipMemcpyAsync(d_rho, tab.data() + ni, (size_t)cl::RLC_RHO * 32, hipMemcpyHostToDevice, st));
+  rc = timed_run(ctx, st, ctx->col_last, [&] {
+    if (staged)
+      hipLaunchKernelGGL((cl::k_poly_rlc<true>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)d_pw, (const uint4*)d_rho, (uint4*)d_cells);
+    else
+      hipLaunchKernelGGL((cl::k_poly_rlc<false>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)d_pw, (const uint4*)d_rho, (uint4*)d_cells);
+  }, [] { return LEMSM_OK; });
+  return ws.done(rc);
 }
 
 const char* col_plan_msg(const char* who, std::string& keep) {
@@ -184,7 +173,7 @@ int lemsm_column_a_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, size_
   rc = col_plan(index, T, cap_coeffs, batch_offset, 1, num_batches, pl);
   if (rc) return fail(ctx, rc, col_plan_msg("column a", keep));
   if (out_num_batches) *out_num_batches = pl.nb;
-  ctx->col_ms = 0; ctx->col_bytes = pl.coeff_bytes + pl.column_bytes; ctx->col_mults = form == LEMSM_FORM_CANONICAL ? pl.coeffs : 0;
+  ctx->col_last = LastStats{0, pl.coeff_bytes + pl.column_bytes, form == LEMSM_FORM_CANONICAL ? (u64)pl.coeffs : 0};
   if (pl.rows > cap_rows) return fail(ctx, LEMSM_ERR_BAD_ARG, "column a: capacity " + std::to_string(cap_rows) + " rows, the column has " + std::to_string(pl.rows));
   if (pl.rows == 0) return LEMSM_OK;
   if (!d_out_column || (pl.coeffs && !d_coeffs)) return LEMSM_ERR_BAD_ARG;
@@ -207,15 +196,15 @@ int lemsm_column_a(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Arena ar("column_staged", ctx->opt.ws_canary != 0);
   const size_t o_co = ar.take("coefficients", std::max<size_t>(cap_coeffs, 1) * 32), o_out = ar.take("column", pl.rows * 32);
-  rc = reserve(ctx, ctx->col_stage, ar.total()); if (rc) return rc;
-  char* b = (char*)ctx->col_stage.p;
-  rc = arena_fill(ctx, ar, b, ctx->stream); if (rc) return rc;
+  Workspace ws;
+  rc = ws.open(ctx, std::move(ar), ctx->col_stage, ar.total(), ctx->stream); if (rc) return rc;
+  char* b = ws.base;
   if (cap_coeffs) HIPCHK(ctx, hipMemcpyAsync(b + o_co, coeffs, cap_coeffs * 32, hipMemcpyHostToDevice, ctx->stream));
   rc = lemsm_column_a_device(ctx, curve, b + o_co, cap_coeffs, index, T, batch_offset, num_batches, form, b + o_out, pl.rows, out_num_batches);
-  if (rc) return arena_done(ctx, ar, b, ctx->stream, rc);
+  if (rc) return ws.done(rc);
   HIPCHK(ctx, hipMemcpyAsync(out_column, b + o_out, pl.rows * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return arena_done(ctx, ar, b, ctx->stream, LEMSM_OK);
+  return ws.done(LEMSM_OK);
 }
 
 int lemsm_poly_rlc_device(lemsm_ctx* ctx, int curve, const void* d_column, int form, size_t T, size_t batch_offset, size_t poly_fan_in,
@@ -227,7 +216,7 @@ int lemsm_poly_rlc_device(lemsm_ctx* ctx, int curve, const void* d_column, int f
   if (rc) return fail(ctx, rc, col_plan_msg("poly rlc", keep));
   if (!r) return LEMSM_ERR_BAD_ARG;
   if (!col_canonical(r)) return fail(ctx, LEMSM_ERR_BAD_ARG, "poly rlc: r is not a canonical field element");
-  ctx->col_ms = 0; ctx->col_bytes = pl.column_bytes + 32 * (u64)pl.cells; ctx->col_mults = pl.rlc_mults;
+  ctx->col_last = LastStats{0, pl.column_bytes + 32 * (u64)pl.cells, pl.rlc_mults};
   if (pl.cells > cap_cells) return fail(ctx, LEMSM_ERR_BAD_ARG, "poly rlc: capacity " + std::to_string(cap_cells) + " cells, the call writes " + std::to_string(pl.cells));
   if (pl.cells == 0) return LEMSM_OK;
   if (!d_column || !d_out_cells) return LEMSM_ERR_BAD_ARG;
@@ -248,23 +237,17 @@ int lemsm_poly_rlc(lemsm_ctx* ctx, int curve, const uint64_t* column, int form, 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Arena ar("column_staged", ctx->opt.ws_canary != 0);
   const size_t o_col = ar.take("column", pl.rows * 32), o_out = ar.take("cells", pl.cells * 32);
-  rc = reserve(ctx, ctx->col_stage, ar.total()); if (rc) return rc;
-  char* b = (char*)ctx->col_stage.p;
-  rc = arena_fill(ctx, ar, b, ctx->stream); if (rc) return rc;
+  Workspace ws;
+  rc = ws.open(ctx, std::move(ar), ctx->col_stage, ar.total(), ctx->stream); if (rc) return rc;
+  char* b = ws.base;
   HIPCHK(ctx, hipMemcpyAsync(b + o_col, column, pl.rows * 32, hipMemcpyHostToDevice, ctx->stream));
   rc = lemsm_poly_rlc_device(ctx, curve, b + o_col, form, T, batch_offset, poly_fan_in, num_batches, r, b + o_out, pl.cells);
-  if (rc) return arena_done(ctx, ar, b, ctx->stream, rc);
+  if (rc) return ws.done(rc);
   HIPCHK(ctx, hipMemcpyAsync(out_cells, b + o_out, pl.cells * 32, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return arena_done(ctx, ar, b, ctx->stream, LEMSM_OK);
+  return ws.done(LEMSM_OK);
 }
 
-int lemsm_column_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) {
-  if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (ms) *ms = ctx->col_ms;
-  if (bytes) *bytes = ctx->col_bytes;
-  if (field_mults) *field_mults = ctx->col_mults;
-  return LEMSM_OK;
-}
+int lemsm_column_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::col_last, ms, bytes, field_mults); }
 
 }  // extern "C"

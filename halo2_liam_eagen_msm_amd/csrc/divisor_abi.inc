@@ -1,5 +1,6 @@
 // Host side of the GPU divisor witness (divisor.cuh): level loop, workspace, twiddle / coset tables, C ABI.
-// Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, HIPCHK, fail, align_up).
+// Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, stage, HIPCHK, fail; the guard self-test alone
+// calls reserve, arena_fill and arena_check by hand).
 
 namespace {
 
@@ -52,14 +53,13 @@ int dw_ensure_tables(lemsm_ctx* ctx, u32 logn, u32 gexp) {
   Arena ar("dw_tab", ctx->opt.ws_canary != 0);
   const size_t oW = ar.take("W", nmax / 2 * 32), oGP = ar.take("GP", nmax * 32), oGI = ar.take("GI", nmax * 32);
   const size_t oP2 = ar.take("powers", 96 * 32, 1024), oW32 = ar.take("W32", nmax / 2 * 32, 1024);
-  int rc = reserve(ctx, ctx->dw_tab, ar.end()); if (rc) return rc;
-  char* base = (char*)ctx->dw_tab.p;
-  ctx->dw_tab_off[0] = oW; ctx->dw_tab_off[1] = oGP; ctx->dw_tab_off[2] = oGI; ctx->dw_tab_off[3] = oW32;
-  ctx->dw_logn = 0;   // (the old tables are gone whatever happens below)
-  rc = arena_fill(ctx, ar, base, st); if (rc) return rc;
-  u32* W = (u32*)(base + oW); u32* GP = (u32*)(base + oGP); u32* GI = (u32*)(base + oGI);
-  u32* P2 = (u32*)(base + oP2);
   std::vector<host::fe> p2(3 * 32);
+  ctx->dw_logn = 0;   // (the old tables are gone whatever happens below)
+  Workspace ws;
+  int rc = ws.open(ctx, std::move(ar), ctx->dw_tab, ar.end(), st); if (rc) return rc;
+  ctx->dw_tab_off[0] = oW; ctx->dw_tab_off[1] = oGP; ctx->dw_tab_off[2] = oGI; ctx->dw_tab_off[3] = oW32;
+  u32* W = ws.at<u32>(oW); u32* GP = ws.at<u32>(oGP); u32* GI = ws.at<u32>(oGI);
+  u32* P2 = ws.at<u32>(oP2);
   host::fe w = fr_root_of_unity_2_28();
   for (u32 k = 28; k > logn; k--) w = HFr::sqr(w);               // omega_{2^logn}
   host::fe g = fr_from_u64(7), gp = g;
@@ -72,12 +72,12 @@ int dw_ensure_tables(lemsm_ctx* ctx, u32 logn, u32 gexp) {
   HIPCHK(ctx, hipMemcpyAsync(P2, p2.data(), p2.size() * 32, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)P2, logn - 1, (u32)(nmax / 2), W);
-  hipLaunchKernelGGL(lemsm::dw::k_times32, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)W, (u32)(nmax / 2), (u32*)(base + oW32));
+  hipLaunchKernelGGL(lemsm::dw::k_times32, dim3((u32)((nmax / 2 + 255) / 256)), dim3(256), 0, st, (const u32*)W, (u32)(nmax / 2), ws.at<u32>(oW32));
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax + 255) / 256)), dim3(256), 0, st, (const u32*)(P2 + 32 * 8), logn, (u32)nmax, GP);
   hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((u32)((nmax + 255) / 256)), dim3(256), 0, st, (const u32*)(P2 + 64 * 8), logn, (u32)nmax, GI);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = arena_check(ctx, ar, base, st); if (rc) return rc;   // (the tables are only read from here on)
+  rc = ws.check(); if (rc) return rc;   // (the tables are only read from here on)
   ctx->dw_logn = logn; ctx->dw_gexp = gexp;
   return LEMSM_OK;
 }
@@ -166,10 +166,8 @@ struct DwForest {
   const uint2* d_lens = nullptr; u32* dA = nullptr; u32* dB = nullptr; u32* d_scratch = nullptr;
   u32 reuse_levels = 0;                                   // levels whose forward transforms covered the odd half of the domain only (child-evaluation reuse)
   double ntt_ms = 0; u64 ntt_bytes = 0, ntt_bflies = 0;   // device time, algorithmic bytes (one read + one write of every element per pass) and butterflies of the transforms
-  Arena arena; char* base = nullptr;                      // the carve of ctx->dw_arena (option ws_canary: its guard zones)
+  Workspace ws;                                           // the carve of ctx->dw_arena; ws.done(rc): the status of a return behind the forest's kernels
 };
-// the status of a return behind the forest's kernels: its guard zones first (option ws_canary)
-int dw_forest_done(lemsm_ctx* ctx, const DwForest& fo, int rc) { return fo.base ? arena_done(ctx, fo.arena, fo.base, ctx->stream, rc) : rc; }
 
 // compute_divisor_witness_partial (:453-467) of T point lists at once: list t = counts[t] affine points, concatenated at
 // d_pts.  One forest costs the launches of one tree (levels = those of the longest list).  Results stay in the arena.
@@ -177,7 +175,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
   using namespace lemsm::dw;
   const u32 T = (u32)counts.size();
   hipStream_t st = ctx->stream;
-  fo = DwForest(); fo.trees.resize(T);
+  fo.trees.resize(T);   // (fo: fresh from its constructor)
   if (T == 0) return LEMSM_OK;
   size_t total = 0, longest = 0;
   for (size_t c : counts) { total += c; longest = std::max(longest, c); }
@@ -208,7 +206,7 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
   }
   // The carve.  take(name, bytes, slack): `bytes` is what the kernels touch; `slack` is room the request has always
   // carried and no kernel reads (with option ws_canary a guard zone takes its place, directly behind the bytes).
-  Arena& ar = fo.arena; ar = Arena("dw_arena", ctx->opt.ws_canary != 0);
+  Arena ar("dw_arena", ctx->opt.ws_canary != 0);
   auto take = [&](const char* name, size_t b, size_t slack = 0) { return ar.take(name, b, slack); };
   const size_t oA0 = take("coefA0", coef_bytes), oB0 = take("coefB0", coef_bytes), oA1 = take("coefA1", coef_bytes), oB1 = take("coefB1", coef_bytes);
   const size_t oL0 = take("lens0", node_max * 8), oL1 = take("lens1", node_max * 8);
@@ -234,20 +232,18 @@ int dw_run_forest(lemsm_ctx* ctx, const void* d_pts, const std::vector<size_t>& 
   const size_t oC0i = take("c0in", node_max * 4 * 32), oC0o = take("c0out", node_max * 2 * 32);   // wrap mode: constant terms of the children, of the results
   const size_t root_bytes = (fbuf_bytes / 128 / DW_KB_MIN + node_max) * 32;     // one root per thread of k_pw_prefix: at most elements / DW_KB_MIN + one per node
   const size_t oRt = take("pw_roots", root_bytes, 256 * 32), oRp = take("pw_rpre", root_bytes, 256 * 32);
-  int rc = reserve(ctx, ctx->dw_arena, ar.total() + 4096); if (rc) return rc;   // (+ 4096: slack behind the whole arena)
-  char* base = (char*)ctx->dw_arena.p;
-  fo.base = base;
-  rc = arena_fill(ctx, ar, base, st); if (rc) return rc;
-  auto done = [&](int status) { return dw_forest_done(ctx, fo, status); };   // returns behind a synchronised launch
-  u32* cA[2] = {(u32*)(base + oA0), (u32*)(base + oA1)}; u32* cB[2] = {(u32*)(base + oB0), (u32*)(base + oB1)};
-  uint2* lens[2] = {(uint2*)(base + oL0), (uint2*)(base + oL1)};
-  char* xyzz[2] = {base + oX0, base + oX1}; Plan* plan = (Plan*)(base + oP);
-  u32* d_off = (u32*)(base + oOff);
-  u32* fb2[2] = {(u32*)(base + oFb), (u32*)(base + oFb2)};
-  u32* finv = (u32*)(base + oFinv); u32* fodd = (u32*)(base + oFodd); u32* feven = (u32*)(base + oFev); u32* go = (u32*)(base + oGo); u32* d_exc = (u32*)(base + oExc);
-  Plan* plan2[2] = {plan, (Plan*)(base + oP2)};
-  u32* stats = (u32*)(base + oSt); u32* consts = (u32*)(base + oC); u32* xs = (u32*)(base + oXS);
-  u32* c0in = (u32*)(base + oC0i); u32* c0out = (u32*)(base + oC0o); u32* pw_roots = (u32*)(base + oRt); u32* pw_rpre = (u32*)(base + oRp);
+  Workspace& ws = fo.ws;
+  int rc = ws.open(ctx, std::move(ar), ctx->dw_arena, ar.total() + 4096, st); if (rc) return rc;   // (+ 4096: slack behind the whole arena)
+  auto done = [&](int status) { return ws.done(status); };   // returns behind a synchronised launch
+  u32* cA[2] = {ws.at<u32>(oA0), ws.at<u32>(oA1)}; u32* cB[2] = {ws.at<u32>(oB0), ws.at<u32>(oB1)};
+  uint2* lens[2] = {ws.at<uint2>(oL0), ws.at<uint2>(oL1)};
+  char* xyzz[2] = {ws.at<char>(oX0), ws.at<char>(oX1)}; Plan* plan = ws.at<Plan>(oP);
+  u32* d_off = ws.at<u32>(oOff);
+  u32* fb2[2] = {ws.at<u32>(oFb), ws.at<u32>(oFb2)};
+  u32* finv = ws.at<u32>(oFinv); u32* fodd = ws.at<u32>(oFodd); u32* feven = ws.at<u32>(oFev); u32* go = ws.at<u32>(oGo); u32* d_exc = ws.at<u32>(oExc);
+  Plan* plan2[2] = {plan, ws.at<Plan>(oP2)};
+  u32* stats = ws.at<u32>(oSt); u32* consts = ws.at<u32>(oC); u32* xs = ws.at<u32>(oXS);
+  u32* c0in = ws.at<u32>(oC0i); u32* c0out = ws.at<u32>(oC0o); u32* pw_roots = ws.at<u32>(oRt); u32* pw_rpre = ws.at<u32>(oRp);
   fo.d_scratch = consts + 64;   // T x 32 bytes behind the level constants
   {
     std::vector<u32> flat; flat.reserve(off.size() * (T + 1));
@@ -528,10 +524,10 @@ int lemsm_divisor_witness_device(lemsm_ctx* ctx, int curve, const void* d_points
   if (out_point_affine) memcpy(out_point_affine, res.out_aff, 64);
   if (require_zero_sum) {
     u64 o = 0; for (int i = 0; i < 8; i++) o |= res.out_aff[i];
-    if (o) return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)"));
+    if (o) return fo.ws.done(fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)"));
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
-  return dw_forest_done(ctx, fo, dw_output(ctx, res, out_a, cap_a, len_a, out_b, cap_b, len_b));
+  return fo.ws.done(dw_output(ctx, res, out_a, cap_a, len_a, out_b, cap_b, len_b));
 }
 
 int lemsm_divisor_witness(lemsm_ctx* ctx, int curve, const uint64_t* points_affine, size_t n, int require_zero_sum, int normalise,
@@ -566,7 +562,7 @@ int lemsm_divisor_witness_batch(lemsm_ctx* ctx, int curve, const uint64_t* point
     if (out_points_affine) memcpy(out_points_affine + 8 * t, fo.trees[t].out_aff, 64);
     if (require_zero_sum) {
       u64 o = 0; for (int i = 0; i < 8; i++) o |= fo.trees[t].out_aff[i];
-      if (o) { ctx->bad_index = t; return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: a list does not sum to the identity (panic at src/regular_functions_utils.rs:478)")); }
+      if (o) { ctx->bad_index = t; return fo.ws.done(fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: a list does not sum to the identity (panic at src/regular_functions_utils.rs:478)")); }
     }
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
@@ -581,7 +577,7 @@ int lemsm_divisor_witness_batch(lemsm_ctx* ctx, int curve, const uint64_t* point
   }
   if (used > cap_coeffs) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness batch: coefficient capacity too small"));
+    return fo.ws.done(fail(ctx, LEMSM_ERR_BAD_ARG, "divisor witness batch: coefficient capacity too small"));
   }
   for (size_t t = 0; t < T; t++) {
     const DwResult& res = fo.trees[t];
@@ -590,7 +586,7 @@ int lemsm_divisor_witness_batch(lemsm_ctx* ctx, int curve, const uint64_t* point
     if (res.lb) HIPCHK(ctx, hipMemcpyAsync(out_coeffs + 4 * ix[2], res.B, (size_t)res.lb * 32, hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return dw_forest_done(ctx, fo, LEMSM_OK);
+  return fo.ws.done(LEMSM_OK);
 }
 
 int lemsm_debug_divisor_last_reuse_levels(const lemsm_ctx* ctx, uint32_t* levels) {
@@ -616,9 +612,10 @@ int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t ns
   const size_t cnt = nseq << logn, bytes = cnt * 32;
   Arena ar("debug_ntt", ctx->opt.ws_canary != 0);
   const size_t o_a = ar.take("a", bytes), o_b = ar.take("b", bytes);
-  rc = reserve(ctx, ctx->ws, std::max(ar.total(), 2 * bytes + 512)); if (rc) return rc;   // (guards off: 2 bytes + 512, the larger)
-  rc = arena_fill(ctx, ar, ctx->ws.p, ctx->stream); if (rc) return rc;
-  u32* a = (u32*)((char*)ctx->ws.p + o_a); u32* b = (u32*)((char*)ctx->ws.p + o_b);
+  host::fe acc = HFr::one();   // (the inverse's 1/N: uploaded below)
+  Workspace ws;
+  rc = ws.open(ctx, std::move(ar), ctx->ws, std::max(ar.total(), 2 * bytes + 512), ctx->stream); if (rc) return rc;   // (guards off: 2 bytes + 512, the larger)
+  u32* a = ws.at<u32>(o_a); u32* b = ws.at<u32>(o_b);
   HIPCHK(ctx, hipMemcpyAsync(a, in, bytes, hipMemcpyHostToDevice, ctx->stream));
   const dim3 grid((u32)((cnt + 255) / 256)), blk(256);
   u32* resbuf;
@@ -629,7 +626,7 @@ int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t ns
   } else {          // DIT: bit-reversed in, natural out, then 1/N
     hipLaunchKernelGGL(lemsm::dw::k_bitrev_copy, grid, blk, 0, ctx->stream, (const u32*)a, b, (u32)nseq, logn);
     dw_ntt(ctx, b, (u32)nseq, logn, true);
-    host::fe two = fr_from_u64(2), h = HFr::inv(two), acc = HFr::one();
+    host::fe two = fr_from_u64(2), h = HFr::inv(two);
     for (u32 i = 0; i < logn; i++) acc = HFr::mul(acc, h);
     HIPCHK(ctx, hipMemcpyAsync(a, &acc, 32, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -639,7 +636,7 @@ int lemsm_debug_ntt(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t ns
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(out, resbuf, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return arena_done(ctx, ar, ctx->ws.p, ctx->stream, LEMSM_OK);
+  return ws.done(LEMSM_OK);
 }
 
 // Proof that a damaged guard zone is reported, with no kernel overrunning anything: a three-block arena with guards in the
@@ -691,35 +688,32 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   // (slack no kernel reads: 16 bytes behind the copy and the table, 256 behind the scratch and behind the arena)
   const bool guard = ctx->opt.ws_canary != 0;
   Arena ar_ws("lhs_ws", guard), ar_tmp("lhs_tmp", guard), ar_lists("lhs_lists", guard);
+  std::vector<u32> nnz(d, 0);
+  Workspace ws, tmp, lists;   // (behind negc, nnz: the stream has read and written them when these go)
   const size_t o_jac = ar_ws.take("jacobian", n * 96, 16), o_tab = ar_ws.take("table", nm * 64, 16);
   const size_t o_scr = ar_ws.take("scratch", nm * 160, 256);                         // k_precompute_mult_affine: 160 B per multiple
-  rc = reserve(ctx, ctx->ws, ar_ws.end() + 256); if (rc) return rc;
-  char* wb = (char*)ctx->ws.p;
-  rc = arena_fill(ctx, ar_ws, wb, st); if (rc) return rc;
-  const uint4* table = (const uint4*)(wb + o_tab);
+  rc = ws.open(ctx, std::move(ar_ws), ctx->ws, ar_ws.end() + 256, st); if (rc) return rc;
+  uint4* d_jac = ws.at<uint4>(o_jac); uint4* d_tab = ws.at<uint4>(o_tab);
+  const uint4* table = d_tab;
   if (n) {
-    if (on_device) hipLaunchKernelGGL(lemsm::dw::k_aff_to_jac, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, (uint4*)(wb + o_jac));
-    else HIPCHK(ctx, hipMemcpyAsync(wb + o_jac, points, n * 96, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)(wb + o_jac), (u32)n, (u32)base,
-                       (uint4*)(wb + o_tab), wb + o_scr);
+    if (on_device) hipLaunchKernelGGL(lemsm::dw::k_aff_to_jac, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, d_jac);
+    else HIPCHK(ctx, hipMemcpyAsync(d_jac, points, n * 96, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)d_jac, (u32)n, (u32)base,
+                       d_tab, ws.at<char>(o_scr));
     HIPCHK(ctx, hipGetLastError());
   }
   // all d point lists of :110-127 side by side (one forest): counts first, then flags -> scan -> gather per position
   size_t scan_tmp = 0;
   { hipError_t e = rocprim::exclusive_scan(nullptr, scan_tmp, (u32*)nullptr, (u32*)nullptr, 0u, std::max<size_t>(n, 1), rocprim::plus<u32>(), st);
     if (e != hipSuccess) return fail(ctx, LEMSM_ERR_HIP, "rocprim::exclusive_scan size query failed"); }
-  std::vector<u32> nnz(d, 0);
   // (slack: one word behind the n flags and the n offsets, 1024 bytes behind the arena)
   const size_t o_flags = ar_tmp.take("flags", n * 4, 4), o_offs = ar_tmp.take("offsets", n * 4, 4), o_scan = ar_tmp.take("scan", scan_tmp);
   const size_t o_negc = ar_tmp.take("negcarry", (size_t)d * 64), o_nnz = ar_tmp.take("counts", (size_t)d * 4);
-  rc = reserve(ctx, ctx->dw_tmp, ar_tmp.total() + 1024); if (rc) return rc;
-  char* tb = (char*)ctx->dw_tmp.p;
-  rc = arena_fill(ctx, ar_tmp, tb, st); if (rc) return rc;
-  u32* d_flags = (u32*)(tb + o_flags);
-  u32* d_offs = (u32*)(tb + o_offs);
-  void* d_scan = tb + o_scan;
-  uint4* d_negc = (uint4*)(tb + o_negc);
-  u32* d_nnz = (u32*)(tb + o_nnz);
+  rc = tmp.open(ctx, std::move(ar_tmp), ctx->dw_tmp, ar_tmp.total() + 1024, st); if (rc) return rc;
+  u32* d_flags = tmp.at<u32>(o_flags); u32* d_offs = tmp.at<u32>(o_offs);
+  void* d_scan = tmp.at<char>(o_scan);
+  uint4* d_negc = tmp.at<uint4>(o_negc);
+  u32* d_nnz = tmp.at<u32>(o_nnz);
   HIPCHK(ctx, hipMemcpyAsync(d_negc, negc.data(), (size_t)d * 64, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemsetAsync(d_nnz, 0, (size_t)d * 4, st));
   if (n) hipLaunchKernelGGL(lemsm::dw::k_lhs_count, dim3((u32)((n + 4095) / 4096), d), dim3(256), 0, st, digitsT, (u32)n, d_nnz);
@@ -738,15 +732,10 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
     counts[s_] = (size_t)leads[s_] + nnz[pos] + 1; starts[s_] = total; total += counts[s_];
   }
   const size_t o_lists = ar_lists.take("lists", total * 64, 256);
-  rc = reserve(ctx, ctx->gather, ar_lists.end()); if (rc) return rc;                // (the multi-GPU record buffer doubles as the list buffer)
-  uint4* d_tmp = (uint4*)((char*)ctx->gather.p + o_lists);
-  rc = arena_fill(ctx, ar_lists, ctx->gather.p, st); if (rc) return rc;
+  rc = lists.open(ctx, std::move(ar_lists), ctx->gather, ar_lists.end(), st); if (rc) return rc;   // (the multi-GPU record buffer doubles as the list buffer)
+  uint4* d_tmp = lists.at<uint4>(o_lists);
   // returns behind the (synchronised) list kernels: the three arenas' guard zones first
-  auto lists_done = [&](int status) {
-    status = arena_done(ctx, ar_ws, wb, st, status);
-    status = arena_done(ctx, ar_tmp, tb, st, status);
-    return arena_done(ctx, ar_lists, ctx->gather.p, st, status);
-  };
+  auto lists_done = [&](int status) { return lists.done(tmp.done(ws.done(status))); };
   for (u32 i = i_begin; i < i_end; i++) {
     const u32 pos = d - 1 - i, s_ = i - i_begin;
     uint4* lst = d_tmp + starts[s_] * 4;
@@ -767,7 +756,7 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   rc = dw_run_forest(ctx, d_tmp, counts, fo); if (rc) return lists_done(rc);
   for (u32 i = 0; i < nt; i++) {
     u64 o = 0; for (int q = 0; q < 8; q++) o |= fo.trees[i].out_aff[q];
-    if (o) return lists_done(dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)")));
+    if (o) return lists_done(fo.ws.done(fail(ctx, LEMSM_ERR_SUM_NOT_IDENTITY, "compute_divisor_witness: the points do not sum to the identity (panic at src/regular_functions_utils.rs:478)")));
   }
   if (normalise) { rc = dw_normalise_forest(ctx, fo); if (rc) return rc; }
   HIPCHK(ctx, hipStreamSynchronize(st));
@@ -782,7 +771,7 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
     ix[0] = used; ix[1] = res.la; ix[2] = used + res.la; ix[3] = res.lb;
     used += (size_t)res.la + res.lb;
   }
-  if (used > cap_coeffs) return lists_done(dw_forest_done(ctx, fo, fail(ctx, LEMSM_ERR_BAD_ARG, "lhs witness: coefficient capacity too small (2 d (n + base + 3) always suffices)")));
+  if (used > cap_coeffs) return lists_done(fo.ws.done(fail(ctx, LEMSM_ERR_BAD_ARG, "lhs witness: coefficient capacity too small (2 d (n + base + 3) always suffices)")));
   for (u32 f = f_begin; f < f_end; f++) {
     const size_t* ix = out_index + 4 * (size_t)f;
     const DwResult& res = fo.trees[(d - 1 - f) - i_begin];
@@ -794,7 +783,7 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   ctx->dw_phase_ms[3] = ms_since(t_phase);
   const double ntt_ms = fo.ntt_ms; const u64 ntt_bytes = fo.ntt_bytes; ctx->dw_ntt_bflies = fo.ntt_bflies; ctx->dw_reuse_levels = fo.reuse_levels;
   ctx->dw_ntt_ms = ntt_ms; ctx->dw_ntt_bytes = ntt_bytes;
-  return lists_done(dw_forest_done(ctx, fo, LEMSM_OK));
+  return lists_done(fo.ws.done(LEMSM_OK));
 }
 
 int lemsm_lhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const uint64_t* pts_jacobian, size_t n, uint8_t base,

@@ -15,6 +15,7 @@
 
 #include "../../include/lemsm.h"
 #include "arena.hpp"
+#include "timed_run.hpp"
 #include "hostmath.hpp"
 #include "hostpool.hpp"
 #include "hosttail.hpp"
@@ -120,6 +121,9 @@ struct PyrCacheEntry { DevBuf buf; PyrPlan pp; };   // task tables resident on t
 
 }  // namespace
 
+// what a family's *_last entry reports: device time of the last call's kernels, the bytes and field products it was priced at
+struct LastStats { double ms = 0; u64 bytes = 0, mults = 0; };
+
 // host-pointer entries: where one call's inputs live on the host and where their slabs are staged in HBM
 struct HostStage { const uint8_t* h_scalars; const void* h_points; char* d_scalars; char* d_points; };
 
@@ -146,12 +150,11 @@ struct lemsm_ctx {
   size_t dw_tab_off[4] = {0, 0, 0, 0};   // ... at these offsets of dw_tab: W, GP, GI, W32 (dw_ensure_tables)
   double dw_ntt_ms = 0; u64 dw_ntt_bytes = 0, dw_ntt_bflies = 0; u32 dw_reuse_levels = 0;
   DevBuf rf_coef, rf_ws;             // regular-function evaluation: staged coefficients (host entry), tables / partials / values
-  double rf_ms = 0; u64 rf_bytes = 0, rf_mults = 0;   // lemsm_regfn_eval_last
-  double ld_ms = 0; u64 ld_bytes = 0, ld_mults = 0;   // lemsm_regfn_logderiv_last
+  LastStats rf_last, ld_last;        // lemsm_regfn_eval_last, lemsm_regfn_logderiv_last
   DevBuf rhs_ws, rhs_tab, rhs_pw;    // rhs witness / fraction sums: engine workspace, table + staged columns (host entries), powers of -base
-  double rhs_ms = 0; u64 rhs_bytes = 0, rhs_mults = 0;   // lemsm_rhs_last
+  LastStats rhs_last;                // lemsm_rhs_last
   DevBuf col_ws, col_stage;          // column a / poly rlc: function and power tables, staged inputs + outputs (host entries)
-  double col_ms = 0; u64 col_bytes = 0, col_mults = 0;   // lemsm_column_last
+  LastStats col_last;                // lemsm_column_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
   int plan_world = 1;   // ranks sharing the current call's windows: > 1 pins 16-bit windows (16 split evenly over 2/4/8 ranks, 15 do not)
@@ -201,8 +204,8 @@ int reserve(lemsm_ctx* ctx, DevBuf& b, size_t bytes) {
 }
 
 // Workspace arenas (arena.hpp) on a stream.  Every hand-carved workspace outside the MSM window group goes through these:
-// option ws_canary puts a guard zone behind each sub-buffer, arena_fill patterns the zones before the arena's first launch,
-// arena_done checks them once the arena's kernels have run.
+// option ws_canary puts a guard zone behind each sub-buffer, Workspace::open patterns the zones before the arena's first
+// launch, Workspace::done checks them once the arena's kernels have run.
 using lemsm::arena::Arena;
 struct ArenaHipMem {
   hipStream_t st; hipError_t err = hipSuccess;
@@ -223,14 +226,72 @@ int arena_check(lemsm_ctx* ctx, const Arena& a, const void* base, hipStream_t st
   if (r < 0) return fail(ctx, LEMSM_ERR_HIP, "workspace guard " + a.name() + ": read-back: " + hipGetErrorString(m.err));
   return r ? fail(ctx, LEMSM_ERR_HIP, msg) : LEMSM_OK;
 }
-// the status of a return that comes after the arena's kernels have run: a damaged guard outranks `rc` (and its message)
-int arena_done(lemsm_ctx* ctx, const Arena& a, const void* base, hipStream_t st, int rc) {
-  if (!a.guards() || rc == LEMSM_ERR_HIP || rc == LEMSM_ERR_NOMEM) return rc;   // (a failed runtime call stands as it is)
-  const std::string keep = ctx->last_error;
-  const int g = arena_check(ctx, a, base, st);
-  if (g) return g;
-  ctx->last_error = keep;
-  return rc;
+// One carved workspace in use: the arena, the buffer it is carved from and the stream its work runs on.  open() reserves
+// the buffer and patterns the guard zones, at<T>(offset) is a sub-buffer, check() / done(rc) read the zones back; both
+// stand behind a synchronise.  A scope that is left any other way (a failed call between open and done) waits for the
+// stream first: what was enqueued under it reads and writes host objects of the frame that is being left, so declare
+// those before the scope.
+struct Workspace {
+  lemsm_ctx* ctx = nullptr; Arena ar; char* base = nullptr; hipStream_t st = nullptr;
+  bool in_flight = false;
+  Workspace() {}
+  Workspace(const Workspace&) = delete; Workspace& operator=(const Workspace&) = delete;
+  ~Workspace() { if (in_flight) (void)hipStreamSynchronize(st); }
+  // `a`: the site's carve, taken over here (so after the call's arguments have been evaluated); `request`: the site's own
+  // figure, never derived from the arena (with guards off it is the one the site always asked for)
+  int open(lemsm_ctx* c, Arena&& a, DevBuf& buf, size_t request, hipStream_t s) {
+    int rc = reserve(c, buf, request); if (rc) return rc;
+    ctx = c; ar = std::move(a); base = (char*)buf.p; st = s; in_flight = true;
+    return arena_fill(ctx, ar, base, st);
+  }
+  template <class T> T* at(size_t off) const { return (T*)(base + off); }
+  int check() { in_flight = false; return arena_check(ctx, ar, base, st); }
+  // the status of a return that comes after the arena's kernels have run: a damaged guard outranks `rc` (and its message)
+  int done(int rc) {
+    if (rc == LEMSM_ERR_HIP || rc == LEMSM_ERR_NOMEM) return rc;   // (a failed runtime call stands as it is)
+    if (!ar.guards()) { in_flight = false; return rc; }
+    const std::string keep = ctx->last_error;
+    const int g = check();
+    if (g) return g;
+    ctx->last_error = keep;
+    return rc;
+  }
+};
+
+// A timed section on a stream between ctx->ev[0] and ctx->ev[1] (timed_run.hpp): `launch` enqueues the kernels, `read_back`
+// the device-to-host copies of results and error words and returns a status; rec.ms = the kernels' device time.  Every
+// exit, the error exits too, has synchronised the stream.
+struct HipTimedQueue {
+  lemsm_ctx* ctx; hipStream_t st;
+  int status(hipError_t e, const char* what, bool keep = true) {
+    return e == hipSuccess ? LEMSM_OK : keep ? fail(ctx, LEMSM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)) : LEMSM_ERR_HIP;
+  }
+  int record(int i) { return status(hipEventRecord(ctx->ev[i], st), "hipEventRecord"); }
+  int last_error() { return status(hipGetLastError(), "hipGetLastError"); }
+  int sync(bool keep) { return status(hipStreamSynchronize(st), "hipStreamSynchronize", keep); }
+  int elapsed(double& ms) { float f = 0; const int rc = status(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]), "hipEventElapsedTime"); if (!rc) ms = f; return rc; }
+};
+template <class Launch, class ReadBack>
+int timed_run(lemsm_ctx* ctx, hipStream_t st, LastStats& rec, Launch&& launch, ReadBack&& read_back) {
+  HipTimedQueue q{ctx, st};
+  return lemsm::timed_run(q, rec.ms, launch, read_back);
+}
+// the four lemsm_*_last entries
+int last_stats(const lemsm_ctx* ctx, const LastStats lemsm_ctx::*rec, double* ms, uint64_t* bytes, uint64_t* field_mults) {
+  if (!ctx) return LEMSM_ERR_BAD_ARG;
+  if (ms) *ms = (ctx->*rec).ms;
+  if (bytes) *bytes = (ctx->*rec).bytes;
+  if (field_mults) *field_mults = (ctx->*rec).mults;
+  return LEMSM_OK;
+}
+
+// index rows {offset_a, len_a, offset_b, len_b} of T functions: no half reaches past cap_coeffs, no offset + length wraps
+bool index_rows_ok(const size_t* index, size_t T, size_t cap_coeffs) {
+  for (size_t i = 0; i < 2 * T; i++) {
+    const size_t end = index[2 * i] + index[2 * i + 1];
+    if (end < index[2 * i] || end > cap_coeffs) return false;
+  }
+  return true;
 }
 
 // pinned host staging buffer of the context

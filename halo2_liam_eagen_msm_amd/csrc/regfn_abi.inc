@@ -1,6 +1,6 @@
 // RegularFunction::ev / ev_unchecked (include/lemsm.h: lemsm_regfn_eval*): batched, segmented polynomial evaluation over
-// bn256::Fr on coefficients resident in HBM.  Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, HIPCHK,
-// fail, align_up); the kernels are regfn_eval.cuh's.
+// bn256::Fr on coefficients resident in HBM.  Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, timed_run,
+// LastStats / last_stats, index_rows_ok, stage, HIPCHK, fail); the kernels are regfn_eval.cuh's.
 
 namespace {
 
@@ -8,15 +8,11 @@ struct RfPlan { size_t num_values = 0, max_pts = 0; u64 field_mults = 0, coeff_b
 
 // validates a request and prices it: pure host
 int rf_plan(const size_t* index, size_t T, size_t cap_coeffs, const size_t* counts, size_t K, RfPlan& p) {
-  if (T && !index) return LEMSM_ERR_BAD_ARG;
+  if ((T && !index) || !index_rows_ok(index, T, cap_coeffs)) return LEMSM_ERR_BAD_ARG;
   p = RfPlan();
   size_t sum = 0; bool wrap = false;
   for (size_t t = 0; t < T; t++) {
     const size_t* ix = index + 4 * t;
-    for (int h = 0; h < 2; h++) {
-      const size_t end = ix[2 * h] + ix[2 * h + 1];
-      if (end < ix[2 * h] || end > cap_coeffs) return LEMSM_ERR_BAD_ARG;   // past the buffer, or offset + length wraps
-    }
     const size_t np = counts ? counts[t] : K, len = ix[1] + ix[3];   // (both <= cap_coeffs <= SIZE_MAX / 32 of a real buffer)
     if (counts) { if (sum + np < sum) wrap = true; sum += np; }
     p.max_pts = std::max(p.max_pts, np);
@@ -34,6 +30,8 @@ int rf_plan(const size_t* index, size_t T, size_t cap_coeffs, const size_t* coun
 }
 
 typedef host::HF<host::FrParams64> RfHF;
+
+const char* const RF_CURVE_MSG = "RegularFunction::ev: only Grumpkin (C::Base = bn256::Fr is the one FftPrecomp field, src/precomputed_fft_data.rs:3)";
 
 // ev (:228-231): x = X / Z^2, y = Y / Z^3, one inversion for the whole list (Montgomery's trick on the host: the points are
 // in host memory); Z == 0 is the reference's invert().unwrap() panic
@@ -80,11 +78,11 @@ int lemsm_regfn_eval_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, siz
                             const uint64_t* points, int jacobian, const size_t* counts, size_t K, uint64_t* out_values, size_t* bad_index) {
   namespace rf = lemsm::rf;
   if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, "RegularFunction::ev: only Grumpkin (C::Base = bn256::Fr is the one FftPrecomp field, src/precomputed_fft_data.rs:3)");
+  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, RF_CURVE_MSG);
   RfPlan pl;
   int rc = rf_plan(index, T, cap_coeffs, counts, K, pl);
   if (rc) return fail(ctx, rc, rc == LEMSM_ERR_LEN_MISMATCH ? "regfn eval: K is not the sum of counts" : "regfn eval: an index row reaches past cap_coeffs");
-  ctx->rf_ms = 0; ctx->rf_bytes = pl.coeff_bytes; ctx->rf_mults = pl.field_mults;
+  ctx->rf_last = LastStats{0, pl.coeff_bytes, pl.field_mults};
   if (pl.num_values == 0) return LEMSM_OK;
   if (!points || !out_values || (pl.coeffs && !d_coeffs)) return LEMSM_ERR_BAD_ARG;
   if (K >= ((size_t)1 << 31) || pl.num_values >= ((size_t)1 << 31) || T >= ((size_t)1 << 31)) return fail(ctx, LEMSM_ERR_BAD_ARG, "regfn eval: too many points, functions or values (max 2^31 - 1)");
@@ -129,43 +127,32 @@ int lemsm_regfn_eval_device(lemsm_ctx* ctx, int curve, const void* d_coeffs, siz
   const size_t o_pts = take("points", K * 64), o_pw = take("powers", b_pw), o_pwy = ymax ? take("ypowers", b_pw) : ar.total();
   const size_t o_items = take("items", items.size() * sizeof(rf::Item)), o_fns = take("functions", T * sizeof(rf::Fn));
   const size_t o_fov = take("fn_of_value", fn_of_val.size() * 4), o_part = take("partials", (size_t)npart * 32), o_val = take("values", pl.num_values * 32);
-  rc = reserve(ctx, ctx->rf_ws, ar.total() + 256); if (rc) return rc;   // (+ 256 nobody reads)
-  char* w = (char*)ctx->rf_ws.p;
-  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
-  uint4* d_pts = (uint4*)(w + o_pts);
-  uint4* d_pw = (uint4*)(w + o_pw);
-  uint4* d_pwy = (uint4*)(w + o_pwy);
-  rf::Item* d_items = (rf::Item*)(w + o_items);
-  rf::Fn* d_fns = (rf::Fn*)(w + o_fns);
-  u32* d_fov = (u32*)(w + o_fov);
-  uint4* d_part = (uint4*)(w + o_part);
-  uint4* d_val = (uint4*)(w + o_val);
+  Workspace ws;   // (behind aff, items, fns, fn_of_val: the stream has read them when it goes)
+  rc = ws.open(ctx, std::move(ar), ctx->rf_ws, ar.total() + 256, st); if (rc) return rc;   // (+ 256 nobody reads)
+  uint4* d_pts = ws.at<uint4>(o_pts); uint4* d_pw = ws.at<uint4>(o_pw); uint4* d_pwy = ws.at<uint4>(o_pwy);
+  rf::Item* d_items = ws.at<rf::Item>(o_items); rf::Fn* d_fns = ws.at<rf::Fn>(o_fns); u32* d_fov = ws.at<u32>(o_fov);
+  uint4* d_part = ws.at<uint4>(o_part); uint4* d_val = ws.at<uint4>(o_val);
   HIPCHK(ctx, hipMemcpyAsync(d_pts, aff.data(), K * 64, hipMemcpyHostToDevice, st));
   if (!items.empty()) HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(rf::Item), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(d_fns, fns.data(), T * sizeof(rf::Fn), hipMemcpyHostToDevice, st));
   if (counts) HIPCHK(ctx, hipMemcpyAsync(d_fov, fn_of_val.data(), K * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(rf::k_regfn_powers, dim3((u32)K), dim3(64), 0, st, (const uint4*)d_pts, (u32)K, d_pw);
-  if (ymax) hipLaunchKernelGGL(rf::k_regfn_ypowers, dim3((u32)(((u64)K * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)K, ymax, d_pwy);
-  if (!items.empty()) {
-    if (PT == 1) hipLaunchKernelGGL((rf::k_regfn_tiles<1>), dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(), (const uint4*)d_pw, d_part);
-    else hipLaunchKernelGGL((rf::k_regfn_tiles<rf::RF_PT>), dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(), (const uint4*)d_pw, d_part);
-  }
-  hipLaunchKernelGGL(rf::k_regfn_fold, dim3((u32)pl.num_values), dim3(64), 0, st, (const rf::Fn*)d_fns, (const u32*)d_fov, counts ? 0u : (u32)K, (u64)pl.num_values,
-                     (const uint4*)d_pts, (const uint4*)d_pwy, (const uint4*)d_part, d_val);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-  HIPCHK(ctx, hipMemcpyAsync(out_values, d_val, pl.num_values * 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->rf_ms = ms;
-  return arena_done(ctx, ar, w, st, LEMSM_OK);
+  rc = timed_run(ctx, st, ctx->rf_last, [&] {
+    hipLaunchKernelGGL(rf::k_regfn_powers, dim3((u32)K), dim3(64), 0, st, (const uint4*)d_pts, (u32)K, d_pw);
+    if (ymax) hipLaunchKernelGGL(rf::k_regfn_ypowers, dim3((u32)(((u64)K * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)K, ymax, d_pwy);
+    if (!items.empty()) {
+      if (PT == 1) hipLaunchKernelGGL((rf::k_regfn_tiles<1>), dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(), (const uint4*)d_pw, d_part);
+      else hipLaunchKernelGGL((rf::k_regfn_tiles<rf::RF_PT>), dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(), (const uint4*)d_pw, d_part);
+    }
+    hipLaunchKernelGGL(rf::k_regfn_fold, dim3((u32)pl.num_values), dim3(64), 0, st, (const rf::Fn*)d_fns, (const u32*)d_fov, counts ? 0u : (u32)K, (u64)pl.num_values,
+                       (const uint4*)d_pts, (const uint4*)d_pwy, (const uint4*)d_part, d_val);
+  }, [&] { HIPCHK(ctx, hipMemcpyAsync(out_values, d_val, pl.num_values * 32, hipMemcpyDeviceToHost, st)); return LEMSM_OK; });
+  return ws.done(rc);
 }
 
 int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,
                      const uint64_t* points, int jacobian, const size_t* counts, size_t K, uint64_t* out_values, size_t* bad_index) {
   if (!ctx || (cap_coeffs && !coeffs)) return LEMSM_ERR_BAD_ARG;
-  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, "RegularFunction::ev: only Grumpkin (C::Base = bn256::Fr is the one FftPrecomp field, src/precomputed_fft_data.rs:3)");
+  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, RF_CURVE_MSG);
   if (cap_coeffs > (size_t)-1 / 32) return fail(ctx, LEMSM_ERR_BAD_ARG, "regfn eval: cap_coeffs too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = stage(ctx, ctx->rf_coef, coeffs, cap_coeffs * 32); if (rc) return rc;
@@ -173,12 +160,6 @@ int lemsm_regfn_eval(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t c
   return lemsm_regfn_eval_device(ctx, curve, ctx->rf_coef.p, cap_coeffs, index, T, points, jacobian, counts, K, out_values, bad_index);
 }
 
-int lemsm_regfn_eval_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults) {
-  if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (ms) *ms = ctx->rf_ms;
-  if (coeff_bytes) *coeff_bytes = ctx->rf_bytes;
-  if (field_mults) *field_mults = ctx->rf_mults;
-  return LEMSM_OK;
-}
+int lemsm_regfn_eval_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::rf_last, ms, coeff_bytes, field_mults); }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // L(f) of resident divisor witnesses and the argument's residual (include/lemsm.h: lemsm_regfn_logderiv*,
 // lemsm_argument_residual; DESIGN 6b).  Included at the end of lemsm.hip after regfn_abi.inc (it uses rf_plan, RfHF,
-// fr_from_u64, lemsm_ctx, reserve, stage, HIPCHK, fail, align_up); the kernels are regfn_logderiv.cuh's.
+// RF_CURVE_MSG, fr_from_u64, lemsm_ctx, Arena, Workspace, timed_run, LastStats / last_stats, stage, HIPCHK, fail); the
+// kernels are regfn_logderiv.cuh's.
 
 namespace {
 
@@ -77,54 +78,44 @@ int ld_run(lemsm_ctx* ctx, const void* d_coeffs, const size_t* index, size_t T, 
   const size_t o_L = ar.take("leaves", npairs * 32), o_sum = ar.take("sums", K * 32);
   const size_t o_pd = want_pd ? ar.take("poly_values", 8 * npairs * 32) : 0;
   const size_t o_err = ar.take("error_word", 8, 248);   // the kernels' error word lives in the 256 bytes behind the last block
-  int rc = reserve(ctx, ctx->rf_ws, ar.total() + 256);   // (+ 256 nobody reads)
-  if (rc) return rc;
-  char* w = (char*)ctx->rf_ws.p;
-  rc = arena_fill(ctx, ar, w, st); if (rc) return rc;
-  uint4* d_pts = (uint4*)(w + o_pts);
-  uint4* d_pw = (uint4*)(w + o_pw); uint4* d_dpw = (uint4*)(w + o_dpw); uint4* d_pwy = (uint4*)(w + o_pwy); uint4* d_dpwy = (uint4*)(w + o_dpwy);
-  uint4* d_dydx = (uint4*)(w + o_dydx);
-  rf::LdChal* d_chal = (rf::LdChal*)(w + o_chal);
-  rf::Item* d_items = (rf::Item*)(w + o_items);
-  rf::Fn* d_fns = (rf::Fn*)(w + o_fns);
-  uint4* d_part = (uint4*)(w + o_part);
-  uint4* d_num = (uint4*)(w + o_num); uint4* d_den = (uint4*)(w + o_den); uint4* d_pre = (uint4*)(w + o_pre);
-  o.L = (uint4*)(w + o_L); o.sum = (uint4*)(w + o_sum);
-  o.pd = want_pd ? (uint4*)(w + o_pd) : nullptr;
-  unsigned long long* d_err = (unsigned long long*)(w + o_err);
+  unsigned long long errw = ~0ull;
+  Workspace ws;   // (behind items, fns, errw: the stream has read and written them when it goes)
+  int rc = ws.open(ctx, std::move(ar), ctx->rf_ws, ar.total() + 256, st); if (rc) return rc;   // (+ 256 nobody reads)
+  uint4* d_pts = ws.at<uint4>(o_pts);
+  uint4* d_pw = ws.at<uint4>(o_pw); uint4* d_dpw = ws.at<uint4>(o_dpw); uint4* d_pwy = ws.at<uint4>(o_pwy); uint4* d_dpwy = ws.at<uint4>(o_dpwy);
+  uint4* d_dydx = ws.at<uint4>(o_dydx);
+  rf::LdChal* d_chal = ws.at<rf::LdChal>(o_chal); rf::Item* d_items = ws.at<rf::Item>(o_items); rf::Fn* d_fns = ws.at<rf::Fn>(o_fns);
+  uint4* d_part = ws.at<uint4>(o_part);
+  uint4* d_num = ws.at<uint4>(o_num); uint4* d_den = ws.at<uint4>(o_den); uint4* d_pre = ws.at<uint4>(o_pre);
+  o.L = ws.at<uint4>(o_L); o.sum = ws.at<uint4>(o_sum);
+  o.pd = want_pd ? ws.at<uint4>(o_pd) : nullptr;
+  unsigned long long* d_err = ws.at<unsigned long long>(o_err);
   HIPCHK(ctx, hipMemcpyAsync(d_pts, absc.data(), rows * 64, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(d_chal, chal.data(), rows * sizeof(rf::LdChal), hipMemcpyHostToDevice, st));
   if (!items.empty()) HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(rf::Item), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(d_fns, fns.data(), T * sizeof(rf::Fn), hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemsetAsync(d_err, 0xff, 8, st));
   rf::LdWeight wt; memcpy(wt.w, weight.l, 32);
-  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(rf::k_regfn_powers, dim3((u32)rows), dim3(64), 0, st, (const uint4*)d_pts, (u32)rows, d_pw);
-  hipLaunchKernelGGL(rf::k_ld_dtable, dim3((u32)((rows * 64 + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)rows, 64u, d_dpw);
-  if (ymax) {
-    hipLaunchKernelGGL(rf::k_ld_ypowers, dim3((u32)((rows * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)rows, ymax, d_pwy, d_dydx);
-    hipLaunchKernelGGL(rf::k_ld_dtable, dim3((u32)((rows * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pwy, (u32)rows, ymax, d_dpwy);
-  }
-  if (!items.empty())
-    hipLaunchKernelGGL(rf::k_ld_tiles, dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(),
-                       (const uint4*)d_pw, (const uint4*)d_dpw, d_part);
-  hipLaunchKernelGGL(rf::k_ld_fold, dim3((u32)npairs), dim3(64), 0, st, (const rf::Fn*)d_fns, (u32)K, (u64)npairs, (const rf::LdChal*)d_chal,
-                     (const uint4*)d_pwy, (const uint4*)d_dpwy, (const uint4*)d_dydx, (const uint4*)d_part, d_num, d_den, d_err, o.pd);
-  const u64 nthr = (npairs + rk - 1) / rk;
-  hipLaunchKernelGGL(rf::k_ld_invert, dim3((u32)((nthr + 63) / 64)), dim3(64), 0, st, (const uint4*)d_num, (const uint4*)d_den, d_pre, (u64)npairs, rk, o.L);
-  hipLaunchKernelGGL(rf::k_ld_sum, dim3((u32)((K + 63) / 64)), dim3(64), 0, st, (const uint4*)o.L, (u32)T, (u32)K, wt, o.sum);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-  unsigned long long errw = ~0ull;
-  HIPCHK(ctx, hipMemcpyAsync(&errw, d_err, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->ld_ms = ms;
+  rc = timed_run(ctx, st, ctx->ld_last, [&] {
+    hipLaunchKernelGGL(rf::k_regfn_powers, dim3((u32)rows), dim3(64), 0, st, (const uint4*)d_pts, (u32)rows, d_pw);
+    hipLaunchKernelGGL(rf::k_ld_dtable, dim3((u32)((rows * 64 + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)rows, 64u, d_dpw);
+    if (ymax) {
+      hipLaunchKernelGGL(rf::k_ld_ypowers, dim3((u32)((rows * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pw, (u32)rows, ymax, d_pwy, d_dydx);
+      hipLaunchKernelGGL(rf::k_ld_dtable, dim3((u32)((rows * ymax + 255) / 256)), dim3(256), 0, st, (const uint4*)d_pwy, (u32)rows, ymax, d_dpwy);
+    }
+    if (!items.empty())
+      hipLaunchKernelGGL(rf::k_ld_tiles, dim3((u32)items.size()), dim3(64), 0, st, (const uint4*)d_coeffs, (const rf::Item*)d_items, (u32)items.size(),
+                         (const uint4*)d_pw, (const uint4*)d_dpw, d_part);
+    hipLaunchKernelGGL(rf::k_ld_fold, dim3((u32)npairs), dim3(64), 0, st, (const rf::Fn*)d_fns, (u32)K, (u64)npairs, (const rf::LdChal*)d_chal,
+                       (const uint4*)d_pwy, (const uint4*)d_dpwy, (const uint4*)d_dydx, (const uint4*)d_part, d_num, d_den, d_err, o.pd);
+    const u64 nthr = (npairs + rk - 1) / rk;
+    hipLaunchKernelGGL(rf::k_ld_invert, dim3((u32)((nthr + 63) / 64)), dim3(64), 0, st, (const uint4*)d_num, (const uint4*)d_den, d_pre, (u64)npairs, rk, o.L);
+    hipLaunchKernelGGL(rf::k_ld_sum, dim3((u32)((K + 63) / 64)), dim3(64), 0, st, (const uint4*)o.L, (u32)T, (u32)K, wt, o.sum);
+  }, [&] { HIPCHK(ctx, hipMemcpyAsync(&errw, d_err, 8, hipMemcpyDeviceToHost, st)); return LEMSM_OK; });
+  if (rc) return rc;
   *err = errw;
-  return arena_check(ctx, ar, w, st);   // (before the caller turns the error word into a status: a damaged guard outranks it)
+  return ws.check();   // (before the caller turns the error word into a status: a damaged guard outranks it)
 }
-
-const char* const LD_CURVE_MSG = "RegularFunction::ev: only Grumpkin (C::Base = bn256::Fr is the one FftPrecomp field, src/precomputed_fft_data.rs:3)";
 
 int ld_limits(lemsm_ctx* ctx, size_t T, size_t K) {
   if (K >= ((size_t)1 << 30) || T >= ((size_t)1 << 31) || (K && T > (((size_t)1 << 31) - 1) / K))
@@ -170,13 +161,13 @@ int lemsm_regfn_logderiv_device(lemsm_ctx* ctx, int curve, const void* d_coeffs,
                                 const uint64_t* a_xy, size_t K, uint8_t base, uint64_t* out_L, uint64_t* out_sum, uint64_t* out_t, size_t* bad_index) {
   namespace rf = lemsm::rf;
   if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, LD_CURVE_MSG);
+  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, RF_CURVE_MSG);
   if (base < 3) return fail(ctx, LEMSM_ERR_BAD_BASE, "base must be >= 3");
   RfPlan pl;
   int rc = rf_plan(index, T, cap_coeffs, nullptr, K, pl);
   if (rc) return fail(ctx, rc, "regfn logderiv: an index row reaches past cap_coeffs");
   rc = ld_limits(ctx, T, K); if (rc) return rc;
-  ctx->ld_ms = 0; ctx->ld_bytes = pl.coeff_bytes; ctx->ld_mults = 4 * pl.field_mults;
+  ctx->ld_last = LastStats{0, pl.coeff_bytes, 4 * pl.field_mults};
   if (K == 0) return LEMSM_OK;
   if (!a_xy || (pl.coeffs && !d_coeffs)) return LEMSM_ERR_BAD_ARG;
   std::vector<uint64_t> absc(2 * K * 8), tt(K * 4);
@@ -210,7 +201,7 @@ int lemsm_regfn_logderiv_device(lemsm_ctx* ctx, int curve, const void* d_coeffs,
 int lemsm_regfn_logderiv(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T,
                          const uint64_t* a_xy, size_t K, uint8_t base, uint64_t* out_L, uint64_t* out_sum, uint64_t* out_t, size_t* bad_index) {
   if (!ctx || (cap_coeffs && !coeffs)) return LEMSM_ERR_BAD_ARG;
-  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, LD_CURVE_MSG);
+  if (curve != LEMSM_GRUMPKIN) return fail(ctx, LEMSM_ERR_BAD_CURVE, RF_CURVE_MSG);
   if (cap_coeffs > (size_t)-1 / 32) return fail(ctx, LEMSM_ERR_BAD_ARG, "regfn logderiv: cap_coeffs too large");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = stage(ctx, ctx->rf_coef, coeffs, cap_coeffs * 32); if (rc) return rc;
@@ -218,13 +209,7 @@ int lemsm_regfn_logderiv(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size
   return lemsm_regfn_logderiv_device(ctx, curve, ctx->rf_coef.p, cap_coeffs, index, T, a_xy, K, base, out_L, out_sum, out_t, bad_index);
 }
 
-int lemsm_regfn_logderiv_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults) {
-  if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (ms) *ms = ctx->ld_ms;
-  if (coeff_bytes) *coeff_bytes = ctx->ld_bytes;
-  if (field_mults) *field_mults = ctx->ld_mults;
-  return LEMSM_OK;
-}
+int lemsm_regfn_logderiv_last(const lemsm_ctx* ctx, double* ms, uint64_t* coeff_bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::ld_last, ms, coeff_bytes, field_mults); }
 
 int lemsm_debug_regfn_deriv(lemsm_ctx* ctx, const uint64_t* coeffs, size_t cap_coeffs, const size_t* index, size_t T, const uint64_t* xs,
                             size_t K, uint64_t* out) {

@@ -1,7 +1,7 @@
 // The right-hand side of the argument (include/lemsm.h: lemsm_rhs_*, lemsm_multiples_table_device, lemsm_fraction_sums*):
 // the running sums of the reference's "rhs main" gate (src/config.rs:504-538) and of its lookup columns (:402-437).
-// Included at the end of lemsm.hip (it uses lemsm_ctx, DevBuf, reserve, stage, HIPCHK, fail, align_up, make_lhs_plan,
-// with_curve, k_precompute_mult_affine); the kernels are rhs.cuh's.
+// Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, timed_run, LastStats / last_stats, stage, HIPCHK, fail,
+// make_lhs_plan, with_curve, k_precompute_mult_affine); the kernels are rhs.cuh's.
 
 namespace {
 
@@ -46,36 +46,34 @@ FsWs fs_carve(const FsGeom& g, bool guard) {
 template <class F, class Src>
 int fs_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const uint64_t* init, void* d_out, uint64_t* out_totals, u64* err_den, u64* err_range) {
   hipStream_t st = ctx->stream;
-  const FsWs ws = fs_carve(g, ctx->opt.ws_canary != 0);
-  int rc = reserve(ctx, ctx->rhs_ws, ws.ar.total()); if (rc) return rc;
-  char* w = (char*)ctx->rhs_ws.p;
-  rc = arena_fill(ctx, ws.ar, w, st); if (rc) return rc;
-  uint4* bufN = (uint4*)(w + ws.bufN); uint4* bufD = (uint4*)(w + ws.bufD); uint4* bufP = (uint4*)(w + ws.bufP);
-  uint4* roots = (uint4*)(w + ws.roots); uint4* rpre = (uint4*)(w + ws.rpre);
-  uint4* segsum = (uint4*)(w + ws.segsum);
-  uint4* d_init = (uint4*)(w + ws.init); uint4* d_tot = (uint4*)(w + ws.tot);
-  fs::ErrWord* d_err = (fs::ErrWord*)(w + ws.err);
+  FsWs o = fs_carve(g, ctx->opt.ws_canary != 0);
+  u64 errw[2] = {~0ull, ~0ull};
+  Workspace ws;   // (behind errw: the stream has written it when it goes)
+  int rc = ws.open(ctx, std::move(o.ar), ctx->rhs_ws, o.ar.total(), st); if (rc) return rc;
+  uint4* bufN = ws.at<uint4>(o.bufN); uint4* bufD = ws.at<uint4>(o.bufD); uint4* bufP = ws.at<uint4>(o.bufP);
+  uint4* roots = ws.at<uint4>(o.roots); uint4* rpre = ws.at<uint4>(o.rpre);
+  uint4* segsum = ws.at<uint4>(o.segsum);
+  uint4* d_init = ws.at<uint4>(o.init); uint4* d_tot = ws.at<uint4>(o.tot);
+  fs::ErrWord* d_err = ws.at<fs::ErrWord>(o.err);
   if (init) HIPCHK(ctx, hipMemcpyAsync(d_init, init, g.chains * 32, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemsetAsync(d_err, 0xff, 16, st));
-  HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
   const u64 nsc = g.nseg * g.chains;
-  hipLaunchKernelGGL((fs::k_fs_prefix<F, Src>), dim3((u32)g.nblk), dim3(256), 0, st, src, g.N, bufN, bufD, bufP, roots, d_err);
-  hipLaunchKernelGGL((fs::k_fs_rootinv<F>), dim3((u32)((g.nthreads_inv + 255) / 256)), dim3(256), 0, st, roots, rpre, g.R, g.rk);
-  hipLaunchKernelGGL((fs::k_fs_apply<F>), dim3((u32)g.nblk), dim3(256), 0, st, g.N, bufN, (const uint4*)bufD, (const uint4*)bufP, (const uint4*)roots);
-  hipLaunchKernelGGL((fs::k_fs_segsum<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, segsum);
-  hipLaunchKernelGGL((fs::k_fs_segscan<F>), dim3((u32)g.chains), dim3(256), 0, st, segsum, g.chains, g.nseg, init ? (const uint4*)d_init : (const uint4*)nullptr, d_tot);
-  if (d_out)
-    hipLaunchKernelGGL((fs::k_fs_finish<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, (const uint4*)segsum, (uint4*)d_out);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-  u64 errw[2] = {~0ull, ~0ull};
-  HIPCHK(ctx, hipMemcpyAsync(errw, d_err, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipMemcpyAsync(out_totals, d_tot, g.chains * 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  float ms = 0; HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->rhs_ms = ms;
+  rc = timed_run(ctx, st, ctx->rhs_last, [&] {
+    hipLaunchKernelGGL((fs::k_fs_prefix<F, Src>), dim3((u32)g.nblk), dim3(256), 0, st, src, g.N, bufN, bufD, bufP, roots, d_err);
+    hipLaunchKernelGGL((fs::k_fs_rootinv<F>), dim3((u32)((g.nthreads_inv + 255) / 256)), dim3(256), 0, st, roots, rpre, g.R, g.rk);
+    hipLaunchKernelGGL((fs::k_fs_apply<F>), dim3((u32)g.nblk), dim3(256), 0, st, g.N, bufN, (const uint4*)bufD, (const uint4*)bufP, (const uint4*)roots);
+    hipLaunchKernelGGL((fs::k_fs_segsum<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, segsum);
+    hipLaunchKernelGGL((fs::k_fs_segscan<F>), dim3((u32)g.chains), dim3(256), 0, st, segsum, g.chains, g.nseg, init ? (const uint4*)d_init : (const uint4*)nullptr, d_tot);
+    if (d_out)
+      hipLaunchKernelGGL((fs::k_fs_finish<F>), dim3((u32)((nsc + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.chains, g.S, g.nseg, (const uint4*)segsum, (uint4*)d_out);
+  }, [&] {
+    HIPCHK(ctx, hipMemcpyAsync(errw, d_err, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(out_totals, d_tot, g.chains * 32, hipMemcpyDeviceToHost, st));
+    return LEMSM_OK;
+  });
+  if (rc) return rc;
   *err_den = errw[0]; *err_range = errw[1];
-  return arena_check(ctx, ws.ar, w, st);   // (before the caller turns the error words into a status: a damaged guard outranks them)
+  return ws.check();   // (before the caller turns the error words into a status: a damaged guard outranks them)
 }
 
 int fs_div_by_zero(lemsm_ctx* ctx, u64 index, size_t* bad_index, const char* what) {
@@ -130,8 +128,8 @@ int rhs_device_t(lemsm_ctx* ctx, const void* d_scalars, const void* d_table, con
   std::vector<u32> pw; rhs_power_table(base, pl.d, pw);
   Arena ar_pw("rhs_pw", ctx->opt.ws_canary != 0);
   ar_pw.take("powers", pw.size() * 4, 256);
-  int rc = reserve(ctx, ctx->rhs_pw, ar_pw.end()); if (rc) return rc;
-  rc = arena_fill(ctx, ar_pw, ctx->rhs_pw.p, ctx->stream); if (rc) return rc;
+  Workspace ws_pw;   // (behind pw: the stream has read it when it goes)
+  int rc = ws_pw.open(ctx, std::move(ar_pw), ctx->rhs_pw, ar_pw.end(), ctx->stream); if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->rhs_pw.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   fs::RhsSrc<F, typename C::P> src;
   src.scalars = (const uint4*)d_scalars; src.table = (const uint4*)d_table; src.pw = (const u32*)ctx->rhs_pw.p;
@@ -143,8 +141,8 @@ int rhs_device_t(lemsm_ctx* ctx, const void* d_scalars, const void* d_table, con
   uint64_t* totals = out_totals;
   if (!totals) { totals_tmp.resize(nb * 4); totals = totals_tmp.data(); }
   u64 err_den = ~0ull, err_range = ~0ull;
-  rc = fs_run<F>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range); if (rc) return rc;   // (pw stays valid: the call has synchronised)
-  rc = arena_check(ctx, ar_pw, ctx->rhs_pw.p, ctx->stream); if (rc) return rc;
+  rc = fs_run<F>(ctx, src, g, init, d_out_running, totals, &err_den, &err_range); if (rc) return rc;
+  rc = ws_pw.check(); if (rc) return rc;
   if (err_range != ~0ull) {
     if (bad_index) *bad_index = (size_t)err_range;
     ctx->bad_index = (size_t)err_range;
@@ -180,9 +178,9 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Arena ar("multiples_ws", ctx->opt.ws_canary != 0);
   const size_t o_jac = ar.take("jacobian", n * 96), in_bytes = ar.take("scratch", pl.num_terms * 160, 256);   // k_precompute_mult_affine: 160 B of scratch per multiple (+ 256 nobody reads)
-  rc = reserve(ctx, ctx->ws, ar.end()); if (rc) return rc;
-  char* b = (char*)ctx->ws.p + o_jac;
-  rc = arena_fill(ctx, ar, ctx->ws.p, ctx->stream); if (rc) return rc;
+  Workspace ws;
+  rc = ws.open(ctx, std::move(ar), ctx->ws, ar.end(), ctx->stream); if (rc) return rc;
+  char* b = ws.at<char>(o_jac);
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
   with_curve(curve, [&](auto cv) {
     typedef typename decltype(cv)::F F;
@@ -191,7 +189,7 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   });
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return arena_done(ctx, ar, ctx->ws.p, ctx->stream, LEMSM_OK);
+  return ws.done(LEMSM_OK);
 }
 
 int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, const void* d_table, size_t n, uint8_t base,
@@ -203,7 +201,7 @@ int lemsm_rhs_witness_device(lemsm_ctx* ctx, int curve, const void* d_scalars, c
   if (rc) return fail(ctx, rc, rc == LEMSM_ERR_BAD_BASE ? "base must be >= 3" : rc == LEMSM_ERR_BAD_CURVE ? "unknown curve id" : "n (base - 1) too large");
   if (!a_xy || !t) return LEMSM_ERR_BAD_ARG;
   const size_t nb = (size_t)base - 1;
-  ctx->rhs_ms = 0; ctx->rhs_bytes = pl.table_bytes + (d_out_running ? pl.out_bytes : 0); ctx->rhs_mults = pl.field_mults;
+  ctx->rhs_last = LastStats{0, pl.table_bytes + (d_out_running ? pl.out_bytes : 0), pl.field_mults};
   if (n == 0) {
     std::vector<uint64_t> tot(nb * 4);
     fs_totals_of_init(init, nb, tot.data());
@@ -235,17 +233,16 @@ int lemsm_rhs_witness(lemsm_ctx* ctx, int curve, const uint8_t* scalars, const u
   Arena ar_tab("rhs_tab", guard), ar_scr("rhs_scratch", guard);
   const size_t o_tab = ar_tab.take("table", pl.num_terms * 64);
   const size_t o_run = out_running ? ar_tab.take("running", pl.num_terms * 32, 256) : 0;
-  rc = reserve(ctx, ctx->rhs_tab, out_running ? ar_tab.end() : ar_tab.total() + 256); if (rc) return rc;   // (+ 256 nobody reads behind the last block)
-  ar_scr.take("scratch", pl.num_terms * 160, 256);                                                           // (the same)
-  rc = reserve(ctx, ctx->ws, ar_scr.end()); if (rc) return rc;
-  rc = arena_fill(ctx, ar_tab, ctx->rhs_tab.p, ctx->stream); if (rc) return rc;
-  rc = arena_fill(ctx, ar_scr, ctx->ws.p, ctx->stream); if (rc) return rc;
-  char* tab = (char*)ctx->rhs_tab.p + o_tab;
-  char* d_run = out_running ? (char*)ctx->rhs_tab.p + o_run : nullptr;
-  auto staged_done = [&](int status) { return arena_done(ctx, ar_scr, ctx->ws.p, ctx->stream, arena_done(ctx, ar_tab, ctx->rhs_tab.p, ctx->stream, status)); };
+  Workspace ws_tab, ws_scr;
+  rc = ws_tab.open(ctx, std::move(ar_tab), ctx->rhs_tab, out_running ? ar_tab.end() : ar_tab.total() + 256, ctx->stream); if (rc) return rc;   // (+ 256 nobody reads behind the last block)
+  ar_scr.take("scratch", pl.num_terms * 160, 256);                                                                                     // (the same)
+  rc = ws_scr.open(ctx, std::move(ar_scr), ctx->ws, ar_scr.end(), ctx->stream); if (rc) return rc;
+  char* tab = ws_tab.at<char>(o_tab);
+  char* d_run = out_running ? ws_tab.at<char>(o_run) : nullptr;
+  auto staged_done = [&](int status) { return ws_scr.done(ws_tab.done(status)); };
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
   with_curve(curve, [&](auto cv) {
-    hipLaunchKernelGGL((k_precompute_mult_affine<typename decltype(cv)::F>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, (char*)ctx->ws.p);
+    hipLaunchKernelGGL((k_precompute_mult_affine<typename decltype(cv)::F>), grid, blk, 0, ctx->stream, (const uint4*)ctx->in_aux.p, (u32)n, (u32)base, (uint4*)tab, ws_scr.base);
   });
   HIPCHK(ctx, hipGetLastError());
   rc = lemsm_rhs_witness_device(ctx, curve, ctx->in_s.p, tab, n, base, a_xy, t, init, d_run, out_totals, out_sum, bad_index);
@@ -263,8 +260,7 @@ int lemsm_fraction_sums_device(lemsm_ctx* ctx, int curve, const void* d_num, con
   int rc = check_curve(ctx, curve); if (rc) return rc;
   if (chains == 0) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: chains must be >= 1");
   if (n > (size_t)-1 / 64 || chains > (size_t)-1 / 64 || chains >= ((size_t)1 << 31)) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n or chains too large");
-  ctx->rhs_ms = 0; ctx->rhs_bytes = 32 * (u64)n * ((d_num ? 2 : 1) + (d_out_running ? 1 : 0));
-  ctx->rhs_mults = n ? fs_mults(fs_geom(n, chains), 0) : 0;
+  ctx->rhs_last = LastStats{0, 32 * (u64)n * ((d_num ? 2 : 1) + (d_out_running ? 1 : 0)), n ? fs_mults(fs_geom(n, chains), 0) : 0};
   if (n == 0) { if (out_totals) fs_totals_of_init(init, chains, out_totals); return LEMSM_OK; }
   if (!d_den) return LEMSM_ERR_BAD_ARG;
   if (n >= ((size_t)1 << 40)) return fail(ctx, LEMSM_ERR_BAD_ARG, "fraction sums: n too large");
@@ -294,27 +290,20 @@ int lemsm_fraction_sums(lemsm_ctx* ctx, int curve, const uint64_t* num, const ui
   HIPCHK(ctx, hipSetDevice(ctx->device));
   Arena ar("fs_staged", ctx->opt.ws_canary != 0);
   const size_t o_num = ar.take("numerators", n * 32), o_den = ar.take("denominators", n * 32), o_run = ar.take("running", n * 32);
-  rc = reserve(ctx, ctx->rhs_tab, ar.total() + 256); if (rc) return rc;   // (+ 256 nobody reads)
-  char* b = (char*)ctx->rhs_tab.p;
-  rc = arena_fill(ctx, ar, b, ctx->stream); if (rc) return rc;
-  char* d_num = num ? b + o_num : nullptr; char* d_den = b + o_den; char* d_run = out_running ? b + o_run : nullptr;
+  Workspace ws;
+  rc = ws.open(ctx, std::move(ar), ctx->rhs_tab, ar.total() + 256, ctx->stream); if (rc) return rc;   // (+ 256 nobody reads)
+  char* d_num = num ? ws.at<char>(o_num) : nullptr; char* d_den = ws.at<char>(o_den); char* d_run = out_running ? ws.at<char>(o_run) : nullptr;
   if (num) HIPCHK(ctx, hipMemcpyAsync(d_num, num, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_den, den, n * 32, hipMemcpyHostToDevice, ctx->stream));
   rc = lemsm_fraction_sums_device(ctx, curve, d_num, d_den, n, chains, init, d_run, out_totals, bad_index);
-  if (rc) return arena_done(ctx, ar, b, ctx->stream, rc);
+  if (rc) return ws.done(rc);
   if (out_running) {
     HIPCHK(ctx, hipMemcpyAsync(out_running, d_run, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
-  return arena_done(ctx, ar, b, ctx->stream, LEMSM_OK);
+  return ws.done(LEMSM_OK);
 }
 
-int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) {
-  if (!ctx) return LEMSM_ERR_BAD_ARG;
-  if (ms) *ms = ctx->rhs_ms;
-  if (bytes) *bytes = ctx->rhs_bytes;
-  if (field_mults) *field_mults = ctx->rhs_mults;
-  return LEMSM_OK;
-}
+int lemsm_rhs_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::rhs_last, ms, bytes, field_mults); }
 
 }  // extern "C"

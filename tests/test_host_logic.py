@@ -218,6 +218,19 @@ def test_arena_helper_on_a_host_buffer(tmp_path, sanitize):
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
+def test_timed_run_synchronises_on_every_exit(tmp_path):
+    """the timed section of the witness entries (csrc/timed_run.hpp) alone on a fake stream that fails its n-th call, every n
+    in turn (tests/timed_run_check.cpp, under -fsanitize=address,undefined): the stream has been synchronised whenever the
+    helper returns, the first error is the status, and the success path keeps its order"""
+    import subprocess
+    exe = tmp_path / "timed_run_check"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-o", str(exe), os.path.join(ROOT, "tests", "timed_run_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "timed_run ok" in out.stdout, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
 def test_oracle_c_under_asan_ubsan():
     """the C oracle (test infrastructure) rebuilt with -fsanitize=address,undefined (`make -C oracle asan`) and the golden-vector
     tests of tests/test_oracle_golden.py run against that build in a child interpreter with libasan preloaded"""
