@@ -16,8 +16,12 @@ the C ABI and compares with a reference that is not the library.  The families (
     regfn             RegularFunction::ev against big-integer Horner, L(f) against rhs_ref.L
     lhs_witness       compute_lhs_witness in full: host entry == device entry, the carry, the functions
 Input shapes aim at the rare branches: P next to -P with equal scalars (cancellation), repeated points
-(doubling), identity points, all-equal and tiny scalars, scalars = order-1.  The family of case k is a function
-of (seed, k) alone (case_kinds), so which families a seed reaches can be listed without a GPU."""
+(doubling), identity points, all-equal and tiny scalars, scalars = order-1.  The families that decompose scalars in a
+negabase (lhs, scalar_witness, rhs, lhs_witness) take their usual short list of bases in three cases out of four; in the
+fourth the base is uniform in 3..255 and up to eight scalars of tests/negbase_cases.py (word carries of `q + 1`, mis-estimated
+fp32 quotients) replace random ones (draw_base, edge_picks; the case line names the base and the spliced scalars).
+The family of case k is a function of (seed, k) alone (case_kinds), so which families a seed reaches can be listed without a
+GPU; a mismatch is replayed from its seed and case index."""
 import os
 import sys
 import time
@@ -30,6 +34,7 @@ from halo2_liam_eagen_msm_amd import api   # noqa: E402
 from oracle import cref, pyref             # noqa: E402
 from oracle import divisor as dv           # noqa: E402
 import json                                # noqa: E402
+import negbase_cases                       # noqa: E402
 import rhs_ref                             # noqa: E402
 
 CURVES = [pyref.BN254_G1, pyref.GRUMPKIN]
@@ -121,6 +126,25 @@ def neg_points(curve, pts):
     return out
 
 
+def draw_base(rng, short):
+    """(base, wide): a base of the family's short list, or -- one case out of four -- any base in 3..255"""
+    base = int(rng.choice(short))
+    wide = bool(rng.random() < 0.25)
+    return (int(rng.integers(3, 256)) if wide else base), wide
+
+
+def edge_picks(rng, base, bound, n, signed=False):
+    """up to eight (index, scalar) pairs, indices distinct and below n: members of negbase_cases.carry_family and
+    estimate_family for this base; signed: the carry family's magnitudes, with either sign"""
+    pool = negbase_cases.carry_members(negbase_cases.carry_family(base, bound, rng, negative=signed)) + negbase_cases.estimate_family(base)
+    count = min(n, int(rng.integers(1, 9)))
+    where = rng.choice(n, size=count, replace=False)
+    vals = [pool[int(i)] for i in rng.integers(0, len(pool), count)]
+    if signed:
+        vals = [v if rng.random() < 0.5 else -v for v in vals]
+    return [(int(j), v) for j, v in zip(where, vals)]
+
+
 def make_case(rng, curve):
     n = int(rng.choice([rng.integers(1, 40), rng.integers(40, 3000), rng.integers(3000, 70000), rng.integers(3000, 70000),
                         rng.integers(70000, 1 << 20)]))
@@ -192,7 +216,7 @@ def witness_case(rng, ctx, O, seed, cases):
 
 
 def scalar_witness_case(rng, ctx, seed, cases):
-    base = int(rng.choice([3, 5, 16, 17, 255])); nd = int(rng.integers(1, 60)); lt = int(rng.integers(1, 20))
+    (base, wide), nd, lt = draw_base(rng, [3, 5, 16, 17, 255]), int(rng.integers(1, 60)), int(rng.integers(1, 20))
     vals = [int(rng.integers(0, 1 << 62)) << int(rng.integers(0, 66)) for _ in range(40)]
     vals = [v if rng.random() < 0.7 else -v for v in vals]
     if rng.random() < 0.55:
@@ -211,6 +235,18 @@ def scalar_witness_case(rng, ctx, seed, cases):
                 break
             except pyref.RefPanic:
                 continue
+    def panics(v):
+        try:
+            pyref.prepare_scalar_witness(v, base, nd, lt)
+            return False
+        except pyref.RefPanic:
+            return True
+    if wide:
+        # a batch the reference accepts stays one: only edge scalars it accepts as well are spliced in
+        clean = not any(panics(v) for v in vals)
+        for j, v in edge_picks(rng, base, 1 << 126, len(vals), signed=True):
+            if not (clean and panics(v)):
+                vals[j] = v
     sc = np.frombuffer(b"".join(abs(v).to_bytes(32, "little") for v in vals), np.uint8).reshape(-1, 32)
     neg = np.array([1 if v < 0 else 0 for v in vals], np.uint8)
     first = None; kinds = []
@@ -224,10 +260,10 @@ def scalar_witness_case(rng, ctx, seed, cases):
     try:
         arr = ctx.prepare_scalar_witness_batch(sc, neg, base, nd, lt)
         if first is not None:
-            print("MISMATCH seed=%d case=%d scalar witness: expected %s at %d" % (seed, cases, kinds[first], first), flush=True); sys.exit(1)
+            print("MISMATCH seed=%d case=%d scalar witness base=%d nd=%d lt=%d: expected %s at %d (v=%d)" % (seed, cases, base, nd, lt, kinds[first], first, vals[first]), flush=True); sys.exit(1)
     except (api.TooManyDigits, api.RefIndexOutOfBounds, api.RefArithmeticOverflow) as e:
         if first is None or not isinstance(e, exc[kinds[first]]) or e.index != first:
-            print("MISMATCH seed=%d case=%d scalar witness error %r, expected %s at %s" % (seed, cases, e, None if first is None else kinds[first], first), flush=True); sys.exit(1)
+            print("MISMATCH seed=%d case=%d scalar witness base=%d nd=%d lt=%d: error %r, expected %s at %s" % (seed, cases, base, nd, lt, e, None if first is None else kinds[first], first), flush=True); sys.exit(1)
         return "scalar_witness(panic)"
     for j, v in enumerate(vals):
         for r in range(base):
@@ -287,7 +323,7 @@ def rhs_case(rng, ctx, cs):
     group law); host and device entries agree.  The challenge is drawn until the reference alone meets no zero denominator."""
     curve = CURVES[int(rng.integers(0, 2))]
     p, cid = curve.fp, curve.cid
-    base = int(rng.choice([3, 4, 5, 16, 17, 255]))
+    base, wide = draw_base(rng, [3, 4, 5, 16, 17, 255])
     n = int(rng.choice([0, 1, 2, int(rng.integers(3, 66)), int(rng.integers(66, 700)), int(rng.integers(700, 3000))]))
     n = min(n, 64) if base == 255 else min(n, 12000 // (base - 1))     # Python inversions: two per table row
     nb = base - 1
@@ -305,9 +341,12 @@ def rhs_case(rng, ctx, cs):
         raw[half:2 * half] = neg_points(curve, raw[:half]); scalars[half:2 * half] = scalars[:half]
     elif n and shape == "identity":
         raw[int(rng.integers(0, n))] = 0
+    edges = edge_picks(rng, base, pyref.scalar_bound(curve.order), n) if wide and n else []
+    for j, v in edges:
+        scalars[j] = v
     pts = [curve.raw_to_affine(r.tobytes()) for r in raw]
     init = _rand_fes(sm, nb, p) if rng.random() < 0.5 else None
-    cs.desc = "%s base=%d n=%d shape=%s init=%s" % (curve.name, base, n, shape, init is not None)
+    cs.desc = "%s base=%d n=%d shape=%s init=%s edges=%s" % (curve.name, base, n, shape, init is not None, edges)
     d = pyref.num_digits(curve.order, base)
     table = [rhs_ref.multiples(curve, q, base) for q in pts]
     for _ in range(8):
@@ -458,7 +497,7 @@ def lhs_witness_case(rng, ctx, O, cs):
     g = pyref.GRUMPKIN; p = g.fp
     n = int(rng.choice([1, 2, int(rng.integers(3, 13)), int(rng.integers(13, 41)), int(rng.integers(13, 41)), int(rng.integers(41, 120)),
                         int(rng.integers(120, 301))]))
-    base = int(rng.choice([3, 5, 16]))
+    base, wide = draw_base(rng, [3, 5, 16])
     shape = str(rng.choice(["random", "few_points", "equal_scalars"]))
     sm = pyref.SplitMix64(int(rng.integers(1, 1 << 62)))
     sc = pyref.gen_scalars_half(sm, n, g.order)
@@ -467,7 +506,10 @@ def lhs_witness_case(rng, ctx, O, cs):
         aff = aff[rng.integers(0, min(n, 3), n)].copy()
     elif shape == "equal_scalars":
         sc = [sc[0]] * n
-    cs.desc = "n=%d base=%d shape=%s" % (n, base, shape)
+    edges = edge_picks(rng, base, pyref.scalar_bound(g.order), n) if wide else []
+    for j, v in edges:
+        sc[j] = v
+    cs.desc = "n=%d base=%d shape=%s edges=%s" % (n, base, shape, edges)
     pts = [g.raw_to_affine(r.tobytes()) for r in aff]
     zs = [1 + sm.next256() % (p - 1) for _ in range(n)]
     jac = np.frombuffer(b"".join(g.affine_to_jacobian_raw(q, z) for q, z in zip(pts, zs)), np.uint64).reshape(-1, 12)
@@ -489,7 +531,7 @@ def lhs_witness_case(rng, ctx, O, cs):
         oa, la, ob, lb = (int(v) for v in index[f])
         if (la, lb) != (a.shape[0], b.shape[0]) or not ((flat[oa: oa + la] == a).all() and (flat[ob: ob + lb] == b).all()):
             cs.mismatch("function %d: host and device entries differ" % f)
-    if n <= 40:                                                # (what test_compute_lhs_witness_full_return_value affords)
+    if n <= 40 and n + base <= 56:                             # lists of up to n + base + 1 points (what test_compute_lhs_witness_full_return_value affords)
         _, efns = dv.compute_lhs_witness(O, sc, [O.from_affine(q, z) for q, z in zip(pts, zs)], base)
         for f, (got, exp) in enumerate(zip(fns, efns)):
             if (_from_mont(got[0], p), _from_mont(got[1], p)) != O.normalise(exp):
@@ -580,11 +622,14 @@ def main(secs=None, seed=None, cases=None):
                 exp = cref.best_multiexp(curve.cid, sc, pts, 8)
                 what = "msm"
             else:
-                n = int(rng.integers(1, 3000)); shape = "lhs"; base = int(rng.choice([3, 4, 5, 16, 17, 255]))
+                n = int(rng.integers(1, 3000)); shape = "lhs"; base, wide = draw_base(rng, [3, 4, 5, 16, 17, 255])
                 pts = cref.gen_points(curve.cid, int(rng.integers(1, 1 << 30)), min(n, 50))[rng.integers(0, min(n, 50), n)]
                 sc = cref.gen_scalars(curve.cid, int(rng.integers(1, 1 << 30)), n, half=True)
                 if rng.random() < 0.3:
                     sc[:] = sc[0]
+                edges = edge_picks(rng, base, pyref.scalar_bound(curve.order), n) if wide else []
+                for j, v in edges:
+                    sc[j] = np.frombuffer(v.to_bytes(32, "little"), np.uint8)
                 pj = cref.aff_to_jac(curve.cid, pts)
                 if sharded:
                     ds, dp = ctx.to_device(sc), ctx.to_device(pts)
@@ -593,8 +638,8 @@ def main(secs=None, seed=None, cases=None):
                     got, carries = ctx.lhs_msm(curve.cid, sc, pj, base, True)
                 exp, ecar = cref.lhs_msm(curve.cid, sc, pj, base, True)
                 for i in range(carries.shape[0]):
-                    assert cref.jac_to_canonical(curve.cid, carries[i]) == cref.jac_to_canonical(curve.cid, ecar[i]), ("carry", i, seed, cases, opts)
-                what = "lhs base %d" % base
+                    assert cref.jac_to_canonical(curve.cid, carries[i]) == cref.jac_to_canonical(curve.cid, ecar[i]), ("carry", i, seed, cases, base, edges, opts)
+                what = "lhs base %d edges=%s" % (base, edges)
             ok = cref.jac_to_canonical(curve.cid, np.ascontiguousarray(got, np.uint64)) == cref.jac_to_canonical(curve.cid, exp)
             if not ok:
                 print("MISMATCH seed=%d case=%d %s %s n=%d shape=%s host_entry=%s sharded=%s world=%d opts=%s" % (seed, cases, what, curve.name, n, shape, host_entry, sharded, world, opts), flush=True)

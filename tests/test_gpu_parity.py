@@ -1098,11 +1098,16 @@ def test_negbase_truncation_is_counted(ctx):
     """digits beyond d are dropped like `.take(d)` (src/argument_witness_calc.rs:99); the count of scalars it happened to is exposed"""
     sc = np.zeros((4, 32), np.uint8)
     sc[0, 0] = 1; sc[1, :2] = 255; sc[2, :8] = 255; sc[3, :15] = 255
-    ctx.negbase_decompose_batch(sc, 16, 40)
+    full = ctx.negbase_decompose_batch(sc, 16, 40)
     assert ctx.last_truncated_count() == 0
     digs = ctx.negbase_decompose_batch(sc, 16, 5)
     assert ctx.last_truncated_count() == 2
     assert digs.shape == (4, 5)
+    # 2^64 - 1 and 2^120 - 1 carry `q + 1` across 32-bit words: the digits themselves, whole and truncated
+    vals = [int.from_bytes(r.tobytes(), "little") for r in sc]
+    assert full.tolist() == [pyref.negbase_digits_padded(v, 16, 40) for v in vals]
+    assert digs.tolist() == [pyref.negbase_digits_padded(v, 16, 5) for v in vals]
+    assert np.array_equal(full, cref.negbase_decompose_batch(sc, 16, 40)) and np.array_equal(digs, cref.negbase_decompose_batch(sc, 16, 5))
 
 
 # ------------------------------------------------------------------ multi-GPU entries of the C ABI, rehearsed on one GPU
