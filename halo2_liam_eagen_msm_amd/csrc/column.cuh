@@ -23,6 +23,7 @@
 // Field: bn256::Fr, strict 8 x 32-bit Montgomery arithmetic (field32.cuh), 32-byte elements, 16-byte loads and stores.
 #pragma once
 #include "field32.cuh"
+#include "regfn_eval.cuh"
 
 namespace lemsm {
 namespace col {
@@ -92,15 +93,6 @@ __global__ __launch_bounds__(256) void k_column_a(const uint4* __restrict__ coef
   }
 }
 
-__device__ __forceinline__ void shfl_up_fe(fe& r, const fe& a, u32 off) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = (u32)__shfl_up((int)a.v[i], off, 64);
-}
-__device__ __forceinline__ void bcast_fe(fe& r, const fe& a, int src) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = (u32)__shfl((int)a.v[i], src, 64);
-}
-
 // one wave per G consecutive batches (G = 1 when c_skip > 64); pw[i] = r^i (times R for a canonical column), i < ceil(bs / cskip);
 // rho[k] = (r^F)^k, k <= 64; cells[j cskip + t].  STAGED: G bs <= RLC_LDS_ELEMS.
 template <bool STAGED>
@@ -135,12 +127,12 @@ __global__ __launch_bounds__(64) void k_poly_rlc(const uint4* __restrict__ colum
     }
     for (u32 off = 1; off < clen; off <<= 1) {                    // c_t = sum_{s <= t} rho^(t - s) S_s within the batch
       fe up;
-      shfl_up_fe(up, c, off);
+      rf::shfl_up_fe(up, c, off);
       if (act && tl >= off) { fe rp; F::load(rp, rho + 2 * off); F::mul(up, up, rp); F::add(c, c, up); }
     }
     if (t0 && act) { fe rp; F::load(rp, rho + 2 * (tl + 1)); F::mul(rp, rp, carry); F::add(c, c, rp); }
     if (act) F::store(cells + 2 * ((jb + g) * cskip + t), c);
-    bcast_fe(carry, c, 63);                                       // (read only when another 64 cells follow: lane 63 is then active)
+    rf::shfl_fe(carry, c, 63);                                    // (read only when another 64 cells follow: lane 63 is then active)
   }
 }
 

@@ -65,9 +65,6 @@ __device__ __forceinline__ void st(u32* p, const fe& a) {
 }
 __device__ __forceinline__ bool aff_id(const fe& x, const fe& y) { return F::is_zero(x) && F::is_zero(y); }
 
-// a^-1 by Fermat in the lazy 29-bit field (inv29.cuh)
-__device__ __forceinline__ void inv_fast(fe& r, const fe& a) { inv_lazy<FrParams, Fr29Params>(r, a); }
-
 // line through two affine, non-identity points P = (x1,y1), Q = (x2,y2): lx x + ly y + lz with
 // lx = y1 - y2, ly = x2 - x1, lz = x1 y2 - y1 x2  (linefunc :290-292 with z = 1); all zero iff P == Q.
 __device__ __forceinline__ bool line_through(fe& lx, fe& ly, fe& lz, const fe& x1, const fe& y1, const fe& x2, const fe& y2) {
@@ -905,22 +902,7 @@ __global__ __launch_bounds__(256) void k_pw_prefix(u32* __restrict__ buf, const 
 
 static const u32 DW_RK = 32;     // most roots per thread of k_pw_rootinv (fewer when a level has few roots: a short level is latency, not work)
 __global__ __launch_bounds__(256) void k_pw_rootinv(u32* __restrict__ roots, u32* __restrict__ rpre /* scratch, as long as roots */, u64 count, u32 rk /* roots per thread */) {
-  const u64 t = (u64)blockIdx.x * 256 + threadIdx.x;
-  const u64 r0 = t * rk;
-  if (r0 >= count) return;
-  const u32 m = (u32)min((u64)rk, count - r0);
-  fe run; F::set_one(run);
-  for (u32 j = 0; j < m; j++) {
-    fe v; ld(v, roots + (r0 + j) * 8);
-    st(rpre + (r0 + j) * 8, run);
-    F::mul(run, run, v);
-  }
-  fe inv; inv_fast(inv, run);
-  for (u32 j = m; j-- > 0;) {
-    fe v, pj, o; ld(v, roots + (r0 + j) * 8); ld(pj, rpre + (r0 + j) * 8);
-    F::mul(o, inv, pj); F::mul(inv, inv, v);
-    st(roots + (r0 + j) * 8, o);
-  }
+  rootinv_chunk<F>((uint4*)roots, (uint4*)rpre, count, rk);
 }
 
 __global__ __launch_bounds__(256) void k_pw_apply(u32* __restrict__ buf, const Plan* __restrict__ plan, u32 nnodes, u32 logN, u32 stride /* threads per node */,
@@ -1068,18 +1050,6 @@ __global__ __launch_bounds__(256) void k_lhs_gather(const uint8_t* __restrict__ 
   const uint4* s = table + ((size_t)j * (base - 1) + (dg - 1)) * 4;      // precomputed_points[j][id_by_digit(digit)]  :123
   uint4* o = out + ((size_t)lead + offs[j]) * 4;
   o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3];
-}
-// affine rows (64 B, (0,0) = identity) -> Jacobian rows (96 B, z = 1 in Montgomery form, identity = zeros)
-__global__ __launch_bounds__(256) void k_aff_to_jac(const uint4* __restrict__ aff, u32 n, uint4* __restrict__ jac) {
-  u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint4 a0 = aff[(size_t)i * 4], a1 = aff[(size_t)i * 4 + 1], a2 = aff[(size_t)i * 4 + 2], a3 = aff[(size_t)i * 4 + 3];
-  const bool id = (a0.x | a0.y | a0.z | a0.w | a1.x | a1.y | a1.z | a1.w | a2.x | a2.y | a2.z | a2.w | a3.x | a3.y | a3.z | a3.w) == 0;
-  fe one; F::set_one(one);
-  uint4 z0 = id ? make_uint4(0, 0, 0, 0) : make_uint4(one.v[0], one.v[1], one.v[2], one.v[3]);
-  uint4 z1 = id ? make_uint4(0, 0, 0, 0) : make_uint4(one.v[4], one.v[5], one.v[6], one.v[7]);
-  uint4* o = jac + (size_t)i * 6;
-  o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3; o[4] = z0; o[5] = z1;
 }
 // out[i] = pt for i < count (the `base` copies of -carry, :112-116) ; and single-slot writes
 __global__ __launch_bounds__(256) void k_fill_points(const uint4* __restrict__ pt, u32 count, uint4* __restrict__ out) {

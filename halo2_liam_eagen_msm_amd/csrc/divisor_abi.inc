@@ -696,7 +696,7 @@ static int lhs_witness_core(lemsm_ctx* ctx, int curve, bool on_device, const voi
   uint4* d_jac = ws.at<uint4>(o_jac); uint4* d_tab = ws.at<uint4>(o_tab);
   const uint4* table = d_tab;
   if (n) {
-    if (on_device) hipLaunchKernelGGL(lemsm::dw::k_aff_to_jac, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, d_jac);
+    if (on_device) hipLaunchKernelGGL((k_affine_to_jacobian<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)points, (u32)n, d_jac);
     else HIPCHK(ctx, hipMemcpyAsync(d_jac, points, n * 96, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL((k_precompute_mult_affine<FrDev>), dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const uint4*)d_jac, (u32)n, (u32)base,
                        d_tab, ws.at<char>(o_scr));

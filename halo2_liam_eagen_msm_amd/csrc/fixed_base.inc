@@ -138,10 +138,7 @@ __global__ __launch_bounds__(256) void k_fixed_digits(const uint4* __restrict__ 
     }
     // non-canonical scalars (>= order) contribute nothing and are reported once per base (its k = 0 row); the host
     // turns the smallest virtual index back into the base's index
-    u32 bw = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) { u32 dmy = __builtin_subc(s[w], fa.kadd.order[w], bw, &bw); (void)dmy; }
-    if (valid && !bw) {
+    if (valid && !lt_u256(s, fa.kadd.order)) {
       if (k == 0) { atomicAdd(&err[0], 1u); atomicMax(&err[1], ~j); }
 #pragma unroll
       for (int w = 0; w < 8; w++) s[w] = 0;

@@ -37,4 +37,26 @@ __device__ __forceinline__ void inv_via_lazy(typename F::fe& r, const typename F
   inv_lazy<typename Lazy29Of<F>::P32, typename Lazy29Of<F>::P29>(r, a);
 }
 
+// Montgomery's trick over the rk roots (32-byte elements) a thread of a 256-wide block owns: roots[r] <- 1 / roots[r] at the
+// price of one inv_via_lazy per thread.  The body of dw::k_pw_rootinv and rhs::k_fs_rootinv.
+template <class F>
+__device__ __forceinline__ void rootinv_chunk(uint4* __restrict__ roots, uint4* __restrict__ rpre /* scratch, as long as roots */, u64 count, u32 rk) {
+  typedef typename F::fe fe;
+  const u64 r0 = ((u64)blockIdx.x * 256 + threadIdx.x) * rk;
+  if (r0 >= count) return;
+  const u32 m = (u32)min((u64)rk, count - r0);
+  fe run; F::set_one(run);
+  for (u32 j = 0; j < m; j++) {
+    fe v; F::load(v, roots + 2 * (r0 + j));
+    F::store(rpre + 2 * (r0 + j), run);
+    F::mul(run, run, v);
+  }
+  fe inv; inv_via_lazy<F>(inv, run);
+  for (u32 j = m; j-- > 0;) {
+    fe v, pj, o; F::load(v, roots + 2 * (r0 + j)); F::load(pj, rpre + 2 * (r0 + j));
+    F::mul(o, inv, pj); F::mul(inv, inv, v);
+    F::store(roots + 2 * (r0 + j), o);
+  }
+}
+
 }  // namespace lemsm

@@ -7,7 +7,7 @@
 //   that turns bucket sums into per-window (total, U_0..U_{L-1}) -> host Horner.
 //
 // Reference behaviour being replaced (paths relative to /root/reference):
-//   src/negbase_utils.rs:20-36        negbase_decompose         -> k_negbase_digits
+//   src/negbase_utils.rs:20-36        negbase_decompose         -> NegWalk (negbase.cuh), walked by k_negbase_digits
 //   src/negbase_utils.rs:46-51        id_by_digit (bucket = digit-1, 0 skipped) -> NegDec
 //   src/argument_witness_calc.rs:97   scalar range assert       -> k_negbase_digits (flag)
 //   src/argument_witness_calc.rs:105-127 per-digit sums S_i of the Horner recursion -> buckets
@@ -15,6 +15,7 @@
 #pragma once
 #include "kernels_ec.cuh"
 #include "inv29.cuh"
+#include "negbase.cuh"
 
 namespace lemsm {
 
@@ -67,10 +68,7 @@ __global__ __launch_bounds__(BS) void k_pip_digits(const uint4* __restrict__ sca
       u32 s[8] = {a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y, b[u].z, b[u].w};
       // scalars must be canonical (< order), as PrimeField::to_repr() guarantees; anything else is
       // reported (LEMSM_ERR_SCALAR_OUT_OF_RANGE) and contributes nothing
-      u32 bw = 0;
-#pragma unroll
-      for (int i = 0; i < 8; i++) { u32 dmy = __builtin_subc(s[i], kadd.order[i], bw, &bw); (void)dmy; }
-      if (!bw) {
+      if (!lt_u256(s, kadd.order)) {
         atomicAdd(&err[0], 1u); atomicMax(&err[1], ~j);
 #pragma unroll
         for (int i = 0; i < 8; i++) s[i] = 0;
@@ -640,8 +638,8 @@ __global__ void k_copy_points(const CopyTask* __restrict__ tasks, u32 ntasks, u3
 // ------------------------------------------------------------------------------------
 // negabase decomposition (src/negbase_utils.rs:20-36) of scalars < isqrt(order)+2
 // (range assert of src/argument_witness_calc.rs:97: first offending index -> err[0] via atomicMin).
-// x is held as sign + 128-bit magnitude in 8 x 16-bit half limbs; one step is
-//   digit = x mod B (non-negative), x <- -((x - digit)/B).
+// The recurrence itself is NegWalk (negbase.cuh); a thread walks four words when its magnitude is below 2^128 (every
+// in-range scalar) and eight otherwise (the generic API path, check_range = 0, takes any 256-bit value).
 // Output: digits[j*d + i] (scalar-major, the C ABI layout) and/or digitsT[i*n + j].
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_negbase_digits(const uint4* __restrict__ scalars, u32 n, u32 base, u32 d,
@@ -655,99 +653,27 @@ __global__ __launch_bounds__(256) void k_negbase_digits(const uint4* __restrict_
   u32 j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   uint4 a = scalars[2 * (size_t)j], b = scalars[2 * (size_t)j + 1];
-  u32 s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  // s < bound ?
-  u32 bw = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) { u32 dummy = __builtin_subc(s[i], bound[i], bw, &bw); (void)dummy; }
-  bool in_range = bw != 0;
-  if (check_range && !in_range) { atomicMin(&err[0], j); }
-  // magnitude in 16-bit halves (values beyond 128 bits only occur for out-of-range input; the
-  // generic API path (check_range = 0) handles full 256-bit values with 16 halves)
-  u32 h[16];
-#pragma unroll
-  for (int i = 0; i < 8; i++) { h[2 * i] = s[i] & 0xffffu; h[2 * i + 1] = s[i] >> 16; }
-  bool neg = negative ? negative[j] != 0 : false;
-  {   // -0 is 0
-    u32 nz0 = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) nz0 |= h[k];
-    if (!nz0) neg = false;
-  }
-  const float rb = 1.0f / (float)base;
-  const u32 shift = (base & (base - 1u)) == 0 ? (u32)__builtin_ctz(base) : 0u;
-  // Power-of-two base and a magnitude below 2^128 (every in-range scalar; B = 16 is the bench configuration): the same
-  // recurrence on four 32-bit words -- a funnel shift per word instead of sixteen 16-bit halves, ~4x fewer instructions
-  // (the kernel is ALU-bound: 75 -> ~20 us per 2^20 scalars).  The generic loop below then has nothing left to do.
-  u32 i_begin = 0;
-  if (shift && !(s[4] | s[5] | s[6] | s[7])) {
-    u32 m0 = s[0], m1 = s[1], m2 = s[2], m3 = s[3];
-    for (u32 i = 0; i < d; i++) {
-      const u32 rem = m0 & (base - 1u);
-      m0 = __builtin_amdgcn_alignbit(m1, m0, shift); m1 = __builtin_amdgcn_alignbit(m2, m1, shift);
-      m2 = __builtin_amdgcn_alignbit(m3, m2, shift); m3 >>= shift;
-      u32 digit;
-      if (!neg) { digit = rem; neg = true; }
-      else {
-        digit = rem ? base - rem : 0u;
-        if (rem) {   // |x| <- q + 1
-          m0 += 1u; const u32 c0 = m0 == 0u; m1 += c0; const u32 c1 = c0 & (m1 == 0u); m2 += c1; const u32 c2 = c1 & (m2 == 0u); m3 += c2;
-        }
-        neg = false;
-      }
-      if (!(m0 | m1 | m2 | m3)) neg = false;
+  const u32 s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  if (check_range && !lt_u256(s, bound)) { atomicMin(&err[0], j); }
+  const bool neg = negative ? negative[j] != 0 : false;
+  const NegConsts nc = neg_consts(base);
+  auto walk = [&](auto w) {
+    w.init(s, neg);
+    auto put = [&](u32 i, u32 digit) {
       if (digits) digits[(size_t)j * d + i] = (uint8_t)digit;
       if (digitsT && i >= row_begin && i < row_end) digitsT[(size_t)i * n + j] = (uint8_t)digit;
-    }
-    h[0] = m0 & 0xffffu; h[1] = m0 >> 16; h[2] = m1 & 0xffffu; h[3] = m1 >> 16; h[4] = m2 & 0xffffu; h[5] = m2 >> 16; h[6] = m3 & 0xffffu; h[7] = m3 >> 16;
-    i_begin = d;
-  }
-  for (u32 i = i_begin; i < d; i++) {
-    // (q, rem) = divmod(|x|, base)
-    u32 rem = 0;
-    if (shift) {            // power-of-two base (the bench configuration, B = 16): a 2^shift-bit right shift
-      rem = h[0] & (base - 1u);
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        u32 nxt = k < 15 ? h[k + 1] : 0u;
-        h[k] = ((h[k] | (nxt << 16)) >> shift) & 0xffffu;
-      }
-    } else {                // most significant half first; partial dividends < 2^24 are exact in fp32
-#pragma unroll
-      for (int k = 15; k >= 0; k--) {
-        u32 cur = (rem << 16) | h[k];
-        u32 q = (u32)((float)cur * rb);
-        int r = (int)cur - (int)(q * base);
-        if (r < 0) { q--; r += (int)base; }
-        if (r >= (int)base) { q++; r -= (int)base; }
-        h[k] = q; rem = (u32)r;
-      }
-    }
-    u32 digit;
-    if (!neg) { digit = rem; neg = true; }
-    else {
-      digit = rem ? base - rem : 0u;
-      if (rem) {   // |x| <- q + 1
-        u32 cy = 1;
-#pragma unroll
-        for (int k = 0; k < 16; k++) { u32 v = h[k] + cy; h[k] = v & 0xffffu; cy = v >> 16; }
-      }
-      neg = false;
-    }
-    u32 nz = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) nz |= h[k];
-    if (!nz) neg = false;
-    if (digits) digits[(size_t)j * d + i] = (uint8_t)digit;
-    if (digitsT && i >= row_begin && i < row_end) digitsT[(size_t)i * n + j] = (uint8_t)digit;
-  }
-  // digits beyond d are truncated exactly like chain(repeat(0)).take(d) at
-  // src/argument_witness_calc.rs:99; err[1] counts scalars whose expansion did not fit
-  u32 nz = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++) nz |= h[k];
-  if (nz) { atomicAdd(&err[1], 1u); atomicMin(&err[2], j); }
-  if (trunc) trunc[j] = nz ? 1 : 0;
+    };
+    // one loop per kind of base, so that the test of the kind is outside: the step of a power of two (B = 16 is the bench
+    // configuration) is a dozen instructions, and the kernel is ALU-bound
+    if (nc.shift) for (u32 i = 0; i < d; i++) put(i, w.step(nc));
+    else for (u32 i = 0; i < d; i++) put(i, w.step(nc));
+    // digits beyond d are truncated exactly like chain(repeat(0)).take(d) at
+    // src/argument_witness_calc.rs:99; err[1] counts scalars whose expansion did not fit
+    const bool left = !w.zero();
+    if (left) { atomicAdd(&err[1], 1u); atomicMin(&err[2], j); }
+    if (trunc) trunc[j] = left ? 1 : 0;
+  };
+  if (!(s[4] | s[5] | s[6] | s[7])) walk(NegWalk<4>()); else walk(NegWalk<8>());
 }
 
 // ------------------------------------------------------------------------------------
@@ -888,6 +814,17 @@ __global__ __launch_bounds__(256) void k_jac_to_affine(const uint4* __restrict__
     F::mul(x, x, zi2); F::mul(y, y, zi3);
     F::store(o, x); F::store(o + 2, y);
   }
+}
+
+// the way back: affine rows (64 B, identity = (0, 0)) as Jacobian rows (96 B): Z = 1, identity Z = 0
+template <class F>
+__global__ __launch_bounds__(256) void k_affine_to_jacobian(const uint4* __restrict__ aff, u32 n, uint4* __restrict__ jac) {
+  typedef typename F::fe fe;
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  fe x, y, z; F::load(x, aff + 4 * (size_t)j); F::load(y, aff + 4 * (size_t)j + 2);
+  if (F::is_zero(x) && F::is_zero(y)) F::set_zero(z); else F::set_one(z);
+  F::store(jac + 6 * (size_t)j, x); F::store(jac + 6 * (size_t)j + 2, y); F::store(jac + 6 * (size_t)j + 4, z);
 }
 
 // ------------------------------------------------------------------------------------

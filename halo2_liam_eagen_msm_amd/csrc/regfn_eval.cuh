@@ -47,6 +47,10 @@ __device__ __forceinline__ void shfl_fe(fe& r, const fe& a, int src) {
 #pragma unroll
   for (int i = 0; i < 8; i++) r.v[i] = (u32)__shfl((int)a.v[i], src, 64);
 }
+__device__ __forceinline__ void shfl_up_fe(fe& r, const fe& a, u32 off) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (u32)__shfl_up((int)a.v[i], off, 64);
+}
 __device__ __forceinline__ void wave_sum(fe& a) {   // lane 0 ends with the sum over the wave, always in this order
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {

@@ -25,6 +25,7 @@
 #pragma once
 #include "field32.cuh"
 #include "inv29.cuh"
+#include "negbase.cuh"
 
 namespace lemsm {
 namespace rhs {
@@ -55,19 +56,14 @@ struct ArraySrc {
 
 struct RhsConsts { u32 ax[8], t[8], f[8], bound[8]; };   // Ax, t, f = t Ax - Ay (raw Montgomery); isqrt(order) + 2
 
-// (q, r) = divmod(cur, base) for cur < 2^24 (exact in fp32; the estimate is off by at most one)
-__device__ __forceinline__ void divmod24(u32 cur, u32 base, float rb, u32& q, u32& r) {
-  q = (u32)((float)cur * rb);
-  int rr = (int)cur - (int)(q * base);
-  if (rr < 0) { q--; rr += (int)base; }
-  if (rr >= (int)base) { q++; rr -= (int)base; }
-  r = (u32)rr;
-}
-
-// term (j, k): the bucket straight from the scalar -- the negabase recurrence of k_negbase_digits (src/negbase_utils.rs:20-36)
-// on four 32-bit words in registers, the powers (-base)^i of the positions whose digit is k added up as 160-bit two's
-// complement integers (|bucket| < base^d < 2^144), one conversion into Montgomery form -- then one product each for the
-// denominator and for bucket (x - Ax).
+// term (j, k): the bucket straight from the scalar -- the negabase recurrence (src/negbase_utils.rs:20-36) on four 32-bit
+// words in registers, the powers (-base)^i of the positions whose digit is k added up as 160-bit two's complement integers
+// (|bucket| < base^d < 2^144), one conversion into Montgomery form -- then one product each for the denominator and for
+// bucket (x - Ax).
+// The loop below is NegWalk<4>::step of negbase.cuh written out, the second text of the recurrence on the device: through
+// NegWalk the same steps compiled to another register allocation of the whole kernel and lemsm_rhs_witness_device measured
+// 2 % slower at 2^20 (profiles/negbase_shared/NOTES.md).  A change to NegWalk::step belongs here as well;
+// tests/test_gpu_negbase_edges.py aims the same inputs at both.
 template <class F, class P>
 struct RhsSrc {
   typedef typename F::fe fe;
@@ -82,10 +78,7 @@ struct RhsSrc {
     const u32 k = (u32)(i - j * nb) + 1u;
     const uint4 a = scalars[2 * j], b = scalars[2 * j + 1];
     const u32 s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    u32 bw = 0;
-#pragma unroll
-    for (int l = 0; l < 8; l++) (void)__builtin_subc(s[l], c.bound[l], bw, &bw);
-    if (!bw) { atomicMin(&err[1], (ErrWord)j); return true; }   // assert!(&x < &sq_p), src/argument_witness_calc.rs:97
+    if (!lt_u256(s, c.bound)) { atomicMin(&err[1], (ErrWord)j); return true; }   // assert!(&x < &sq_p), src/argument_witness_calc.rs:97
     u32 m0 = s[0], m1 = s[1], m2 = s[2], m3 = s[3];            // |x| < 2^128 for every in-range scalar
     bool neg = false;
     u32 acc[5] = {0, 0, 0, 0, 0};
@@ -165,22 +158,7 @@ __global__ __launch_bounds__(256) void k_fs_prefix(Src src, u64 N, uint4* __rest
 
 template <class F>
 __global__ __launch_bounds__(256) void k_fs_rootinv(uint4* __restrict__ roots, uint4* __restrict__ rpre /* scratch, as long as roots */, u64 count, u32 rk) {
-  typedef typename F::fe fe;
-  const u64 r0 = ((u64)blockIdx.x * 256 + threadIdx.x) * rk;
-  if (r0 >= count) return;
-  const u32 m = (u32)min((u64)rk, count - r0);
-  fe run; F::set_one(run);
-  for (u32 j = 0; j < m; j++) {
-    fe v; F::load(v, roots + 2 * (r0 + j));
-    F::store(rpre + 2 * (r0 + j), run);
-    F::mul(run, run, v);
-  }
-  fe inv; inv_via_lazy<F>(inv, run);
-  for (u32 j = m; j-- > 0;) {
-    fe v, pj, o; F::load(v, roots + 2 * (r0 + j)); F::load(pj, rpre + 2 * (r0 + j));
-    F::mul(o, inv, pj); F::mul(inv, inv, v);
-    F::store(roots + 2 * (r0 + j), o);
-  }
+  rootinv_chunk<F>(roots, rpre, count, rk);
 }
 
 template <class F>
@@ -256,17 +234,6 @@ __global__ __launch_bounds__(256) void k_fs_finish(const uint4* __restrict__ ter
   fe run; F::load(run, segoff + 2 * g);
   u64 i = seg * S * chains + c;
   for (u64 r = 0; r < S && i < N; r++, i += chains) { fe v; F::load(v, terms + 2 * i); F::add(run, run, v); F::store(out + 2 * i, run); }
-}
-
-// affine rows (64 B, identity = (0, 0)) as the Jacobian rows k_precompute_mult_affine reads: Z = 1, identity Z = 0
-template <class F>
-__global__ __launch_bounds__(256) void k_affine_to_jacobian(const uint4* __restrict__ aff, u32 n, uint4* __restrict__ jac) {
-  typedef typename F::fe fe;
-  const u32 j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  fe x, y, z; F::load(x, aff + 4 * (size_t)j); F::load(y, aff + 4 * (size_t)j + 2);
-  if (F::is_zero(x) && F::is_zero(y)) F::set_zero(z); else F::set_one(z);
-  F::store(jac + 6 * (size_t)j, x); F::store(jac + 6 * (size_t)j + 2, y); F::store(jac + 6 * (size_t)j + 4, z);
 }
 
 }  // namespace rhs

@@ -184,7 +184,7 @@ int lemsm_multiples_table_device(lemsm_ctx* ctx, int curve, const void* d_points
   const dim3 grid((u32)((n + 255) / 256)), blk(256);
   with_curve(curve, [&](auto cv) {
     typedef typename decltype(cv)::F F;
-    hipLaunchKernelGGL((fs::k_affine_to_jacobian<F>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
+    hipLaunchKernelGGL((k_affine_to_jacobian<F>), grid, blk, 0, ctx->stream, (const uint4*)d_points_affine, (u32)n, (uint4*)b);
     hipLaunchKernelGGL((k_precompute_mult_affine<F>), grid, blk, 0, ctx->stream, (const uint4*)b, (u32)n, (u32)base, (uint4*)d_out_table, b + in_bytes);
   });
   HIPCHK(ctx, hipGetLastError());

@@ -1,8 +1,9 @@
 """Inputs that steer the device kernels' negabase recurrence into its rare branches, and a CPU model of that recurrence
 (test infrastructure; plain Python and numpy, no GPU).
 
-The recurrence of src/negbase_utils.rs:20-36 is restated twice on the device with multi-word arithmetic: k_negbase_digits
-(csrc/kernels.cuh) and rhs::RhsSrc::get (csrc/rhs.cuh).  Per step both do
+The recurrence of src/negbase_utils.rs:20-36 is restated twice on the device with multi-word arithmetic: NegWalk
+(csrc/negbase.cuh), which k_negbase_digits (csrc/kernels.cuh) walks on four or eight words, and the loop of rhs::RhsSrc::get
+(csrc/rhs.cuh), NegWalk<4>'s steps written out.  Per step both do
     (q, rem) = divmod(|x|, base)         base a power of two: a funnel shift over 32-bit words,
                                          otherwise: sixteen-bit halves, most significant first, each partial dividend
                                          cur = rem << 16 | half < base << 16 divided through the fp32 estimate
@@ -246,7 +247,7 @@ def pattern_extremes(base, d, bound):
 
 
 def wide_family(rng, bases=WIDE_BASES, randoms=300):
-    """256-bit values for the generic entry (any magnitude, sixteen halves): 2^256 - 1, 2^128, 2^128 - 1, 2^255,
+    """256-bit values for the generic entry (any magnitude, eight words): 2^256 - 1, 2^128, 2^128 - 1, 2^255,
     (2^(16 k) - 1) << 4 for k = 1..15 (ripples across the halves), for every base of `bases` (2^(32 w) - 1) base^j + rem above
     2^128 and the carry family of eight words (the `+ 1` rippling into each of the words 1..7), and `randoms` random values."""
     vals = {(1 << 256) - 1, 1 << 128, (1 << 128) - 1, 1 << 255}

@@ -1,9 +1,10 @@
-"""The two device copies of the negabase recurrence (k_negbase_digits in csrc/kernels.cuh, rhs::RhsSrc::get in csrc/rhs.cuh) on
-the inputs of tests/negbase_cases.py: scalars on which the `|x| <- q + 1` carry ripples across one, two and three 32-bit
-words, partial dividends whose fp32 quotient estimate is off by one in either direction, extreme digit patterns, and
-full-width 256-bit magnitudes -- at every base 2..255 for the digits, at chosen bases through the lhs, rhs and scalar-witness
-entries.  Every expectation is an exact integer from oracle/pyref.py, oracle/cref.py or tests/rhs_ref.py.
-tests/test_negbase_cases.py shows on a CPU model that each family makes a kernel without the part it aims at give a wrong digit."""
+"""The two device texts of the negabase recurrence (NegWalk in csrc/negbase.cuh, which k_negbase_digits walks, and the loop of
+rhs::RhsSrc::get in csrc/rhs.cuh) on the inputs of tests/negbase_cases.py: scalars on which the `|x| <- q + 1` carry ripples
+across one, two and three 32-bit words, partial dividends whose fp32 quotient estimate is off by one in either direction,
+extreme digit patterns, and full-width 256-bit magnitudes -- at every base 2..255 for the digits, at chosen bases through the
+lhs, rhs and scalar-witness entries.  Every expectation is an exact integer from oracle/pyref.py, oracle/cref.py or
+tests/rhs_ref.py.  tests/test_negbase_cases.py shows on a CPU model that each family makes a kernel without the part it aims
+at give a wrong digit."""
 import math
 
 import numpy as np
@@ -48,8 +49,8 @@ def wide():
 
 @pytest.mark.parametrize("base", nc.WIDE_BASES)
 def test_full_width_magnitudes(ctx, wide, base):
-    """any 256-bit value (the generic entry checks no range): the power-of-two path above 2^128 and the sixteen-half division
-    with non-zero high halves; with d five digits short of that the digits are the oracle's first d and the truncations are counted"""
+    """any 256-bit value (the generic entry checks no range): the power-of-two path above 2^128 and the division on eight
+    words with non-zero high words; with d five digits short of that the digits are the oracle's first d and the truncations are counted"""
     vals, sc = wide
     full = len(pyref.negbase_decompose((1 << 256) - 1, base)) + 2
     exp = [pyref.negbase_decompose(v, base) for v in vals]
@@ -61,6 +62,26 @@ def test_full_width_magnitudes(ctx, wide, base):
         for j, e in enumerate(exp):
             assert got[j].tolist() == (e + [0] * d)[:d], (base, d, vals[j])
     assert sum(len(e) > full - 5 for e in exp) > 0
+
+
+@pytest.mark.parametrize("base", [16, 5, 221])
+def test_neighbouring_lanes_of_both_widths(ctx, base):
+    """the width of the walk is chosen per thread at every base: n = 128 with even lanes below 2^128 (four words) and odd lanes
+    at or above it (eight words) -- 2^128 itself, 2^256 - 1, the four-word and eight-word carry families, then twenty
+    random values each -- in one call with every digit (d = the length of 2^256 - 1, the longest there is, + 2): the oracle's
+    digits, nothing truncated"""
+    rng = pyref.SplitMix64(12800 + base)
+    low = [0, (1 << 128) - 1] + nc.carry_members(nc.carry_family(base, 1 << 128, rng))
+    high = [1 << 128, (1 << 256) - 1] + [v for v in nc.carry_members(nc.carry_family(base, 1 << 256, rng, words=8)) if v >> 128]
+    low = low[:44] + [nc._bits(rng, 128) for _ in range(20)]
+    high = high[:44] + [nc._bits(rng, 256) | 1 << 255 for _ in range(20)]
+    vals = [v for pair in zip(low, high) for v in pair]
+    assert len(vals) == 128 and all((v >> 128 != 0) == (j % 2 == 1) for j, v in enumerate(vals))
+    d = len(pyref.negbase_decompose((1 << 256) - 1, base)) + 2
+    got = ctx.negbase_decompose_batch(nc.to_bytes(vals), base, d)
+    assert ctx.last_truncated_count() == 0
+    for j, v in enumerate(vals):
+        assert got[j].tolist() == pyref.negbase_digits_padded(v, base, d), (base, v)
 
 
 # ---- 3. lhs -----------------------------------------------------------------------------------------------------------------

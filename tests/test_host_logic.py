@@ -243,3 +243,45 @@ def test_oracle_c_under_asan_ubsan():
                           "-k", "not asan"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-3000:]
+
+
+def test_negbase_walk_under_asan_ubsan(tmp_path):
+    """the device's negabase recurrence (csrc/negbase.cuh: the statements k_negbase_digits runs) compiled for
+    the host with -fsanitize=address,undefined (tests/negbase_walk_check.cpp) on the inputs of tests/negbase_cases.py: the
+    carry, estimate and pattern families at every base 2..255 on four and on eight words, the signed carry families at four
+    bases, and the full-width family with all its digits and five digits short; every line against oracle/pyref.py"""
+    import subprocess
+    import negbase_cases as nc
+    exe = tmp_path / "negbase_walk_check"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-o", str(exe), os.path.join(ROOT, "tests", "negbase_walk_check.cpp")])
+    G = pyref.GRUMPKIN
+    bound = pyref.scalar_bound(G.order)
+    cases = []                                              # (words, base, d, signed value)
+    for base in range(2, 256):
+        d = pyref.num_digits(G.order, base) + 2
+        fam = sorted(set().union(*nc.families(base, d, bound, pyref.SplitMix64(base))))
+        cases += [(w, base, d, s) for w in (4, 8) for s in fam]
+    for base in (16, 5, 41, 221):
+        d = pyref.num_digits(G.order, base) + 2
+        mags = nc.carry_members(nc.carry_family(base, 1 << 126, pyref.SplitMix64(5000 + base), negative=True))
+        assert mags
+        cases += [(w, base, d, v) for w in (4, 8) for m in mags for v in (-m, m)]
+    wide = nc.wide_family(pyref.SplitMix64(2256))
+    for base in nc.WIDE_BASES:
+        full = len(pyref.negbase_decompose((1 << 256) - 1, base)) + 2
+        cases += [(8, base, d, v) for d in (full, full - 5) for v in wide]
+    text = "".join("%d %d %d %d %x\n" % (w, base, d, v < 0, abs(v)) for w, base, d, v in cases)
+    out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-3000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(cases)
+    truncated = 0
+    for (w, base, d, v), line in zip(cases, lines):
+        exp = pyref.negbase_decompose(v, base)
+        got = [int(t) for t in line.split()]
+        assert got[:-1] == (exp + [0] * d)[:d], (w, base, d, v)
+        assert got[-1] == (len(exp) > d), (w, base, d, v)
+        truncated += got[-1]
+    assert truncated > 0

@@ -51,7 +51,7 @@ def test_model_equals_the_oracles_at_full_width():
             run = nc.model_words(s, base, d, carry_words=7, words=8)
             assert run.digits == want == exp[j].tolist(), (base, s)
             depth = max(depth, run.depth)
-        assert depth == 7, base                    # the `+ 1` ripples through all sixteen halves
+        assert depth == 7, base                    # the `+ 1` ripples through all eight words
 
 
 @split
