@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     RefDivisionByZero, regfn_eval_plan, regular_function_ev, regular_function_ev_unchecked,
     regfn_logderiv_plan, argument_residual, compute_lhs_logderiv,
     column_plan, assemble_column_a, compute_poly_rlc,
+    fft_plan, omega_pow, omega_pow_inv, half_pow, best_fft, kate_division, eval_polynomial, polynomial_mul,
 )

@@ -67,6 +67,8 @@ SYMBOLS = [
     "lemsm_rhs_plan", "lemsm_multiples_table_device", "lemsm_rhs_witness_device", "lemsm_rhs_witness",
     "lemsm_fraction_sums_device", "lemsm_fraction_sums", "lemsm_rhs_last",
     "lemsm_column_plan", "lemsm_column_a_device", "lemsm_column_a", "lemsm_poly_rlc_device", "lemsm_poly_rlc", "lemsm_column_last",
+    "lemsm_fft_omega", "lemsm_fft_half_pow", "lemsm_fft_plan", "lemsm_fft_device", "lemsm_fft",
+    "lemsm_kate_division_device", "lemsm_kate_division", "lemsm_poly_mul_device", "lemsm_poly_mul", "lemsm_poly_last",
 ]
 
 
@@ -206,6 +208,16 @@ def load() -> ctypes.CDLL:
         "lemsm_poly_rlc_device": (i, [vp, i, vp, i, sz, sz, sz, sz, u64p, vp, sz]),
         "lemsm_poly_rlc": (i, [vp, i, u64p, i, sz, sz, sz, sz, u64p, u64p, sz]),
         "lemsm_column_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_fft_omega": (i, [ctypes.c_uint32, i, u64p]),
+        "lemsm_fft_half_pow": (i, [ctypes.c_uint64, u64p]),
+        "lemsm_fft_plan": (i, [ctypes.c_uint32, sz, u32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_fft_device": (i, [vp, vp, sz, ctypes.c_uint32, u64p, u64p]),
+        "lemsm_fft": (i, [vp, u64p, u64p, sz, ctypes.c_uint32, u64p, u64p]),
+        "lemsm_kate_division_device": (i, [vp, vp, sz, vp, sz, u64p, vp, sz, szp]),
+        "lemsm_kate_division": (i, [vp, u64p, sz, vp, sz, u64p, u64p, sz, szp]),
+        "lemsm_poly_mul_device": (i, [vp, vp, sz, vp, sz, vp, sz, szp]),
+        "lemsm_poly_mul": (i, [vp, u64p, sz, u64p, sz, u64p, sz, szp]),
+        "lemsm_poly_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -761,6 +761,77 @@ class Context:
         self._check(self.lib.lemsm_column_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- halo2::arithmetic on resident data: best_fft, kate_division, the Polynomial product ----
+    def fft_device(self, d_data: int, nseq: int, logn: int, omega, scale=None):
+        """halo2's best_fft (src/regular_functions_utils.rs:119-124) in place on nseq sequences of 2^logn elements (32 B, raw
+        Montgomery) at device pointer d_data, natural order in and out: a[k] <- scale sum_j a[j] omega^(j k).  omega: a
+        primitive 2^logn-th root of unity (4 limbs; its inverse gives the inverse transform); scale: None (unscaled, as
+        best_fft) or 4 limbs (half_pow(logn) for 1/n)."""
+        w = np.ascontiguousarray(omega, np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.uint64).reshape(4)
+        self._check(self.lib.lemsm_fft_device(self.h, d_data, nseq, logn, _ptr(w), _ptr(sc) if sc is not None else None))
+
+    def fft(self, data, logn: int, omega, scale=None) -> np.ndarray:
+        """the same for host data ((nseq 2^logn, 4) uint64): returns the transforms"""
+        a = _limbs(data, 4)
+        if a.shape[0] == 0 or a.shape[0] % (1 << logn):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the data is not a whole number of sequences of 2^logn elements")
+        w = np.ascontiguousarray(omega, np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.uint64).reshape(4)
+        out = np.zeros_like(a)
+        self._check(self.lib.lemsm_fft(self.h, _ptr(a), _ptr(out), a.shape[0] >> logn, logn, _ptr(w), _ptr(sc) if sc is not None else None))
+        return out
+
+    def kate_division_device(self, d_in: int, cap_in: int, index, b, d_out: int, cap_out: int):
+        """Polynomial::kate_div / halo2 kate_division (:45-47) of the rows `index` ((T, 2) {offset, len} in elements of the
+        cap_in coefficients at device pointer d_in) by (x - b): the quotient of row t (len - 1 coefficients) goes to the
+        same offset of d_out (cap_out elements, not overlapping d_in).  A row of length 0: RefArithmeticOverflow (.index)."""
+        index = np.ascontiguousarray(index, np.uintp).reshape(-1, 2)
+        bb = np.ascontiguousarray(b, np.uint64).reshape(4)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_kate_division_device(self.h, d_in, cap_in, _ptr(index) if index.size else None, index.shape[0], _ptr(bb),
+                                                 d_out, cap_out, ctypes.byref(bad))
+        self._check(rc, bad.value)
+
+    def kate_division(self, polys, b):
+        """the same for polys = [coefficient array (len, 4), ...] in host memory: the list of quotients ((len - 1, 4) each)"""
+        parts = [_limbs(p, 4) if np.size(p) else np.zeros((0, 4), np.uint64) for p in polys]
+        rows, used = [], 0
+        for p in parts:
+            rows.append((used, p.shape[0])); used += p.shape[0]
+        coeffs = np.concatenate(parts) if used else np.zeros((0, 4), np.uint64)
+        index = np.array(rows, np.uintp).reshape(-1, 2)
+        bb = np.ascontiguousarray(b, np.uint64).reshape(4)
+        out = np.zeros((max(used, 1), 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_kate_division(self.h, _ptr(coeffs) if used else None, used, _ptr(index) if index.size else None, index.shape[0],
+                                          _ptr(bb), _ptr(out), out.shape[0], ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return [out[o:o + n - 1].copy() for o, n in rows]
+
+    def poly_mul_device(self, d_a: int, la: int, d_b: int, lb: int, d_out: int, cap_out: int) -> int:
+        """&p * &q (:209-216) of la and lb coefficients at device pointers d_a and d_b into d_out (cap_out elements, not
+        overlapping the operands): returns the product's length la + lb - 1.  Two empty operands: RefArithmeticOverflow."""
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.lemsm_poly_mul_device(self.h, d_a, la, d_b, lb, d_out, cap_out, ctypes.byref(n)))
+        return n.value
+
+    def poly_mul(self, p, q) -> np.ndarray:
+        """the same for coefficient arrays in host memory: (la + lb - 1, 4) uint64"""
+        a = _limbs(p, 4) if np.size(p) else np.zeros((0, 4), np.uint64)
+        b = _limbs(q, 4) if np.size(q) else np.zeros((0, 4), np.uint64)
+        la, lb = a.shape[0], b.shape[0]
+        out = np.zeros((max(la + lb - 1, 1), 4), np.uint64)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.lemsm_poly_mul(self.h, _ptr(a) if la else None, la, _ptr(b) if lb else None, lb, _ptr(out), out.shape[0], ctypes.byref(n)))
+        return out[:n.value]
+
+    def poly_last(self) -> Tuple[float, int, int]:
+        """(device ms, bytes, field_mults) of the last fft* / kate_division* / poly_mul* call"""
+        ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_poly_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
+        return ms.value, by.value, fm.value
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -1283,6 +1354,72 @@ def regular_function_ev_unchecked(fn, x, y, curve="grumpkin", ctx: Optional[Cont
     Montgomery limbs each), no on-curve test; 4 raw Montgomery limbs"""
     pt = np.concatenate([np.asarray(x, np.uint64).reshape(4), np.asarray(y, np.uint64).reshape(4)]).reshape(1, 8)
     return (ctx or default_context()).regfn_eval(curve, [fn], pt, None, False)[0]
+
+
+def fft_plan(logn: int, nseq: int = 1) -> dict:
+    """the price of nseq transforms of 2^logn elements (pure host: lemsm_fft_plan): {"passes", "bytes",
+    "butterflies"}; raises LemsmError (LEMSM_ERR_BAD_ARG) where the transform entries would"""
+    lib = _lib.load()
+    ps = ctypes.c_uint32(); by = ctypes.c_uint64(); bf = ctypes.c_uint64()
+    rc = lib.lemsm_fft_plan(logn, nseq, ctypes.byref(ps), ctypes.byref(by), ctypes.byref(bf))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"passes": ps.value, "bytes": by.value, "butterflies": bf.value}
+
+
+def _fft_const(fn, *args) -> np.ndarray:
+    out = np.zeros(4, np.uint64)
+    rc = fn(*args, _ptr(out))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, _lib.load().lemsm_strerror(rc).decode())
+    return out
+
+
+def omega_pow(exp: int) -> np.ndarray:
+    """FftPrecomp::omega_pow (src/regular_functions_utils.rs:20): ROOT_OF_UNITY^(2^exp), the generator of the 2^(28 - exp)-th
+    roots of unity, exp 0 .. 28; 4 raw Montgomery limbs"""
+    if not 0 <= exp <= 28:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "omega_pow: exp 0 .. 28")
+    return _fft_const(_lib.load().lemsm_fft_omega, 28 - exp, 0)
+
+
+def omega_pow_inv(exp: int) -> np.ndarray:
+    """FftPrecomp::omega_pow_inv (:21): the inverse of omega_pow(exp)"""
+    if not 0 <= exp <= 28:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "omega_pow_inv: exp 0 .. 28")
+    return _fft_const(_lib.load().lemsm_fft_omega, 28 - exp, 1)
+
+
+def half_pow(exp: int) -> np.ndarray:
+    """FftPrecomp::half_pow (:22): 2^-exp, exp < 64"""
+    if exp < 0:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "half_pow: exp 0 .. 63")
+    return _fft_const(_lib.load().lemsm_fft_half_pow, exp)
+
+
+def best_fft(a, omega, log_n: int, ctx: Optional[Context] = None) -> np.ndarray:
+    """halo2 arithmetic::best_fft(a, omega, log_n) (called at src/regular_functions_utils.rs:119-124), unscaled; returns the
+    transform of a ((2^log_n, 4) raw Montgomery limbs) instead of working in place"""
+    return (ctx or default_context()).fft(a, log_n, omega)
+
+
+def kate_division(a, b, ctx: Optional[Context] = None) -> np.ndarray:
+    """halo2 arithmetic::kate_division(a, b) (Polynomial::kate_div, :45-47): the quotient of a(x) by (x - b), (len - 1, 4);
+    RefArithmeticOverflow for an empty a"""
+    return (ctx or default_context()).kate_division([a], b)[0]
+
+
+def eval_polynomial(poly, x, ctx: Optional[Context] = None) -> np.ndarray:
+    """halo2 arithmetic::eval_polynomial(poly, x) (Polynomial::ev, :41-43): the regular-function evaluation with an empty b
+    part; 4 raw Montgomery limbs"""
+    pt = np.concatenate([np.asarray(x, np.uint64).reshape(4), np.zeros(4, np.uint64)]).reshape(1, 8)
+    return (ctx or default_context()).regfn_eval("grumpkin", [(poly, np.zeros((0, 4), np.uint64))], pt, None, False)[0]
+
+
+def polynomial_mul(p, q, ctx: Optional[Context] = None) -> np.ndarray:
+    """&p * &q of the reference's Polynomial (impl Mul, :209-216): (la + lb - 1, 4); RefArithmeticOverflow for two empty
+    operands (:55)"""
+    return (ctx or default_context()).poly_mul(p, q)
 
 
 def _neg_affine_raw(curve_id: int, pts: np.ndarray) -> np.ndarray:

@@ -28,6 +28,7 @@
 #include "regfn_logderiv.cuh"
 #include "rhs.cuh"
 #include "column.cuh"
+#include "poly.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -155,6 +156,9 @@ struct lemsm_ctx {
   LastStats rhs_last;                // lemsm_rhs_last
   DevBuf col_ws, col_stage;          // column a / poly rlc: function and power tables, staged inputs + outputs (host entries)
   LastStats col_last;                // lemsm_column_last
+  DevBuf poly_ws, poly_stage, poly_tab;   // fft / kate_division / poly_mul: call workspace, staged arrays (host entries), the twiddle table omega^t
+  host::fe poly_tab_omega = {{0, 0, 0, 0}}; u32 poly_tab_logn = 0; bool poly_tab_valid = false;   // ... which holds t < 2^(poly_tab_logn - 1) of this omega
+  LastStats poly_last;               // lemsm_poly_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
   int plan_world = 1;   // ranks sharing the current call's windows: > 1 pins 16-bit windows (16 split evenly over 2/4/8 ranks, 15 do not)
@@ -1820,7 +1824,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);
@@ -2725,3 +2729,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "regfn_logderiv_abi.inc"
 #include "rhs_abi.inc"
 #include "column_abi.inc"
+#include "poly_abi.inc"

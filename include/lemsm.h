@@ -577,6 +577,60 @@ int lemsm_poly_rlc(lemsm_ctx* ctx, int curve, const uint64_t* column, int form, 
    and the bytes (read + written) and field multiplications its plan prices it with.  (src/config.rs:246-283) */
 int lemsm_column_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
 
+/* ---- halo2::arithmetic on resident data: best_fft, kate_division, the Polynomial product -------------------------------
+   (src/regular_functions_utils.rs:5 imports best_fft, best_multiexp, eval_polynomial, kate_division) --------- */
+/* Everything here is over bn256::Fr (Grumpkin's base field, the scalar field of BN254 G1, the one FftPrecomp field:
+   src/precomputed_fft_data.rs:3); an element is 32 bytes, 4 raw Montgomery limbs, as for every other cell entry.  The
+   entries keep the conventions of the witness entries: a capacity that is too small is LEMSM_ERR_BAD_ARG with the lengths
+   set, the output untouched and nothing left queued; a field argument that is not canonical is LEMSM_ERR_BAD_ARG; sums run
+   in a fixed order, so the host entry, the device entry and repeated calls give the same bytes; option ws_canary guards
+   every carved workspace.
+   eval_polynomial (:42, Polynomial::ev) has no entry of its own: lemsm_regfn_eval_device with index rows
+   {offset, len, 0, 0} (an empty b part) and affine points (x, anything) is Polynomial::ev at x. */
+/* The FftPrecomp trait (:17-24), pure host.  omega: omega_pow(28 - logn), or omega_pow_inv(28 - logn) with inverse != 0:
+   the generator of the 2^logn-th roots of unity the reference uses (logn 0 .. 28; more: LEMSM_ERR_BAD_ARG). */
+int lemsm_fft_omega(uint32_t logn, int inverse, uint64_t out[4]);
+/* half_pow(exp) = 2^-exp (:22; exp < 64, the length of the reference's table; more: LEMSM_ERR_BAD_ARG) */
+int lemsm_fft_half_pow(uint64_t exp, uint64_t out[4]);
+/* Pure host: prices nseq transforms of 2^logn elements.  logn 0 .. 26, nseq >= 1, nseq << logn <= 2^28 (else
+   LEMSM_ERR_BAD_ARG).  passes = the LDS-tiled passes over HBM (one of up to 10 stages, then one per 8 stages more) plus one
+   for the reordering; bytes = 64 (nseq << logn) passes; butterflies = nseq logn 2^(logn-1), one field product each.
+   (halo2 best_fft, called at :119-124) */
+int lemsm_fft_plan(uint32_t logn, size_t nseq, uint32_t* passes, uint64_t* bytes, uint64_t* butterflies);
+/* halo2's best_fft(a, omega, log_n) (:119-124), in place on nseq sequences of 2^logn elements resident at d_data, natural
+   order in and out: a[k] <- scale sum_j a[j] omega^(j k).  scale == NULL: unscaled, as best_fft leaves it; otherwise the
+   factor is folded into the reordering pass (mul_fft's half_pow, an inverse transform's 1/n).  omega must be a primitive
+   2^logn-th root of unity (omega^(2^(logn-1)) == -1; omega == 1 for logn 0), else LEMSM_ERR_BAD_ARG: an inverse transform
+   is the same call with omega^-1.  The table omega^t, t < 2^(logn-1) (32 B 2^(logn-1): 1 GB at 2^26) is kept in the
+   context for the next call with the same (omega, logn); no memory for it: LEMSM_ERR_NOMEM. */
+int lemsm_fft_device(lemsm_ctx* ctx, void* d_data, size_t nseq, uint32_t logn, const uint64_t omega[4], const uint64_t* scale);
+/* The same with host arrays (uploaded, the device path, downloaded); in == out is allowed.  (best_fft, :119-124) */
+int lemsm_fft(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, const uint64_t omega[4], const uint64_t* scale);
+/* Polynomial::kate_div (:45-47), halo2's kate_division(a, b): the quotient of a(x) by (x - b), remainder dropped, of T rows
+   that share b (the two parts of a RegularFunction in merge, :357).  index: T x 2 rows {offset, len} in elements of d_in;
+   the quotient of row t lies at the same offset of d_out and has len - 1 coefficients: q[len-2] = a[len-1],
+   q[i] = a[i+1] + b q[i+1].  A row of length 1 gives an empty row.  A row of length 0 is the reference's vec![0; len - 1]
+   underflow: LEMSM_ERR_ARITH_OVERFLOW, the row in *bad_index (optional), nothing written.  A row reaching past cap_in, a
+   quotient reaching past cap_out, two rows that overlap, or d_out overlapping d_in (the byte ranges of the two
+   capacities): LEMSM_ERR_BAD_ARG, nothing written. */
+int lemsm_kate_division_device(lemsm_ctx* ctx, const void* d_in, size_t cap_in, const size_t* index, size_t T, const uint64_t b[4],
+                               void* d_out, size_t cap_out, size_t* bad_index);
+/* The same with host arrays; only the quotient rows of `out` are written.  (:45-47) */
+int lemsm_kate_division(lemsm_ctx* ctx, const uint64_t* in, size_t cap_in, const size_t* index, size_t T, const uint64_t b[4],
+                        uint64_t* out, size_t cap_out, size_t* bad_index);
+/* &p * &q (impl Mul, :209-216) of la and lb coefficients resident in HBM: *len_out = la + lb - 1 coefficients at d_out.
+   la == lb == 0 is the usize underflow of :55: LEMSM_ERR_ARITH_OVERFLOW.  Exactly one empty operand: la + lb - 1 zeros,
+   what mul_naive returns.  la + lb - 1 > 2^26, or cap_out too small (then *len_out is set and the output untouched), or
+   the product's bytes overlapping an operand: LEMSM_ERR_BAD_ARG.  The arithmetic is exact, so which of the reference's two
+   algorithms ran does not show in the bits: an operand of fewer than 32 coefficients takes the direct kernel (mul_naive,
+   :54-62), anything else two forward transforms, one pointwise pass and one inverse transform (mul_fft, :102-129). */
+int lemsm_poly_mul_device(lemsm_ctx* ctx, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t cap_out, size_t* len_out);
+/* The same with host arrays.  (:209-216) */
+int lemsm_poly_mul(lemsm_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* out, size_t cap_out, size_t* len_out);
+/* Device time (ms, HIP events around the launches on the context's stream) of the last lemsm_fft* / lemsm_kate_division* /
+   lemsm_poly_mul* call, and the bytes and field multiplications it is priced at.  (:45-47, :102-129, :209-216) */
+int lemsm_poly_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
