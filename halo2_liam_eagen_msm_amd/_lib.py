@@ -31,6 +31,8 @@ LEMSM_ERR_DIVISION_BY_ZERO = 14
 LEMSM_COMM_ID_BYTES = 128
 LEMSM_FORM_MONTGOMERY = 0
 LEMSM_FORM_CANONICAL = 1
+LEMSM_EXT_INTERLEAVED = 0
+LEMSM_EXT_COSET_MAJOR = 1
 
 BN254_G1 = 0
 GRUMPKIN = 1
@@ -69,6 +71,8 @@ SYMBOLS = [
     "lemsm_column_plan", "lemsm_column_a_device", "lemsm_column_a", "lemsm_poly_rlc_device", "lemsm_poly_rlc", "lemsm_column_last",
     "lemsm_fft_omega", "lemsm_fft_half_pow", "lemsm_fft_plan", "lemsm_fft_device", "lemsm_fft",
     "lemsm_kate_division_device", "lemsm_kate_division", "lemsm_poly_mul_device", "lemsm_poly_mul", "lemsm_poly_last",
+    "lemsm_domain_plan", "lemsm_vanishing_on_cosets", "lemsm_coset_fft_device", "lemsm_coset_ifft_device", "lemsm_coset_fft", "lemsm_coset_ifft",
+    "lemsm_coeff_to_extended_device", "lemsm_extended_to_coeff_device", "lemsm_coeff_to_extended", "lemsm_extended_to_coeff",
 ]
 
 
@@ -218,6 +222,16 @@ def load() -> ctypes.CDLL:
         "lemsm_poly_mul_device": (i, [vp, vp, sz, vp, sz, vp, sz, szp]),
         "lemsm_poly_mul": (i, [vp, u64p, sz, u64p, sz, u64p, sz, szp]),
         "lemsm_poly_last": (i, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_domain_plan": (i, [ctypes.c_uint32, ctypes.c_uint32, sz, u32p] + [ctypes.POINTER(ctypes.c_uint64)] * 3),
+        "lemsm_vanishing_on_cosets": (i, [ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]),
+        "lemsm_coset_fft_device": (i, [vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p]),
+        "lemsm_coset_ifft_device": (i, [vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p]),
+        "lemsm_coset_fft": (i, [vp, u64p, u64p, sz, ctypes.c_uint32, u64p, u64p, u64p]),
+        "lemsm_coset_ifft": (i, [vp, u64p, u64p, sz, ctypes.c_uint32, u64p, u64p, u64p]),
+        "lemsm_coeff_to_extended_device": (i, [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, u64p, i, vp, sz]),
+        "lemsm_extended_to_coeff_device": (i, [vp, vp, ctypes.c_uint32, ctypes.c_uint32, u64p, i, i, i, vp, sz, szp]),
+        "lemsm_coeff_to_extended": (i, [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32, u64p, i, u64p, sz]),
+        "lemsm_extended_to_coeff": (i, [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, u64p, i, i, i, u64p, sz, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -29,6 +29,7 @@ import numpy as np
 from . import _lib
 from ._lib import BN254_G1, GRUMPKIN
 from ._lib import LEMSM_FORM_CANONICAL as FORM_CANONICAL, LEMSM_FORM_MONTGOMERY as FORM_MONTGOMERY
+from ._lib import LEMSM_EXT_COSET_MAJOR as EXT_COSET_MAJOR, LEMSM_EXT_INTERLEAVED as EXT_INTERLEAVED
 
 ORDER = {
     BN254_G1: 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
@@ -832,6 +833,86 @@ class Context:
         self._check(self.lib.lemsm_poly_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- halo2's EvaluationDomain on resident data: coset and extended-domain transforms ----
+    def _coset_args(self, omega, shift, scale):
+        w = np.ascontiguousarray(omega, np.uint64).reshape(4)
+        g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.uint64).reshape(4)
+        return w, g, sc
+
+    def coset_fft_device(self, d_data: int, nseq: int, logn: int, omega, shift, scale=None):
+        """a[k] <- scale sum_j a[j] shift^j omega^(j k), in place on nseq sequences of 2^logn elements at device pointer d_data:
+        the values on the coset shift <omega>.  shift: any non-zero element (4 limbs); shift = 1 is fft_device."""
+        w, g, sc = self._coset_args(omega, shift, scale)
+        self._check(self.lib.lemsm_coset_fft_device(self.h, d_data, nseq, logn, _ptr(w), _ptr(g), _ptr(sc) if sc is not None else None))
+
+    def coset_ifft_device(self, d_data: int, nseq: int, logn: int, omega_inv, shift_inv, scale=None):
+        """a[j] <- scale shift_inv^j sum_k a[k] omega_inv^(j k): the inverse of coset_fft_device with omega^-1, shift^-1 and
+        scale = half_pow(logn)"""
+        w, g, sc = self._coset_args(omega_inv, shift_inv, scale)
+        self._check(self.lib.lemsm_coset_ifft_device(self.h, d_data, nseq, logn, _ptr(w), _ptr(g), _ptr(sc) if sc is not None else None))
+
+    def _coset_host(self, fn, data, logn, omega, shift, scale):
+        a = _limbs(data, 4)
+        if a.shape[0] == 0 or a.shape[0] % (1 << logn):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the data is not a whole number of sequences of 2^logn elements")
+        w, g, sc = self._coset_args(omega, shift, scale)
+        out = np.zeros_like(a)
+        self._check(fn(self.h, _ptr(a), _ptr(out), a.shape[0] >> logn, logn, _ptr(w), _ptr(g), _ptr(sc) if sc is not None else None))
+        return out
+
+    def coset_fft(self, data, logn: int, omega, shift, scale=None) -> np.ndarray:
+        """coset_fft_device for host data ((nseq 2^logn, 4) uint64): returns the transforms"""
+        return self._coset_host(self.lib.lemsm_coset_fft, data, logn, omega, shift, scale)
+
+    def coset_ifft(self, data, logn: int, omega_inv, shift_inv, scale=None) -> np.ndarray:
+        """coset_ifft_device for host data"""
+        return self._coset_host(self.lib.lemsm_coset_ifft, data, logn, omega_inv, shift_inv, scale)
+
+    def coeff_to_extended_device(self, d_coeffs: int, n_coeffs: int, logn: int, logm: int, shift, d_out: int, cap_out: int,
+                                 layout: int = _lib.LEMSM_EXT_INTERLEAVED):
+        """EvaluationDomain::coeff_to_extended: the values of the n_coeffs <= 2^(logn + logm) coefficients at device pointer
+        d_coeffs at the points shift w_ext^c w^r (c < 2^logm, r < 2^logn) into d_out (cap_out >= 2^(logn + logm) elements, no
+        overlap), at element c + 2^logm r (EXT_INTERLEAVED, halo2's order) or c 2^logn + r (EXT_COSET_MAJOR)"""
+        g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+        self._check(self.lib.lemsm_coeff_to_extended_device(self.h, d_coeffs, n_coeffs, logn, logm, _ptr(g), layout, d_out, cap_out))
+
+    def extended_to_coeff_device(self, d_evals: int, logn: int, logm: int, shift, d_out: int, n_out: int, layout: int = _lib.LEMSM_EXT_INTERLEAVED,
+                                 divide_vanishing: bool = False, form: int = _lib.LEMSM_FORM_MONTGOMERY):
+        """EvaluationDomain::extended_to_coeff (with divide_by_vanishing_poly folded in when divide_vanishing): the first n_out
+        coefficients of the polynomial with the 2^(logn + logm) values at d_evals, into d_out in `form`.  RefDivisionByZero
+        (.index = the coset) when X^n - 1 vanishes on a coset."""
+        g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_extended_to_coeff_device(self.h, d_evals, logn, logm, _ptr(g), layout, int(bool(divide_vanishing)), form, d_out, n_out,
+                                                     ctypes.byref(bad))
+        self._check(rc, bad.value)
+
+    def coeff_to_extended(self, coeffs, logn: int, logm: int, shift, layout: int = _lib.LEMSM_EXT_INTERLEAVED) -> np.ndarray:
+        """coeff_to_extended_device for a coefficient array in host memory: (2^(logn + logm), 4) uint64"""
+        a = _limbs(coeffs, 4) if np.size(coeffs) else np.zeros((0, 4), np.uint64)
+        g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+        N = 1 << (logn + logm)
+        out = np.zeros((N, 4), np.uint64)
+        self._check(self.lib.lemsm_coeff_to_extended(self.h, _ptr(a) if a.shape[0] else None, a.shape[0], logn, logm, _ptr(g), layout, _ptr(out), N))
+        return out
+
+    def extended_to_coeff(self, evals, logn: int, logm: int, shift, n_out: Optional[int] = None, layout: int = _lib.LEMSM_EXT_INTERLEAVED,
+                          divide_vanishing: bool = False, form: int = _lib.LEMSM_FORM_MONTGOMERY) -> np.ndarray:
+        """extended_to_coeff_device for values in host memory ((2^(logn + logm), 4) uint64): (n_out, 4), n_out = all by default"""
+        e = _limbs(evals, 4)
+        N = 1 << (logn + logm)
+        if e.shape[0] != N:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the values are not 2^(logn + logm) elements")
+        n_out = N if n_out is None else n_out
+        g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+        out = np.zeros((max(n_out, 1), 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_extended_to_coeff(self.h, _ptr(e), logn, logm, _ptr(g), layout, int(bool(divide_vanishing)), form, _ptr(out), n_out,
+                                              ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out[:n_out]
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -1395,6 +1476,33 @@ def half_pow(exp: int) -> np.ndarray:
     if exp < 0:
         raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "half_pow: exp 0 .. 63")
     return _fft_const(_lib.load().lemsm_fft_half_pow, exp)
+
+
+def domain_plan(logn: int, logm: int, n_coeffs: Optional[int] = None) -> dict:
+    """the price of one coeff_to_extended_device call in the coset-major layout (pure host: lemsm_domain_plan):
+    {"passes", "bytes", "field_mults", "workspace_bytes"}; n_coeffs = 2^logn by default (halo2's call); raises LemsmError
+    (LEMSM_ERR_BAD_ARG) where the entry would"""
+    lib = _lib.load()
+    ps = ctypes.c_uint32(); by = ctypes.c_uint64(); fm = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_domain_plan(logn, logm, (1 << logn) if n_coeffs is None else n_coeffs, ctypes.byref(ps), ctypes.byref(by), ctypes.byref(fm),
+                               ctypes.byref(wb))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"passes": ps.value, "bytes": by.value, "field_mults": fm.value, "workspace_bytes": wb.value}
+
+
+def vanishing_on_cosets(logn: int, logm: int, shift) -> np.ndarray:
+    """t_c = (shift w_ext^c)^(2^logn) - 1, c < 2^logm: the value of X^n - 1 on every coset of the extended domain, (2^logm, 4)
+    raw Montgomery limbs, zeros included (pure host: lemsm_vanishing_on_cosets)"""
+    if not 0 <= logm <= 4:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "vanishing_on_cosets: logm 0 .. 4")
+    lib = _lib.load()
+    g = np.ascontiguousarray(shift, np.uint64).reshape(4)
+    out = np.zeros((1 << logm, 4), np.uint64)
+    rc = lib.lemsm_vanishing_on_cosets(logn, logm, _ptr(g), _ptr(out))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return out
 
 
 def best_fft(a, omega, log_n: int, ctx: Optional[Context] = None) -> np.ndarray:

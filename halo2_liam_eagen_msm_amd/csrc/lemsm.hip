@@ -29,6 +29,7 @@
 #include "rhs.cuh"
 #include "column.cuh"
 #include "poly.cuh"
+#include "domain.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -2730,3 +2731,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "rhs_abi.inc"
 #include "column_abi.inc"
 #include "poly_abi.inc"
+#include "domain_abi.inc"

@@ -631,6 +631,62 @@ int lemsm_poly_mul(lemsm_ctx* ctx, const uint64_t* a, size_t la, const uint64_t*
    lemsm_poly_mul* call, and the bytes and field multiplications it is priced at.  (:45-47, :102-129, :209-216) */
 int lemsm_poly_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
 
+/* ---- halo2's EvaluationDomain on resident data: coset and extended-domain transforms ---------------------
+   bn256::Fr, 32-byte raw Montgomery elements, the conventions of the entries above (LEMSM_ERR_BAD_ARG leaves nothing
+   queued and the outputs untouched; the figures of every call go to lemsm_poly_last).
+   n = 2^logn, m = 2^logm, N = m n; w_ext = lemsm_fft_omega(logn + logm), w = w_ext^m = lemsm_fft_omega(logn),
+   theta = w_ext^n; shift = g, any non-zero field element (halo2 passes F::ZETA); s_c = g w_ext^c generates coset c < m
+   and t_c = s_c^n - 1 = g^n theta^c - 1 is the value of X^n - 1 on it.  The point with halo2's index e = c + m r is
+   s_c w^r; `layout` says where its value lies.  Limits: logn <= 26, logm <= 4, logn + logm <= 28 (the 2-adicity of the
+   field).  The mapping to halo2_proofs' poly/domain.rs is stated from memory; the formulas here are the contract. */
+enum {
+  LEMSM_EXT_INTERLEAVED = 0,   /* at element c + m r: halo2's ExtendedLagrangeCoeff order */
+  LEMSM_EXT_COSET_MAJOR = 1    /* at element c n + r: a rotation is an index shift inside one coset */
+};
+/* Pure host: the price of one lemsm_coeff_to_extended_device call in the coset-major layout: passes over HBM (the spread,
+   the tiled transform passes, the reorder), their bytes, the field products (butterflies, powers, the fold of
+   coefficients past n) and the workspace bytes the call reserves.  The interleaved layout (logm > 0) and
+   lemsm_extended_to_coeff_device reserve 32 N bytes more (the m sequences cannot stand in the caller's buffer); the
+   latter runs the same passes plus the combine.  A limit exceeded or n_coeffs > N: LEMSM_ERR_BAD_ARG. */
+int lemsm_domain_plan(uint32_t logn, uint32_t logm, size_t n_coeffs, uint32_t* passes, uint64_t* bytes, uint64_t* field_mults,
+                      uint64_t* workspace_bytes);
+/* Pure host, no context: out_t[c] = t_c, c < m, raw Montgomery limbs, zeros included (t_c == 0: coset c is the domain
+   itself and lemsm_extended_to_coeff* cannot divide there).  shift zero or not canonical: LEMSM_ERR_BAD_ARG. */
+int lemsm_vanishing_on_cosets(uint32_t logn, uint32_t logm, const uint64_t shift[4], uint64_t* out_t);
+/* a[k] <- scale sum_j a[j] shift^j omega^(j k): the values on the coset shift <omega>, in place on nseq sequences, natural
+   order in and out; omega and scale as lemsm_fft_device, nseq << logn <= 2^28.  shift == 1 gives the bytes of
+   lemsm_fft_device.  The powers cost one more pass over the data (at most 3 products an element). */
+int lemsm_coset_fft_device(lemsm_ctx* ctx, void* d_data, size_t nseq, uint32_t logn, const uint64_t omega[4], const uint64_t shift[4],
+                           const uint64_t* scale);
+/* a[j] <- scale shift_inv^j sum_k a[k] omega_inv^(j k): the inverse of the above with omega^-1, shift^-1 and scale = 1/n
+   (lemsm_fft_half_pow(logn)); the powers ride on the reordering pass. */
+int lemsm_coset_ifft_device(lemsm_ctx* ctx, void* d_data, size_t nseq, uint32_t logn, const uint64_t omega_inv[4], const uint64_t shift_inv[4],
+                            const uint64_t* scale);
+/* The same with host arrays (uploaded, the device path, downloaded); in == out is allowed. */
+int lemsm_coset_fft(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, const uint64_t omega[4], const uint64_t shift[4],
+                    const uint64_t* scale);
+int lemsm_coset_ifft(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, const uint64_t omega_inv[4],
+                     const uint64_t shift_inv[4], const uint64_t* scale);
+/* EvaluationDomain::coeff_to_extended over a caller-chosen coset generator: P = sum_{j < n_coeffs} a[j] X^j, n_coeffs <= N
+   (halo2 calls it with n; 0 gives zeros); writes P(s_c w^r) for all c < m, r < n to d_out (cap_out >= N elements, no
+   overlap with d_coeffs) in `layout`.  m transforms of n elements over the size-n table, so N may be 2^28 where one
+   transform stops at 2^26.  logm = 0 with shift = 1 is the plain transform. */
+int lemsm_coeff_to_extended_device(lemsm_ctx* ctx, const void* d_coeffs, size_t n_coeffs, uint32_t logn, uint32_t logm, const uint64_t shift[4],
+                                   int layout, void* d_out, size_t cap_out);
+/* EvaluationDomain::extended_to_coeff, the exact inverse of the above for every polynomial of degree < N: from the N values
+   at d_evals (in `layout`; with divide_vanishing != 0 each first divided by t_c: divide_by_vanishing_poly) the first
+   n_out <= N coefficients to d_out (no overlap with d_evals) in `form`: LEMSM_FORM_MONTGOMERY, or LEMSM_FORM_CANONICAL, the
+   scalars lemsm_msm_device takes.  Coefficients from n_out on are not written and not checked (halo2's truncation to
+   n quotient_poly_degree).  divide_vanishing with some t_c == 0 (g = 1, for example): LEMSM_ERR_DIVISION_BY_ZERO with c in
+   *bad_index (optional) and lemsm_last_bad_index, nothing written. */
+int lemsm_extended_to_coeff_device(lemsm_ctx* ctx, const void* d_evals, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
+                                   int divide_vanishing, int form, void* d_out, size_t n_out, size_t* bad_index);
+/* The same two with host arrays. */
+int lemsm_coeff_to_extended(lemsm_ctx* ctx, const uint64_t* coeffs, size_t n_coeffs, uint32_t logn, uint32_t logm, const uint64_t shift[4],
+                            int layout, uint64_t* out, size_t cap_out);
+int lemsm_extended_to_coeff(lemsm_ctx* ctx, const uint64_t* evals, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
+                            int divide_vanishing, int form, uint64_t* out, size_t n_out, size_t* bad_index);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
