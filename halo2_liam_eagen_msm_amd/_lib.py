@@ -73,7 +73,27 @@ SYMBOLS = [
     "lemsm_kate_division_device", "lemsm_kate_division", "lemsm_poly_mul_device", "lemsm_poly_mul", "lemsm_poly_last",
     "lemsm_domain_plan", "lemsm_vanishing_on_cosets", "lemsm_coset_fft_device", "lemsm_coset_ifft_device", "lemsm_coset_fft", "lemsm_coset_ifft",
     "lemsm_coeff_to_extended_device", "lemsm_extended_to_coeff_device", "lemsm_coeff_to_extended", "lemsm_extended_to_coeff",
+    "lemsm_gate_plan", "lemsm_gate_eval_device", "lemsm_gate_eval",
 ]
+
+
+class GateQuery(ctypes.Structure):
+    """lemsm_gate_query"""
+    _fields_ = [("column", ctypes.c_int32), ("rotation", ctypes.c_int32)]
+
+
+class GateProgram(ctypes.Structure):
+    """lemsm_gate_program"""
+    _fields_ = [("code", ctypes.c_void_p), ("n_code", ctypes.c_size_t), ("queries", ctypes.c_void_p), ("n_queries", ctypes.c_size_t),
+                ("consts", ctypes.c_void_p), ("n_consts", ctypes.c_size_t)]
+
+
+# the opcodes of a gate program's code words (low 8 bits; operand = word >> 8)
+GATE_OPS = ("PUSH_CELL", "PUSH_CONST", "PUSH_X", "ADD", "SUB", "MUL", "NEG", "ADD_CELL", "SUB_CELL", "MUL_CELL",
+            "ADD_CONST", "SUB_CONST", "MUL_CONST", "FOLD")
+(LEMSM_GATE_PUSH_CELL, LEMSM_GATE_PUSH_CONST, LEMSM_GATE_PUSH_X, LEMSM_GATE_ADD, LEMSM_GATE_SUB, LEMSM_GATE_MUL, LEMSM_GATE_NEG,
+ LEMSM_GATE_ADD_CELL, LEMSM_GATE_SUB_CELL, LEMSM_GATE_MUL_CELL, LEMSM_GATE_ADD_CONST, LEMSM_GATE_SUB_CONST, LEMSM_GATE_MUL_CONST,
+ LEMSM_GATE_FOLD) = range(14)
 
 
 def build(force: bool = False) -> str:
@@ -232,6 +252,9 @@ def load() -> ctypes.CDLL:
         "lemsm_extended_to_coeff_device": (i, [vp, vp, ctypes.c_uint32, ctypes.c_uint32, u64p, i, i, i, vp, sz, szp]),
         "lemsm_coeff_to_extended": (i, [vp, u64p, sz, ctypes.c_uint32, ctypes.c_uint32, u64p, i, u64p, sz]),
         "lemsm_extended_to_coeff": (i, [vp, u64p, ctypes.c_uint32, ctypes.c_uint32, u64p, i, i, i, u64p, sz, szp]),
+        "lemsm_gate_plan": (i, [ctypes.POINTER(GateProgram), sz, u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), szp]),
+        "lemsm_gate_eval_device": (i, [vp, ctypes.POINTER(GateProgram), vp, sz] + [ctypes.c_uint32] * 4 + [u64p, u64p, vp, sz, szp]),
+        "lemsm_gate_eval": (i, [vp, ctypes.POINTER(GateProgram), vp, sz] + [ctypes.c_uint32] * 4 + [u64p, u64p, u64p, sz, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -913,6 +913,43 @@ class Context:
         self._check(rc, bad.value)
         return out[:n_out]
 
+    # ---- gate expressions on the extended domain: the numerator of the quotient h ----
+    def _gate_args(self, prog, logm, y, shift, coset_begin, coset_count):
+        yy = np.ascontiguousarray(y, np.uint64).reshape(4)
+        g = None if shift is None else np.ascontiguousarray(shift, np.uint64).reshape(4)
+        return yy, g, (1 << logm) - coset_begin if coset_count is None else coset_count
+
+    def gate_eval_device(self, prog: "GateProgram", d_columns: Sequence[int], logn: int, logm: int, d_out: int, cap_out: int, y, shift=None,
+                         coset_begin: int = 0, coset_count: Optional[int] = None):
+        """h <- h y + gate, gate by gate (halo2's evaluate_h over the custom gates, src/config.rs:232-568), of the compiled
+        program `prog` at the points of cosets coset_begin .. coset_begin + coset_count - 1 (all from coset_begin by default) of
+        the extended domain: d_columns are device pointers to 2^(logn + logm) elements each in EXT_COSET_MAJOR, the values go to
+        the same elements of d_out (cap_out >= 2^(logn + logm), no overlap with a column).  y and shift: 4 raw Montgomery limbs;
+        shift (the g of coeff_to_extended_device) is needed only when the program uses X()."""
+        yy, g, count = self._gate_args(prog, logm, y, shift, coset_begin, coset_count)
+        cols = (ctypes.c_void_p * max(len(d_columns), 1))(*[int(c) for c in d_columns])
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_gate_eval_device(self.h, ctypes.byref(prog.struct()), cols, len(d_columns), logn, logm, coset_begin, count,
+                                             _ptr(g) if g is not None else None, _ptr(yy), d_out, cap_out, ctypes.byref(bad))
+        self._check(rc, bad.value)
+
+    def gate_eval(self, prog: "GateProgram", columns, logn: int, logm: int, y, shift=None, coset_begin: int = 0,
+                  coset_count: Optional[int] = None) -> np.ndarray:
+        """gate_eval_device for columns in host memory ((2^(logn + logm), 4) uint64 each, coset-major): the values of the
+        range's cosets, (coset_count 2^logn, 4)"""
+        N, n = 1 << (logn + logm), 1 << logn
+        cols = [_limbs(c, 4) for c in columns]
+        if any(c.shape[0] != N for c in cols):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "a column is not 2^(logn + logm) elements")
+        yy, g, count = self._gate_args(prog, logm, y, shift, coset_begin, coset_count)
+        ptrs = (ctypes.c_void_p * max(len(cols), 1))(*[_ptr(c) for c in cols])
+        out = np.zeros((N, 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_gate_eval(self.h, ctypes.byref(prog.struct()), ptrs, len(cols), logn, logm, coset_begin, count,
+                                      _ptr(g) if g is not None else None, _ptr(yy), _ptr(out), N, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out[coset_begin * n:(coset_begin + count) * n].copy()
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -1503,6 +1540,186 @@ def vanishing_on_cosets(logn: int, logm: int, shift) -> np.ndarray:
     if rc != _lib.LEMSM_OK:
         raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
     return out
+
+
+# ---- gate expressions: a small builder and its compiler to the program lemsm_gate_eval* runs ----
+FR_MODULUS = ORDER[BN254_G1]             # bn256::Fr, the field of every cell
+
+
+class BadGateProgram(LemsmError, ValueError):
+    """lemsm_gate_plan refused a program; .index: the instruction (or constant) it names, None for a limit exceeded"""
+
+    def __init__(self, status, msg, index):
+        super().__init__(status, msg)
+        self.index = index
+
+
+class Expr:
+    """a polynomial expression over cells, constants and the point X, in the manner of halo2's Expression
+    (src/config.rs:232-568 build theirs with +, -, * and unary -)"""
+
+    def __add__(self, o): return Add(self, _expr(o))
+    def __radd__(self, o): return Add(_expr(o), self)
+    def __sub__(self, o): return Sub(self, _expr(o))
+    def __rsub__(self, o): return Sub(_expr(o), self)
+    def __mul__(self, o): return Mul(self, _expr(o))
+    def __rmul__(self, o): return Mul(_expr(o), self)
+    def __neg__(self): return Neg(self)
+
+
+class Cell(Expr):
+    """meta.query_*(column, Rotation(rotation)): the column's value `rotation` rows on (mod n)"""
+
+    def __init__(self, column: int, rotation: int = 0):
+        self.column, self.rotation = int(column), int(rotation)
+
+
+class Const(Expr):
+    """a field constant (an integer in standard form, reduced mod r); a challenge is a constant of one call"""
+
+    def __init__(self, v: int):
+        self.value = int(v) % FR_MODULUS
+
+
+class X(Expr):
+    """the point of the extended domain itself"""
+
+
+class _Binary(Expr):
+    def __init__(self, a: Expr, b: Expr):
+        self.a, self.b = a, b
+
+
+class Add(_Binary):
+    pass
+
+
+class Sub(_Binary):
+    pass
+
+
+class Mul(_Binary):
+    pass
+
+
+class Neg(Expr):
+    def __init__(self, a: Expr):
+        self.a = a
+
+
+def _expr(o) -> Expr:
+    if isinstance(o, Expr):
+        return o
+    if isinstance(o, (int, np.integer)):
+        return Const(o)
+    raise TypeError(f"not a gate expression: {o!r}")
+
+
+class GateProgram:
+    """a compiled gate program: .code (uint32 words), .queries ((n, 2) int32 {column, rotation}, deduplicated), .consts
+    ((n, 4) uint64 raw Montgomery, deduplicated), .ncols (the least column count it can run over) and .plan, the figures
+    of gate_plan (None when built with plan=False)"""
+
+    def __init__(self, code, queries, consts, plan: bool = True):
+        self.code = np.ascontiguousarray(code, np.uint32).reshape(-1)
+        self.queries = np.ascontiguousarray(queries, np.int32).reshape(-1, 2)
+        self.consts = np.ascontiguousarray(consts, np.uint64).reshape(-1, 4)
+        self.ncols = int(self.queries[:, 0].max()) + 1 if self.queries.shape[0] else 0
+        self.plan = gate_plan(self, self.ncols) if plan else None
+
+    def struct(self) -> "_lib.GateProgram":
+        """the lemsm_gate_program over this object's arrays (which must outlive it)"""
+        return _lib.GateProgram(_ptr(self.code) if self.code.size else None, self.code.size,
+                                _ptr(self.queries) if self.queries.size else None, self.queries.shape[0],
+                                _ptr(self.consts) if self.consts.size else None, self.consts.shape[0])
+
+
+def gate_plan(prog: GateProgram, ncols: Optional[int] = None) -> dict:
+    """the validator and the per-point price of a program (pure host: lemsm_gate_plan): {"stack_depth", "folds", "degree",
+    "field_mults_per_point", "cell_loads_per_point"}; BadGateProgram (.index) where the program is refused"""
+    lib = _lib.load()
+    sd = ctypes.c_uint32(); fo = ctypes.c_uint32(); dg = ctypes.c_uint32(); fm = ctypes.c_uint64(); cl = ctypes.c_uint64()
+    untouched = ctypes.c_size_t(-1).value
+    bad = ctypes.c_size_t(untouched)
+    rc = lib.lemsm_gate_plan(ctypes.byref(prog.struct()), prog.ncols if ncols is None else ncols, ctypes.byref(sd), ctypes.byref(fo),
+                             ctypes.byref(dg), ctypes.byref(fm), ctypes.byref(cl), ctypes.byref(bad))
+    if rc != _lib.LEMSM_OK:
+        raise BadGateProgram(rc, lib.lemsm_strerror(rc).decode(), None if bad.value == untouched else bad.value)
+    return {"stack_depth": sd.value, "folds": fo.value, "degree": dg.value, "field_mults_per_point": fm.value,
+            "cell_loads_per_point": cl.value}
+
+
+def compile_gates(exprs: Sequence[Expr]) -> GateProgram:
+    """The postfix program of the gates `exprs`, one FOLD behind each: h = (..(g_0 y + g_1) y + ..) y + g_last.
+    An operand that is a cell or a constant rides on its operator (the *_CELL / *_CONST forms; a leaf on the left of a
+    subtraction as (b - a) then NEG); of two subtrees the one that needs the deeper stack is evaluated first (for a
+    subtraction with the operands exchanged and a NEG behind it), which keeps the stack at the expression's Strahler
+    number; queries and constants are deduplicated."""
+    op = {n: k for k, n in enumerate(_lib.GATE_OPS)}
+    code: List[int] = []
+    queries: dict = {}
+    consts: dict = {}
+    need_memo: dict = {}
+
+    def operand(e):
+        if isinstance(e, Cell):
+            return "CELL", queries.setdefault((e.column, e.rotation), len(queries))
+        return "CONST", consts.setdefault(e.value, len(consts))
+
+    def fusable(e):
+        return isinstance(e, (Cell, Const))
+
+    def need(e):
+        k = id(e)
+        if k not in need_memo:
+            if isinstance(e, Neg):
+                v = need(e.a)
+            elif isinstance(e, _Binary):
+                if fusable(e.b):
+                    v = need(e.a)
+                elif fusable(e.a):
+                    v = need(e.b)
+                else:
+                    lo, hi = sorted((need(e.a), need(e.b)))
+                    v = max(hi, lo + 1)
+            else:
+                v = 1
+            need_memo[k] = v
+        return need_memo[k]
+
+    def emit(e):
+        if isinstance(e, X):
+            code.append(op["PUSH_X"])
+        elif fusable(e):
+            kind, k = operand(e)
+            code.append(op["PUSH_" + kind] | k << 8)
+        elif isinstance(e, Neg):
+            emit(e.a)
+            code.append(op["NEG"])
+        elif isinstance(e, _Binary):
+            name = {Add: "ADD", Sub: "SUB", Mul: "MUL"}[type(e)]
+            a, b = e.a, e.b
+            swapped = not fusable(b) and (fusable(a) or need(b) > need(a))
+            if swapped:
+                a, b = b, a
+            emit(a)
+            if fusable(b):
+                kind, k = operand(b)
+                code.append(op[name + "_" + kind] | k << 8)
+            else:
+                emit(b)
+                code.append(op[name])
+            if swapped and name == "SUB":
+                code.append(op["NEG"])
+        else:
+            raise TypeError(f"not a gate expression: {e!r}")
+
+    for e in exprs:
+        emit(_expr(e))
+        code.append(op["FOLD"])
+    R = 1 << 256
+    cvals = np.frombuffer(b"".join((v * R % FR_MODULUS).to_bytes(32, "little") for v in consts), np.uint64).reshape(-1, 4) if consts else np.zeros((0, 4), np.uint64)
+    return GateProgram(code, np.array(list(queries), np.int32).reshape(-1, 2), cvals.copy())
 
 
 def best_fft(a, omega, log_n: int, ctx: Optional[Context] = None) -> np.ndarray:

@@ -30,6 +30,7 @@
 #include "column.cuh"
 #include "poly.cuh"
 #include "domain.cuh"
+#include "gate.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -2732,3 +2733,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "column_abi.inc"
 #include "poly_abi.inc"
 #include "domain_abi.inc"
+#include "gate_abi.inc"

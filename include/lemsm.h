@@ -687,6 +687,77 @@ int lemsm_coeff_to_extended(lemsm_ctx* ctx, const uint64_t* coeffs, size_t n_coe
 int lemsm_extended_to_coeff(lemsm_ctx* ctx, const uint64_t* evals, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
                             int divide_vanishing, int form, uint64_t* out, size_t n_out, size_t* bad_index);
 
+/* ---- gate expressions on the extended domain: the numerator of the quotient h (src/config.rs:232-568) ------
+   What halo2's evaluate_h does over the custom gates of a circuit, on columns resident in HBM: every gate polynomial is
+   evaluated at every point of the extended domain and the gates are combined by powers of the challenge y,
+   h = (..(g_0 y + g_1) y + ..) y + g_last.  The circuit is data: a postfix program over the cells of the columns, the
+   constants of the call (challenges among them) and the point itself.  The reference's gates (create_gate at
+   src/config.rs:232, :246, :332, :402, :504, :562) are degree 4 over some twenty queried cells.
+   Columns: one buffer of N = m n raw Montgomery elements each, in LEMSM_EXT_COSET_MAJOR -- the only layout these entries
+   take: point (c, r) = s_c w^r (the definitions above) lies at element c n + r, and a query with rotation i reads row
+   (r + i) mod n of the same coset, i.e. the column's polynomial at w^i X.  bn256::Fr, the conventions of the entries
+   above.  The permutation and lookup grand products of halo2, the placement of rows and blinding stay with the caller:
+   LEMSM_GATE_PUSH_X and fixed columns make their terms expressible, nothing here builds them. */
+enum {  /* low 8 bits of a code word; operand = word >> 8 (zero for the opcodes that take none) */
+  LEMSM_GATE_PUSH_CELL = 0,    /* q: push columns[queries[q].column] at row (r + queries[q].rotation) mod n of coset c */
+  LEMSM_GATE_PUSH_CONST = 1,   /* k: push consts[k] (challenges are constants of a call) */
+  LEMSM_GATE_PUSH_X = 2,       /* push the point itself, s_c w^r (permutation-style terms) */
+  LEMSM_GATE_ADD = 3,          /* pop top, pop second, push second + top */
+  LEMSM_GATE_SUB = 4,          /* ... second - top */
+  LEMSM_GATE_MUL = 5,          /* ... second top */
+  LEMSM_GATE_NEG = 6,          /* top <- -top */
+  LEMSM_GATE_ADD_CELL = 7,     /* q: top <- top + cell q */
+  LEMSM_GATE_SUB_CELL = 8,     /* q: top <- top - cell q */
+  LEMSM_GATE_MUL_CELL = 9,     /* q: top <- top cell q */
+  LEMSM_GATE_ADD_CONST = 10,   /* k: top <- top + consts[k] */
+  LEMSM_GATE_SUB_CONST = 11,   /* k: top <- top - consts[k] */
+  LEMSM_GATE_MUL_CONST = 12,   /* k: top <- top consts[k] */
+  LEMSM_GATE_FOLD = 13         /* h <- h y + pop: halo2's combination of gates by powers of y; h starts at 0 */
+};
+typedef struct { int32_t column, rotation; } lemsm_gate_query;
+typedef struct {
+  const uint32_t* code; size_t n_code;
+  const lemsm_gate_query* queries; size_t n_queries;
+  const uint64_t* consts;      /* n_consts x 4 raw Montgomery limbs, canonical */
+  size_t n_consts;
+} lemsm_gate_program;
+/* Pure host, no context: the validator (the device entry calls it too) and the price of a program per point.
+   Limits: n_code <= 4096, n_queries, n_consts <= 256, ncols <= 64, stack depth <= 8, |rotation| < 2^26 (any rotation: it is
+   reduced mod n).  A limit exceeded or a null pointer: LEMSM_ERR_BAD_ARG, *bad_index untouched.  Otherwise
+   LEMSM_ERR_BAD_ARG with *bad_index (optional) set: a constant that is not canonical (the constant's index; every constant is
+   checked, before any instruction); then, per instruction in the order unknown opcode, operand out of range (a query or
+   constant index past its table, a query naming a column < 0 or >= ncols or a rotation past the limit, a non-zero operand
+   field on an opcode that takes none), stack underflow, depth above 8 (the instruction's index); a stack that is not empty
+   at the end, or a program without a FOLD (n_code).  A query that no instruction names is not looked at.
+   stack_depth: the largest number of entries; folds: the FOLD count.  degree: in units of (n - 1), columns holding
+   polynomials of degree < n: a cell or X counts 1, a constant 0, ADD / SUB take the maximum, MUL the sum; the maximum
+   over the folds.  The extended domain must hold it: 2^logm >= degree (halo2's quotient drops one more unit).
+   field_mults_per_point = #(MUL, MUL_CELL, MUL_CONST) + (folds - 1) + (3 if the program has a PUSH_X, however many): the
+   first FOLD is h <- top, and the point is computed once per thread as one product by s_c and logn > 8 ? (logn > 16 ? 2 :
+   1) : 0 for w^r; the plan does not know logn and prices the largest, lemsm_poly_last reports the call's own count.
+   cell_loads_per_point = #(PUSH_CELL, ADD_CELL, SUB_CELL, MUL_CELL).  (halo2 evaluate_h; src/config.rs:232-568) */
+int lemsm_gate_plan(const lemsm_gate_program* prog, size_t ncols, uint32_t* stack_depth, uint32_t* folds, uint32_t* degree,
+                    uint64_t* field_mults_per_point, uint64_t* cell_loads_per_point, size_t* bad_index);
+/* h on cosets coset_begin .. coset_begin + coset_count - 1: elements coset_begin n .. (coset_begin + coset_count) n - 1 of
+   d_out (cap_out >= N elements, raw Montgomery) and nothing else, so a caller may work coset by coset or split the cosets
+   over contexts.  d_columns: ncols device pointers, N elements each, coset-major.  shift = g as lemsm_coeff_to_extended_device
+   took it: read only when the program has a PUSH_X (then NULL, zero or not canonical: LEMSM_ERR_BAD_ARG).  y: canonical.
+   d_out must not overlap any column (rotations make an in-place run a race): LEMSM_ERR_BAD_ARG, as are a null pointer,
+   coset_begin + coset_count > m, a limit exceeded (logn, logm as above), cap_out < N and a program lemsm_gate_plan refuses
+   (*bad_index and lemsm_last_bad_index as there).  coset_count == 0 is LEMSM_OK and writes nothing.  One kernel, a thread
+   per point, sums in program order: the same bytes on every call.  lemsm_poly_last: ms, bytes = (cell_loads_per_point + 1)
+   32 points, and the products.  With lemsm_coeff_to_extended_device before and lemsm_extended_to_coeff_device(..,
+   divide_vanishing = 1, ..) behind it this is halo2's vanishing argument without a download.
+   (src/config.rs:232, :246, :332, :402, :504, :562) */
+int lemsm_gate_eval_device(lemsm_ctx* ctx, const lemsm_gate_program* prog, const void* const* d_columns, size_t ncols, uint32_t logn,
+                           uint32_t logm, uint32_t coset_begin, uint32_t coset_count, const uint64_t* shift, const uint64_t y[4], void* d_out,
+                           size_t cap_out, size_t* bad_index);
+/* The same with the columns and the output in host memory (N elements each; the range's cosets are uploaded, the device
+   path runs, the range is downloaded; `out` outside the range is not written).  (src/config.rs:232-568) */
+int lemsm_gate_eval(lemsm_ctx* ctx, const lemsm_gate_program* prog, const uint64_t* const* columns, size_t ncols, uint32_t logn, uint32_t logm,
+                    uint32_t coset_begin, uint32_t coset_count, const uint64_t* shift, const uint64_t y[4], uint64_t* out, size_t cap_out,
+                    size_t* bad_index);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
