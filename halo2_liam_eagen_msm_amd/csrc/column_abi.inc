@@ -1,6 +1,6 @@
 // Advice column a from the resident divisor witnesses and the cells of the "polynomials random linear combination" gate
 // (include/lemsm.h: lemsm_column_plan, lemsm_column_a*, lemsm_poly_rlc*, lemsm_column_last; src/layout.md:7,
-// src/config.rs:39-48, :246-283).  Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, timed_run, LastStats /
+// src/config.rs:39-48, :246-283).  Included at the end of lemsm.hip (it uses lemsm_ctx, Arena, Workspace, Staged, timed_run, LastStats /
 // last_stats, index_rows_ok, HIPCHK, fail); the kernels are column.cuh's.
 
 namespace {
@@ -92,7 +92,7 @@ int col_assemble(lemsm_ctx* ctx, const void* d_coeffs, const size_t* index, cons
       hipLaunchKernelGGL((cl::k_column_a<true>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)d_fns, (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
     else
       hipLaunchKernelGGL((cl::k_column_a<false>), grid, blk, 0, st, (const uint4*)d_coeffs, (const cl::Fn*)d_fns, (u32)pl.T, bs, tf, nch, (u64)pl.nb, (uint4*)d_out);
-  }, [] { return LEMSM_OK; });
+  });
   return ws.done(rc);
 }
 
@@ -133,7 +133,7 @@ int col_rlc(lemsm_ctx* ctx, const void* d_column, int form, const ColPlan& pl, s
       hipLaunchKernelGGL((cl::k_poly_rlc<true>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)d_pw, (const uint4*)d_rho, (uint4*)d_cells);
     else
       hipLaunchKernelGGL((cl::k_poly_rlc<false>), dim3((u32)nblk), dim3(64), 0, st, (const uint4*)d_column, bs, cskip, G, (u64)pl.nb, (const uint4*)d_pw, (const uint4*)d_rho, (uint4*)d_cells);
-  }, [] { return LEMSM_OK; });
+  });
   return ws.done(rc);
 }
 
@@ -193,18 +193,13 @@ int lemsm_column_a(lemsm_ctx* ctx, int curve, const uint64_t* coeffs, size_t cap
   if (pl.rows > cap_rows || pl.rows == 0)   // (the device entry gives the status and sets the figures)
     return lemsm_column_a_device(ctx, curve, nullptr, cap_coeffs, index, T, batch_offset, num_batches, form, nullptr, cap_rows, out_num_batches);
   if (!out_column) return LEMSM_ERR_BAD_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("column_staged", ctx->opt.ws_canary != 0);
-  const size_t o_co = ar.take("coefficients", std::max<size_t>(cap_coeffs, 1) * 32), o_out = ar.take("column", pl.rows * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->col_stage, ar.total(), ctx->stream); if (rc) return rc;
-  char* b = ws.base;
-  if (cap_coeffs) HIPCHK(ctx, hipMemcpyAsync(b + o_co, coeffs, cap_coeffs * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_column_a_device(ctx, curve, b + o_co, cap_coeffs, index, T, batch_offset, num_batches, form, b + o_out, pl.rows, out_num_batches);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out_column, b + o_out, pl.rows * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "column_staged");
+  const size_t o_co = sg.take("coefficients", std::max<size_t>(cap_coeffs, 1) * 32), o_out = sg.take("column", pl.rows * 32);
+  sg.open(ctx->col_stage);
+  sg.upload(o_co, coeffs, cap_coeffs * 32);
+  sg.call([&] { return lemsm_column_a_device(ctx, curve, sg.at(o_co), cap_coeffs, index, T, batch_offset, num_batches, form, sg.at(o_out), pl.rows, out_num_batches); });
+  sg.download(out_column, o_out, pl.rows * 32);
+  return sg.finish();
 }
 
 int lemsm_poly_rlc_device(lemsm_ctx* ctx, int curve, const void* d_column, int form, size_t T, size_t batch_offset, size_t poly_fan_in,
@@ -234,18 +229,13 @@ int lemsm_poly_rlc(lemsm_ctx* ctx, int curve, const uint64_t* column, int form, 
   if (pl.cells > cap_cells || pl.cells == 0)   // (the device entry gives the status and sets the figures)
     return lemsm_poly_rlc_device(ctx, curve, nullptr, form, T, batch_offset, poly_fan_in, num_batches, r, nullptr, cap_cells);
   if (!column || !out_cells) return LEMSM_ERR_BAD_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("column_staged", ctx->opt.ws_canary != 0);
-  const size_t o_col = ar.take("column", pl.rows * 32), o_out = ar.take("cells", pl.cells * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->col_stage, ar.total(), ctx->stream); if (rc) return rc;
-  char* b = ws.base;
-  HIPCHK(ctx, hipMemcpyAsync(b + o_col, column, pl.rows * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_poly_rlc_device(ctx, curve, b + o_col, form, T, batch_offset, poly_fan_in, num_batches, r, b + o_out, pl.cells);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out_cells, b + o_out, pl.cells * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "column_staged");
+  const size_t o_col = sg.take("column", pl.rows * 32), o_out = sg.take("cells", pl.cells * 32);
+  sg.open(ctx->col_stage);
+  sg.upload(o_col, column, pl.rows * 32);
+  sg.call([&] { return lemsm_poly_rlc_device(ctx, curve, sg.at(o_col), form, T, batch_offset, poly_fan_in, num_batches, r, sg.at(o_out), pl.cells); });
+  sg.download(out_cells, o_out, pl.cells * 32);
+  return sg.finish();
 }
 
 int lemsm_column_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::col_last, ms, bytes, field_mults); }

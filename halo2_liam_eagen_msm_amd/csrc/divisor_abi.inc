@@ -105,11 +105,6 @@ void dw_ntt(lemsm_ctx* ctx, u32* buf, u32 nseq, u32 logN, bool inverse, const le
       hipLaunchKernelGGL(lemsm::dw::k_ntt_stage, grid, blk, 0, ctx->stream, buf, nseq, logN, lm, (const u32*)dw_W(ctx), lhm, 1u);
     return;
   }
-  // passes: the contiguous one covers spans 2^0..2^(S0-1); strided ones the rest in groups of <= 8 stages
-  const u32 S0 = std::min(logN, 10u);
-  struct Pass { u32 lo, S; };
-  std::vector<Pass> up;                    // ascending spans
-  for (u32 lo = S0; lo < logN;) { u32 S = std::min(8u, logN - lo); up.push_back({lo, S}); lo += S; }
   TileIO none; memset(&none, 0, sizeof none);
   // `edge`: this launch is the first pass of a forward transform / the last pass of an inverse one -- where a fused load / store happens
   bool first_done = false;
@@ -143,17 +138,13 @@ void dw_ntt(lemsm_ctx* ctx, u32* buf, u32 nseq, u32 logN, bool inverse, const le
     }
   };
   const dim3 gcont((u32)((total + 1023) / 1024)), gstr((u32)(total >> 10));      // strided: every block owns 2^S * TW = 1024 elements
-  if (!inverse) {
-    for (size_t i = up.size(); i-- > 0;) launch(gstr, up[i].lo, up[i].S, i + 1 == up.size());
-    launch(gcont, 0u, S0, up.empty());
-  } else {
-    launch(gcont, 0u, S0, up.empty());
-    for (size_t i = 0; i < up.size(); i++) launch(gstr, up[i].lo, up[i].S, i + 1 == up.size());
-  }
+  // the passes (ntt_schedule.hpp); the edge is the pass at the strided end of the list, the only pass when there is none
+  const lemsm::ntt::Schedule sch = lemsm::ntt::schedule(logN, inverse);
+  for (u32 i = 0; i < sch.count; i++) launch(sch.pass[i].strided ? gstr : gcont, sch.pass[i].lo, sch.pass[i].S, i == (inverse ? sch.count - 1 : 0u));
 }
 
 // passes over HBM one transform of 2^logN elements makes (dw_ntt)
-u32 dw_ntt_passes(const lemsm_ctx* ctx, u32 logN) { return ctx->opt.ntt_tiled == 2 ? logN : 1u + (logN > 10 ? (logN - 10 + 7) / 8 : 0u); }
+u32 dw_ntt_passes(const lemsm_ctx* ctx, u32 logN) { return ctx->opt.ntt_tiled == 2 ? logN : lemsm::ntt::passes(logN); }
 
 struct DwResult {
   const u32* A = nullptr; const u32* B = nullptr;   // device, 32-byte coefficients

@@ -1,8 +1,9 @@
 // halo2's EvaluationDomain as entries on resident data (include/lemsm.h: lemsm_domain_plan, lemsm_vanishing_on_cosets,
 // lemsm_coset_fft*, lemsm_coset_ifft*, lemsm_coeff_to_extended*, lemsm_extended_to_coeff*; DESIGN 7d).  Included at the end
 // of lemsm.hip behind poly_abi.inc, whose conventions and helpers it keeps (POLY_*, poly_fe, poly_canonical, poly_overlap,
-// poly_omega, poly_half_pow, poly_ntt_passes, poly_table_*, poly_ntt, poly_fft_check; the figures go to ctx->poly_last);
-// the kernels are domain.cuh's, the passes divisor.cuh's k_ntt_tile and the in-place reorder poly.cuh's k_fft_reorder.
+// poly_omega, poly_half_pow, poly_ntt_passes, poly_ntt, poly_fft_check; the twiddle table is the context's PolyTable, the
+// host twins are Staged scopes, the figures go to ctx->poly_last); the kernels are domain.cuh's, the passes divisor.cuh's
+// k_ntt_tile and the in-place reorder poly.cuh's k_fft_reorder.
 
 namespace {
 
@@ -18,8 +19,13 @@ int dom_shift_check(lemsm_ctx* ctx, const uint64_t* shift, const char* who) {
   if (!poly_canonical(shift) || HFr::is_zero(poly_fe(shift))) return fail(ctx, LEMSM_ERR_BAD_ARG, std::string(who) + ": shift is zero or not a canonical field element");
   return LEMSM_OK;
 }
-int dom_check(lemsm_ctx* ctx, u32 logn, u32 logm, const uint64_t* shift, const char* who) {
+// the extended domains the entries serve
+int dom_limits_check(lemsm_ctx* ctx, u32 logn, u32 logm, const char* who) {
   if (logn > POLY_MAX_LOGN || logm > DOM_MAX_LOGM || logn + logm > POLY_S) return fail(ctx, LEMSM_ERR_BAD_ARG, std::string(who) + ": logn at most 26, logm at most 4, logn + logm at most 28");
+  return LEMSM_OK;
+}
+int dom_check(lemsm_ctx* ctx, u32 logn, u32 logm, const uint64_t* shift, const char* who) {
+  int rc = dom_limits_check(ctx, logn, logm, who); if (rc) return rc;
   return dom_shift_check(ctx, shift, who);
 }
 
@@ -83,31 +89,30 @@ int dom_coset_device(lemsm_ctx* ctx, void* d_data, size_t nseq, u32 logn, const 
   if (!d_data) return LEMSM_ERR_BAD_ARG;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const host::fe w = poly_fe(omega);
-  host::fe up[33], sq[dm::POW_SQ]; bool build = false;
-  if (logn) { rc = poly_table_prepare(ctx, w, logn, build, up); if (rc) return rc; }
-  if (scale) up[32] = poly_fe(scale);
+  const host::fe factor = scale ? poly_fe(scale) : HFr::one();
+  host::fe sq[dm::POW_SQ];
+  PolyTable::Use tw;
+  rc = ctx->poly_tab.need(ctx, poly_fe(omega), logn, tw); if (rc) return rc;
   dom_squarings(g, sq);
   DomCarve c;
   Arena ar = dom_arena(ctx->opt.ws_canary != 0, 1, 0, 0, c);
-  Workspace ws;   // (behind up and sq: the stream has read them when it goes)
+  Workspace ws;   // (behind tw, factor and sq: the stream has read them when it goes)
   rc = ws.open(ctx, std::move(ar), ctx->poly_ws, ar.total(), st); if (rc) return rc;
-  if (build) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.tw), up, 32 * 32, hipMemcpyHostToDevice, st));
-  if (scale) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.sc), &up[32], 32, hipMemcpyHostToDevice, st));
+  rc = tw.upload(ctx, ws.at<u32>(c.tw), st); if (rc) return rc;
+  if (scale) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.sc), &factor, 32, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.sq), sq, sizeof sq, hipMemcpyHostToDevice, st));
   const uint4* d_sc = scale ? (const uint4*)ws.at<uint4>(c.sc) : (const uint4*)nullptr;
   uint4* tab = ws.at<uint4>(c.tab);
   const dim3 gall((u32)((total + 255) / 256)), blk(256);
   rc = timed_run(ctx, st, ctx->poly_last, [&] {
-    if (build) poly_table_launch(ctx, st, ws.at<u32>(c.tw), logn);
+    tw.launch(st);
     dom_tables_launch(st, ws.at<uint4>(c.sq), tab, 1, inverse ? d_sc : (const uint4*)nullptr);
     if (!inverse) hipLaunchKernelGGL(dm::k_coset_scale, gall, blk, 0, st, (uint4*)d_data, total, logn, (const uint4*)tab);
     if (logn) poly_ntt(ctx, st, (u32*)d_data, (u32)nseq, logn, false);
     if (inverse) hipLaunchKernelGGL(dm::k_coset_reorder, gall, blk, 0, st, (uint4*)d_data, total, logn, (const uint4*)tab);
     else if (reorder) hipLaunchKernelGGL(pl::k_fft_reorder, gall, blk, 0, st, (uint4*)d_data, total, logn, d_sc);
-  }, [] { return LEMSM_OK; });
-  if (!rc && build) poly_table_built(ctx, w, logn);
-  return ws.done(rc);
+  });
+  return ws.done(tw.commit(rc));
 }
 
 int dom_coset_host(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, u32 logn, const uint64_t* omega, const uint64_t* shift, const uint64_t* scale, bool inverse) {
@@ -115,18 +120,14 @@ int dom_coset_host(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nse
   int rc = poly_fft_check(ctx, nseq, logn, omega, scale); if (rc) return rc;
   rc = dom_shift_check(ctx, shift, inverse ? "coset_ifft" : "coset_fft"); if (rc) return rc;
   if (!in || !out) return LEMSM_ERR_BAD_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (nseq << logn) * 32;
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_d = ar.take("data", bytes);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ws.base + o_d, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = dom_coset_device(ctx, ws.base + o_d, nseq, logn, omega, shift, scale, inverse);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out, ws.base + o_d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_d = sg.take("data", bytes);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_d, in, bytes);
+  sg.call([&] { return dom_coset_device(ctx, sg.at(o_d), nseq, logn, omega, shift, scale, inverse); });
+  sg.download(out, o_d, bytes);
+  return sg.finish();
 }
 
 // the arguments of the two extended entries that do not depend on where the arrays live
@@ -162,7 +163,7 @@ int dom_inverse_check(lemsm_ctx* ctx, u32 logn, u32 logm, const uint64_t* shift,
 extern "C" {
 
 int lemsm_domain_plan(uint32_t logn, uint32_t logm, size_t n_coeffs, uint32_t* passes, uint64_t* bytes, uint64_t* field_mults, uint64_t* workspace_bytes) {
-  if (logn > POLY_MAX_LOGN || logm > DOM_MAX_LOGM || logn + logm > POLY_S || n_coeffs > ((size_t)1 << (logn + logm))) return LEMSM_ERR_BAD_ARG;
+  if (dom_limits_check(nullptr, logn, logm, "domain_plan") || n_coeffs > ((size_t)1 << (logn + logm))) return LEMSM_ERR_BAD_ARG;
   const DomPrice p = dom_price(logn, logm, n_coeffs);
   if (passes) *passes = p.passes;
   if (bytes) *bytes = p.bytes;
@@ -211,14 +212,15 @@ int lemsm_coeff_to_extended_device(lemsm_ctx* ctx, const void* d_coeffs, size_t 
   hipStream_t st = ctx->stream;
   hipError_t cerr = hipSuccess;
   if (n_coeffs == 0) {
-    rc = timed_run(ctx, st, ctx->poly_last, [&] { cerr = hipMemsetAsync(d_out, 0, N * 32, st); }, [] { return LEMSM_OK; });
+    rc = timed_run(ctx, st, ctx->poly_last, [&] { cerr = hipMemsetAsync(d_out, 0, N * 32, st); });
     if (!rc && cerr != hipSuccess) rc = fail(ctx, LEMSM_ERR_HIP, std::string("coeff_to_extended: ") + hipGetErrorString(cerr));
     return rc;
   }
-  const host::fe g = poly_fe(shift), w = poly_omega(logn, false), w_ext = poly_omega(logn + logm, false);
-  host::fe up[32], sq[2 * dm::POW_SQ]; bool build = false;
+  const host::fe g = poly_fe(shift), w_ext = poly_omega(logn + logm, false);
+  host::fe sq[2 * dm::POW_SQ];
   std::vector<host::fe> K;
-  if (logn) { rc = poly_table_prepare(ctx, w, logn, build, up); if (rc) return rc; }
+  PolyTable::Use tw;
+  rc = ctx->poly_tab.need(ctx, poly_omega(logn, false), logn, tw); if (rc) return rc;
   dom_squarings(g, sq); dom_squarings(w_ext, sq + dm::POW_SQ);
   if (fold) {                               // K[c][q] = (s_c^n)^q = (g^n theta^c)^q
     K.resize(m * m);
@@ -232,25 +234,24 @@ int lemsm_coeff_to_extended_device(lemsm_ctx* ctx, const void* d_coeffs, size_t 
   }
   DomCarve c;
   Arena ar = dom_arena(ctx->opt.ws_canary != 0, 2, K.size(), through_ws ? N : 0, c);
-  Workspace ws;   // (behind up, sq and K: the stream has read them when it goes)
+  Workspace ws;   // (behind tw, sq and K: the stream has read them when it goes)
   rc = ws.open(ctx, std::move(ar), ctx->poly_ws, ar.total(), st); if (rc) return rc;
-  if (build) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.tw), up, 32 * 32, hipMemcpyHostToDevice, st));
+  rc = tw.upload(ctx, ws.at<u32>(c.tw), st); if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.sq), sq, sizeof sq, hipMemcpyHostToDevice, st));
   if (fold) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.mat), K.data(), K.size() * 32, hipMemcpyHostToDevice, st));
   uint4* tab = ws.at<uint4>(c.tab);
   uint4* buf = through_ws ? ws.at<uint4>(c.buf) : (uint4*)d_out;
   const dim3 blk(256), gn((u32)((n + 255) / 256)), gN((u32)((N + 255) / 256));
   rc = timed_run(ctx, st, ctx->poly_last, [&] {
-    if (build) poly_table_launch(ctx, st, ws.at<u32>(c.tw), logn);
+    tw.launch(st);
     dom_tables_launch(st, ws.at<uint4>(c.sq), tab, 2, nullptr);
     hipLaunchKernelGGL(dm::k_dom_spread, gn, blk, 0, st, (const uint4*)d_coeffs, (u64)n_coeffs, logn, logm, (const uint4*)tab,
                        fold ? (const uint4*)ws.at<uint4>(c.mat) : (const uint4*)nullptr, buf);
     if (logn) poly_ntt(ctx, st, (u32*)buf, (u32)m, logn, false);
     if (through_ws) hipLaunchKernelGGL(dm::k_dom_interleave, gN, blk, 0, st, (const uint4*)buf, logn, logm, (uint4*)d_out);
     else if (logn > 1) hipLaunchKernelGGL(pl::k_fft_reorder, gN, blk, 0, st, buf, (u64)N, logn, (const uint4*)nullptr);
-  }, [] { return LEMSM_OK; });
-  if (!rc && build) poly_table_built(ctx, w, logn);
-  return ws.done(rc);
+  });
+  return ws.done(tw.commit(rc));
 }
 
 int lemsm_extended_to_coeff_device(lemsm_ctx* ctx, const void* d_evals, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
@@ -267,9 +268,10 @@ int lemsm_extended_to_coeff_device(lemsm_ctx* ctx, const void* d_evals, uint32_t
   if (n_out == 0) return LEMSM_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const host::fe g = poly_fe(shift), w = poly_omega(logn, false);
-  host::fe up[32], sq[2 * dm::POW_SQ]; bool build = false;
-  if (logn) { rc = poly_table_prepare(ctx, w, logn, build, up); if (rc) return rc; }
+  const host::fe g = poly_fe(shift);
+  host::fe sq[2 * dm::POW_SQ];
+  PolyTable::Use tw;
+  rc = ctx->poly_tab.need(ctx, poly_omega(logn, false), logn, tw); if (rc) return rc;
   dom_squarings(HFr::inv(g), sq); dom_squarings(poly_omega(logn + logm, true), sq + dm::POW_SQ);
   // M[q][c] = g^(-n q) theta^(-c q) / (m n), over t_c for the division, times R^-1 for standard form
   std::vector<host::fe> M(m * m);
@@ -289,9 +291,9 @@ int lemsm_extended_to_coeff_device(lemsm_ctx* ctx, const void* d_evals, uint32_t
   }
   DomCarve c;
   Arena ar = dom_arena(ctx->opt.ws_canary != 0, 2, M.size(), N, c);
-  Workspace ws;   // (behind up, sq and M: the stream has read them when it goes)
+  Workspace ws;   // (behind tw, sq and M: the stream has read them when it goes)
   rc = ws.open(ctx, std::move(ar), ctx->poly_ws, ar.total(), st); if (rc) return rc;
-  if (build) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.tw), up, 32 * 32, hipMemcpyHostToDevice, st));
+  rc = tw.upload(ctx, ws.at<u32>(c.tw), st); if (rc) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.sq), sq, sizeof sq, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(c.mat), M.data(), M.size() * 32, hipMemcpyHostToDevice, st));
   uint4* tab = ws.at<uint4>(c.tab);
@@ -299,16 +301,15 @@ int lemsm_extended_to_coeff_device(lemsm_ctx* ctx, const void* d_evals, uint32_t
   const uint4* d_M = ws.at<uint4>(c.mat);
   hipError_t cerr = hipSuccess;
   rc = timed_run(ctx, st, ctx->poly_last, [&] {
-    if (build) poly_table_launch(ctx, st, ws.at<u32>(c.tw), logn);
+    tw.launch(st);
     dom_tables_launch(st, ws.at<uint4>(c.sq), tab, 2, nullptr);
     if (gather) hipLaunchKernelGGL(dm::k_dom_gather, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, (const uint4*)d_evals, logn, logm, buf);
     else cerr = hipMemcpyAsync(buf, d_evals, N * 32, hipMemcpyDeviceToDevice, st);
     if (logn) poly_ntt(ctx, st, (u32*)buf, (u32)m, logn, false);
     dom_combine_launch(st, buf, logn, logm, tab, d_M, (uint4*)d_out, n_out);
-  }, [] { return LEMSM_OK; });
+  });
   if (!rc && cerr != hipSuccess) rc = fail(ctx, LEMSM_ERR_HIP, std::string("extended_to_coeff: ") + hipGetErrorString(cerr));
-  if (!rc && build) poly_table_built(ctx, w, logn);
-  return ws.done(rc);
+  return ws.done(tw.commit(rc));
 }
 
 int lemsm_coeff_to_extended(lemsm_ctx* ctx, const uint64_t* coeffs, size_t n_coeffs, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
@@ -317,17 +318,13 @@ int lemsm_coeff_to_extended(lemsm_ctx* ctx, const uint64_t* coeffs, size_t n_coe
   const size_t N = (size_t)1 << (logn + logm);
   if (!out || (n_coeffs && !coeffs)) return LEMSM_ERR_BAD_ARG;
   if (poly_overlap(coeffs, n_coeffs * 32, out, cap_out * 32)) return fail(ctx, LEMSM_ERR_BAD_ARG, "coeff_to_extended: out overlaps coeffs");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_in = ar.take("coefficients", std::max<size_t>(n_coeffs, 1) * 32), o_out = ar.take("values", N * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  if (n_coeffs) HIPCHK(ctx, hipMemcpyAsync(ws.base + o_in, coeffs, n_coeffs * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_coeff_to_extended_device(ctx, ws.base + o_in, n_coeffs, logn, logm, shift, layout, ws.base + o_out, N);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out, ws.base + o_out, N * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_in = sg.take("coefficients", std::max<size_t>(n_coeffs, 1) * 32), o_out = sg.take("values", N * 32);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_in, coeffs, n_coeffs * 32);
+  sg.call([&] { return lemsm_coeff_to_extended_device(ctx, sg.at(o_in), n_coeffs, logn, logm, shift, layout, sg.at(o_out), N); });
+  sg.download(out, o_out, N * 32);
+  return sg.finish();
 }
 
 int lemsm_extended_to_coeff(lemsm_ctx* ctx, const uint64_t* evals, uint32_t logn, uint32_t logm, const uint64_t shift[4], int layout,
@@ -337,17 +334,13 @@ int lemsm_extended_to_coeff(lemsm_ctx* ctx, const uint64_t* evals, uint32_t logn
   const size_t N = (size_t)1 << (logn + logm);
   if (!evals || (n_out && !out)) return LEMSM_ERR_BAD_ARG;
   if (poly_overlap(evals, N * 32, out, n_out * 32)) return fail(ctx, LEMSM_ERR_BAD_ARG, "extended_to_coeff: out overlaps evals");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_in = ar.take("values", N * 32), o_out = ar.take("coefficients", std::max<size_t>(n_out, 1) * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ws.base + o_in, evals, N * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_extended_to_coeff_device(ctx, ws.base + o_in, logn, logm, shift, layout, divide_vanishing, form, ws.base + o_out, n_out, bad_index);
-  if (rc) return ws.done(rc);
-  if (n_out) HIPCHK(ctx, hipMemcpyAsync(out, ws.base + o_out, n_out * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_in = sg.take("values", N * 32), o_out = sg.take("coefficients", std::max<size_t>(n_out, 1) * 32);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_in, evals, N * 32);
+  sg.call([&] { return lemsm_extended_to_coeff_device(ctx, sg.at(o_in), logn, logm, shift, layout, divide_vanishing, form, sg.at(o_out), n_out, bad_index); });
+  sg.download(out, o_out, n_out * 32);
+  return sg.finish();
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // Gate expressions on the extended domain as entries on resident columns (include/lemsm.h: lemsm_gate_plan,
 // lemsm_gate_eval_device, lemsm_gate_eval; DESIGN 7e; the gates they stand behind: src/config.rs:232-568).  Included at the
-// end of lemsm.hip behind domain_abi.inc, whose helpers and conventions it keeps (dom_check, dom_squarings,
-// dom_tables_launch, poly_fe, poly_canonical, poly_overlap, poly_omega; the figures go to ctx->poly_last); the kernel is
-// gate.cuh's.
+// end of lemsm.hip behind domain_abi.inc, whose helpers and conventions it keeps (dom_limits_check, dom_shift_check,
+// dom_squarings, dom_tables_launch, poly_fe, poly_canonical, poly_overlap, poly_omega; the host twin is a Staged scope, the
+// figures go to ctx->poly_last); the kernel is gate.cuh's.
 
 namespace {
 
@@ -58,14 +58,14 @@ int gate_validate(const lemsm_gate_program* p, size_t ncols, GatePlan& g, size_t
 int gate_check(lemsm_ctx* ctx, const lemsm_gate_program* prog, size_t ncols, u32 logn, u32 logm, u32 coset_begin, u32 coset_count,
                const uint64_t* shift, const uint64_t* y, size_t cap_out, size_t* bad_index, GatePlan& g) {
   if (!ctx || !prog || !y) return LEMSM_ERR_BAD_ARG;
-  if (logn > POLY_MAX_LOGN || logm > DOM_MAX_LOGM || logn + logm > POLY_S) return fail(ctx, LEMSM_ERR_BAD_ARG, "gate_eval: logn at most 26, logm at most 4, logn + logm at most 28");
+  int rc = dom_limits_check(ctx, logn, logm, "gate_eval"); if (rc) return rc;
   const u64 m = (u64)1 << logm;
   if ((u64)coset_begin + coset_count > m) return fail(ctx, LEMSM_ERR_BAD_ARG, "gate_eval: the coset range reaches past 2^logm");
   if (cap_out < ((size_t)1 << (logn + logm))) return fail(ctx, LEMSM_ERR_BAD_ARG, "gate_eval: capacity " + std::to_string(cap_out) + " elements, the extended domain has " + std::to_string((size_t)1 << (logn + logm)));
   if (!poly_canonical(y)) return fail(ctx, LEMSM_ERR_BAD_ARG, "gate_eval: y is not a canonical field element");
   const size_t nowhere = ~(size_t)0;
   size_t where = nowhere;
-  int rc = gate_validate(prog, ncols, g, &where);
+  rc = gate_validate(prog, ncols, g, &where);
   if (rc) {
     if (where == nowhere) return fail(ctx, rc, "gate_eval: the program or ncols exceeds a limit of lemsm_gate_plan, or a table is null");
     if (bad_index) *bad_index = where;
@@ -148,7 +148,7 @@ int lemsm_gate_eval_device(lemsm_ctx* ctx, const lemsm_gate_program* prog, const
     hipLaunchKernelGGL(gt::k_gate_eval, dim3((u32)((points + gt::BLOCK - 1) / gt::BLOCK)), dim3(gt::BLOCK), lds, st, (const u32*)(d_blob + o_code),
                        (u32)prog->n_code, (const gt::Query*)(d_blob + o_q), (const uint4*)d_blob, (const uint4*)(d_blob + o_y),
                        (const uint4*)(d_blob + o_sh), g.has_x ? (const uint4*)tab : (const uint4*)nullptr, (uint4*)d_out, logn, coset_begin, points);
-  }, [] { return LEMSM_OK; });
+  });
   return ws.done(rc);
 }
 
@@ -164,25 +164,21 @@ int lemsm_gate_eval(lemsm_ctx* ctx, const lemsm_gate_program* prog, const uint64
     if (poly_overlap(columns[c], N * 32, out, cap_out * 32)) return fail(ctx, LEMSM_ERR_BAD_ARG, "gate_eval: out overlaps column " + std::to_string(c));
   }
   if (coset_count == 0) return LEMSM_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   // the staged columns and the output, N elements each; only the range's cosets travel (a rotation stays inside its coset)
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
+  Staged sg(ctx, "poly_staged");
   std::vector<size_t> o_col(ncols);
-  for (size_t c = 0; c < ncols; c++) o_col[c] = ar.take("column", N * 32);
-  const size_t o_out = ar.take("values", N * 32);
+  for (size_t c = 0; c < ncols; c++) o_col[c] = sg.take("column", N * 32);
+  const size_t o_out = sg.take("values", N * 32);
   const size_t first = (size_t)coset_begin * n * 32, bytes = (size_t)coset_count * n * 32;
   std::vector<const void*> d_cols(ncols);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  for (size_t c = 0; c < ncols; c++) {
-    d_cols[c] = ws.base + o_col[c];
-    HIPCHK(ctx, hipMemcpyAsync(ws.base + o_col[c] + first, (const char*)columns[c] + first, bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  rc = lemsm_gate_eval_device(ctx, prog, d_cols.data(), ncols, logn, logm, coset_begin, coset_count, shift, y, ws.base + o_out, N, bad_index);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync((char*)out + first, ws.base + o_out + first, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  sg.open(ctx->poly_stage);
+  for (size_t c = 0; c < ncols; c++) sg.upload(o_col[c] + first, (const char*)columns[c] + first, bytes);
+  sg.call([&] {
+    for (size_t c = 0; c < ncols; c++) d_cols[c] = sg.at(o_col[c]);
+    return lemsm_gate_eval_device(ctx, prog, d_cols.data(), ncols, logn, logm, coset_begin, coset_count, shift, y, sg.at(o_out), N, bad_index);
+  });
+  sg.download((char*)out + first, o_out + first, bytes);
+  return sg.finish();
 }
 
 }  // extern "C"

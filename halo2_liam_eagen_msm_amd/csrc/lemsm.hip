@@ -16,6 +16,7 @@
 #include "../../include/lemsm.h"
 #include "arena.hpp"
 #include "timed_run.hpp"
+#include "ntt_schedule.hpp"
 #include "hostmath.hpp"
 #include "hostpool.hpp"
 #include "hosttail.hpp"
@@ -122,6 +123,18 @@ struct DevBuf {
 
 struct PyrCacheEntry { DevBuf buf; PyrPlan pp; };   // task tables resident on the device
 
+// The twiddle table of the polynomial entries (poly_abi.inc): omega^t, t < 2^(logn - 1), of one (omega, logn) at a time.
+// A call says need(omega, logn) and gets its Use: upload() puts omega's 32 squarings into the call's workspace when the
+// table has to be built, launch() enqueues the build inside the call's timed section, commit(rc) takes that section's
+// status.  The table is invalid from need() on (its buffer may have been reallocated) until a commit with rc = 0; a Use
+// that needs no build (the table holds the pair already, or logn = 0: no table at all) does nothing in all three.
+struct PolyTable {
+  DevBuf buf;
+  lemsm::host::fe omega = {{0, 0, 0, 0}}; u32 logn = 0; bool valid = false;   // valid: buf holds t < 2^(logn - 1) of this omega
+  struct Use;
+  int need(lemsm_ctx* ctx, const lemsm::host::fe& w, u32 logn_w, Use& use);
+};
+
 }  // namespace
 
 // what a family's *_last entry reports: device time of the last call's kernels, the bytes and field products it was priced at
@@ -158,8 +171,8 @@ struct lemsm_ctx {
   LastStats rhs_last;                // lemsm_rhs_last
   DevBuf col_ws, col_stage;          // column a / poly rlc: function and power tables, staged inputs + outputs (host entries)
   LastStats col_last;                // lemsm_column_last
-  DevBuf poly_ws, poly_stage, poly_tab;   // fft / kate_division / poly_mul: call workspace, staged arrays (host entries), the twiddle table omega^t
-  host::fe poly_tab_omega = {{0, 0, 0, 0}}; u32 poly_tab_logn = 0; bool poly_tab_valid = false;   // ... which holds t < 2^(poly_tab_logn - 1) of this omega
+  DevBuf poly_ws, poly_stage;        // fft / kate_division / poly_mul: call workspace, staged arrays (host entries)
+  PolyTable poly_tab;                // ... and their twiddle table
   LastStats poly_last;               // lemsm_poly_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
@@ -264,6 +277,38 @@ struct Workspace {
   }
 };
 
+// The host twin of a device entry as one scope: take() the staged arrays' sub-buffers, open() on the family's stage buffer,
+// upload(), call() the device entry on at(offset), download(), finish().  The first failure stands and every later step
+// is skipped.  A failed device entry: nothing is downloaded and finish() returns Workspace::done(its status).  A failed
+// runtime call: finish() returns it and the Workspace's destructor waits for the stream.  A copy of no bytes is skipped.
+struct Staged {
+  lemsm_ctx* ctx; Arena ar; Workspace ws; int rc = LEMSM_OK;
+  Staged(lemsm_ctx* c, const char* arena) : ctx(c), ar(arena, c->opt.ws_canary != 0) {}
+  size_t take(const char* name, size_t bytes) { return ar.take(name, bytes); }
+  void open(DevBuf& stage) {
+    const size_t request = ar.total();
+    rc = status(hipSetDevice(ctx->device), "hipSetDevice");
+    if (!rc) rc = ws.open(ctx, std::move(ar), stage, request, ctx->stream);
+  }
+  char* at(size_t off) const { return ws.base + off; }
+  void upload(size_t off, const void* src, size_t bytes) {
+    if (!rc && bytes) rc = status(hipMemcpyAsync(at(off), src, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync (staged input)");
+  }
+  void download(void* dst, size_t off, size_t bytes) {
+    if (!rc && bytes) rc = status(hipMemcpyAsync(dst, at(off), bytes, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync (staged output)");
+  }
+  template <class Entry> void call(Entry&& entry) {
+    if (rc) return;
+    const int r = entry();
+    if (r) rc = ws.done(r);
+  }
+  int finish() {
+    if (!rc) rc = status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return rc ? rc : ws.done(LEMSM_OK);
+  }
+  int status(hipError_t e, const char* what) { return e == hipSuccess ? LEMSM_OK : fail(ctx, LEMSM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+};
+
 // A timed section on a stream between ctx->ev[0] and ctx->ev[1] (timed_run.hpp): `launch` enqueues the kernels, `read_back`
 // the device-to-host copies of results and error words and returns a status; rec.ms = the kernels' device time.  Every
 // exit, the error exits too, has synchronised the stream.
@@ -282,6 +327,10 @@ int timed_run(lemsm_ctx* ctx, hipStream_t st, LastStats& rec, Launch&& launch, R
   HipTimedQueue q{ctx, st};
   return lemsm::timed_run(q, rec.ms, launch, read_back);
 }
+// ... with nothing to read back: the results stay on the device
+struct NoReadBack { int operator()() const { return LEMSM_OK; } };
+template <class Launch>
+int timed_run(lemsm_ctx* ctx, hipStream_t st, LastStats& rec, Launch&& launch) { return timed_run(ctx, st, rec, launch, NoReadBack()); }
 // the four lemsm_*_last entries
 int last_stats(const lemsm_ctx* ctx, const LastStats lemsm_ctx::*rec, double* ms, uint64_t* bytes, uint64_t* field_mults) {
   if (!ctx) return LEMSM_ERR_BAD_ARG;
@@ -1826,7 +1875,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab.buf}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);

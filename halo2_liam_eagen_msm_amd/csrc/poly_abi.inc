@@ -1,8 +1,9 @@
 // halo2::arithmetic's best_fft and kate_division and the reference's Polynomial product as entries on resident data
 // (include/lemsm.h: lemsm_fft_omega, lemsm_fft_half_pow, lemsm_fft_plan, lemsm_fft*, lemsm_kate_division*, lemsm_poly_mul*,
 // lemsm_poly_last; src/regular_functions_utils.rs:17-24, :45-47, :54-62, :102-129, :209-216).  Included at the end of
-// lemsm.hip (it uses lemsm_ctx, Arena, Workspace, timed_run, LastStats / last_stats, HIPCHK, fail, and divisor_abi.inc's
-// HFr / fr_root_of_unity_2_28 / fr_from_u64); the kernels are poly.cuh's and divisor.cuh's k_ntt_tile / k_twiddles.
+// lemsm.hip (it uses lemsm_ctx, Arena, Workspace, Staged, timed_run, LastStats / last_stats, HIPCHK, fail, reserve, and
+// divisor_abi.inc's HFr / fr_root_of_unity_2_28 / fr_from_u64; it defines the members of lemsm.hip's PolyTable); the passes
+// are ntt_schedule.hpp's, the kernels poly.cuh's and divisor.cuh's k_ntt_tile / k_twiddles.
 
 namespace {
 
@@ -32,49 +33,48 @@ host::fe poly_half_pow(u64 e) {
   return acc;
 }
 
-// HBM passes of one transform of 2^logn elements (dw_ntt's tiling: 10 contiguous stages, then strided groups of 8)
-u32 poly_ntt_passes(u32 logn) { return 1u + (logn > 10 ? (logn - 10 + 7) / 8 : 0u); }
+// HBM passes of one transform of 2^logn elements
+u32 poly_ntt_passes(u32 logn) { return lemsm::ntt::passes(logn); }
 
-// the twiddle table omega^t, t < 2^(logn-1), of the context: `build` = it does not hold (omega, logn) and the caller must
-// run k_twiddles from omega's 32 squarings (p2) before the passes, then poly_table_built
-int poly_table_prepare(lemsm_ctx* ctx, const host::fe& omega, u32 logn, bool& build, host::fe p2[32]) {
-  build = !(ctx->poly_tab_valid && ctx->poly_tab_logn == logn && HFr::eq(ctx->poly_tab_omega, omega));
-  if (!build) return LEMSM_OK;
-  ctx->poly_tab_valid = false;   // (the old table is gone whatever happens below)
-  int rc = reserve(ctx, ctx->poly_tab, ((size_t)1 << (logn - 1)) * 32); if (rc) return rc;
-  host::fe w = omega;
-  for (u32 b = 0; b < 32; b++) { p2[b] = w; w = HFr::sqr(w); }
+// PolyTable (lemsm.hip): the one place that reads and writes the table's state.  A Use with tab = NULL has nothing to build.
+struct PolyTable::Use {          // declare it before the call's Workspace: the stream has read p2 when that goes
+  PolyTable* tab = nullptr; host::fe p2[32]; const u32* d_p2 = nullptr;
+  int upload(lemsm_ctx* ctx, u32* d_squarings, hipStream_t st) {
+    if (tab) HIPCHK(ctx, hipMemcpyAsync(d_squarings, p2, sizeof p2, hipMemcpyHostToDevice, st));
+    d_p2 = d_squarings;
+    return LEMSM_OK;
+  }
+  void launch(hipStream_t st) const {
+    if (!tab) return;
+    const u32 count = 1u << (tab->logn - 1);
+    hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((count + 255) / 256), dim3(256), 0, st, d_p2, tab->logn - 1, count, (u32*)tab->buf.p);
+  }
+  int commit(int rc) { if (tab && !rc) tab->valid = true; return rc; }
+};
+int PolyTable::need(lemsm_ctx* ctx, const host::fe& w, u32 logn_w, Use& use) {
+  use.tab = nullptr;
+  if (logn_w == 0 || (valid && logn == logn_w && HFr::eq(omega, w))) return LEMSM_OK;
+  valid = false;                 // (the old table is gone whatever happens below; omega and logn say what is being built)
+  int rc = reserve(ctx, buf, ((size_t)1 << (logn_w - 1)) * 32); if (rc) return rc;
+  use.tab = this; omega = w; logn = logn_w;
+  for (u32 b = 0; b < 32; b++) use.p2[b] = b ? HFr::sqr(use.p2[b - 1]) : w;
   return LEMSM_OK;
 }
-void poly_table_launch(lemsm_ctx* ctx, hipStream_t st, const u32* d_p2, u32 logn) {
-  const u32 count = 1u << (logn - 1);
-  hipLaunchKernelGGL(lemsm::dw::k_twiddles, dim3((count + 255) / 256), dim3(256), 0, st, d_p2, logn - 1, count, (u32*)ctx->poly_tab.p);
-}
-void poly_table_built(lemsm_ctx* ctx, const host::fe& omega, u32 logn) { ctx->poly_tab_omega = omega; ctx->poly_tab_logn = logn; ctx->poly_tab_valid = true; }
 
 // the passes of nseq transforms of 2^logN elements (logN >= 1) over the context's table, which holds exactly 2^logN's
 // roots.  Forward: decimation in frequency, natural -> bit-reversed; inverse: decimation in time with omega^-1, back.
 void poly_ntt(lemsm_ctx* ctx, hipStream_t st, u32* buf, u32 nseq, u32 logN, bool inverse) {
   using lemsm::dw::TileIO; using lemsm::dw::k_ntt_tile;
-  const u32* W = (const u32*)ctx->poly_tab.p;
+  const u32* W = (const u32*)ctx->poly_tab.buf.p;
   const u32 lhm = logN - 1;
   const u64 total = (u64)nseq << logN;
-  const u32 S0 = std::min(logN, 10u);
   TileIO none; memset(&none, 0, sizeof none);
   const dim3 blk(256), gcont((u32)((total + 1023) / 1024)), gstr((u32)(total >> 10));   // strided: every block owns 1024 elements
-  auto launch = [&](dim3 grid, u32 lo, u32 S) {
-    if (!inverse) hipLaunchKernelGGL((k_ntt_tile<false, 0>), grid, blk, 0, st, buf, total, logN, lo, S, W, lhm, none, (const u32*)buf);
-    else hipLaunchKernelGGL((k_ntt_tile<true, 0>), grid, blk, 0, st, buf, total, logN, lo, S, W, lhm, none, (const u32*)buf);
-  };
-  struct Pass { u32 lo, S; };
-  std::vector<Pass> up;                    // ascending spans
-  for (u32 lo = S0; lo < logN;) { const u32 S = std::min(8u, logN - lo); up.push_back({lo, S}); lo += S; }
-  if (!inverse) {
-    for (size_t i = up.size(); i-- > 0;) launch(gstr, up[i].lo, up[i].S);
-    launch(gcont, 0u, S0);
-  } else {
-    launch(gcont, 0u, S0);
-    for (size_t i = 0; i < up.size(); i++) launch(gstr, up[i].lo, up[i].S);
+  const lemsm::ntt::Schedule sch = lemsm::ntt::schedule(logN, inverse);
+  for (u32 i = 0; i < sch.count; i++) {
+    const lemsm::ntt::Pass& p = sch.pass[i];
+    if (!inverse) hipLaunchKernelGGL((k_ntt_tile<false, 0>), p.strided ? gstr : gcont, blk, 0, st, buf, total, logN, p.lo, p.S, W, lhm, none, (const u32*)buf);
+    else hipLaunchKernelGGL((k_ntt_tile<true, 0>), p.strided ? gstr : gcont, blk, 0, st, buf, total, logN, p.lo, p.S, W, lhm, none, (const u32*)buf);
   }
 }
 
@@ -197,42 +197,36 @@ int lemsm_fft_device(lemsm_ctx* ctx, void* d_data, size_t nseq, uint32_t logn, c
   if (logn == 0 && !reorder) return LEMSM_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const host::fe w = poly_fe(omega);
-  host::fe up[33]; bool build = false;
-  if (logn) { rc = poly_table_prepare(ctx, w, logn, build, up); if (rc) return rc; }
-  if (scale) up[32] = poly_fe(scale);
+  const host::fe factor = scale ? poly_fe(scale) : HFr::one();
+  PolyTable::Use tw;
+  rc = ctx->poly_tab.need(ctx, poly_fe(omega), logn, tw); if (rc) return rc;
   Arena ar("poly_ws", ctx->opt.ws_canary != 0);
   const size_t o_pw = ar.take("powers", 32 * 32), o_sc = ar.take("scale", 32);
-  Workspace ws;   // (behind up: the stream has read it when it goes)
+  Workspace ws;   // (behind tw and factor: the stream has read them when it goes)
   rc = ws.open(ctx, std::move(ar), ctx->poly_ws, ar.total(), st); if (rc) return rc;
-  if (build) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_pw), up, 32 * 32, hipMemcpyHostToDevice, st));
-  if (scale) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_sc), &up[32], 32, hipMemcpyHostToDevice, st));
+  rc = tw.upload(ctx, ws.at<u32>(o_pw), st); if (rc) return rc;
+  if (scale) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_sc), &factor, 32, hipMemcpyHostToDevice, st));
   rc = timed_run(ctx, st, ctx->poly_last, [&] {
-    if (build) poly_table_launch(ctx, st, ws.at<u32>(o_pw), logn);
+    tw.launch(st);
     if (logn) poly_ntt(ctx, st, (u32*)d_data, (u32)nseq, logn, false);
     if (reorder) hipLaunchKernelGGL(pl::k_fft_reorder, dim3((u32)((total + 255) / 256)), dim3(256), 0, st, (uint4*)d_data, total, logn,
                                     scale ? (const uint4*)ws.at<uint4>(o_sc) : (const uint4*)nullptr);
-  }, [] { return LEMSM_OK; });
-  if (!rc && build) poly_table_built(ctx, w, logn);
-  return ws.done(rc);
+  });
+  return ws.done(tw.commit(rc));
 }
 
 int lemsm_fft(lemsm_ctx* ctx, const uint64_t* in, uint64_t* out, size_t nseq, uint32_t logn, const uint64_t omega[4], const uint64_t* scale) {
   if (!ctx) return LEMSM_ERR_BAD_ARG;
   int rc = poly_fft_check(ctx, nseq, logn, omega, scale); if (rc) return rc;
   if (!in || !out) return LEMSM_ERR_BAD_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (nseq << logn) * 32;
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_d = ar.take("data", bytes);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ws.base + o_d, in, bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_fft_device(ctx, ws.base + o_d, nseq, logn, omega, scale);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out, ws.base + o_d, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_d = sg.take("data", bytes);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_d, in, bytes);
+  sg.call([&] { return lemsm_fft_device(ctx, sg.at(o_d), nseq, logn, omega, scale); });
+  sg.download(out, o_d, bytes);
+  return sg.finish();
 }
 
 int lemsm_kate_division_device(lemsm_ctx* ctx, const void* d_in, size_t cap_in, const size_t* index, size_t T, const uint64_t b[4],
@@ -272,7 +266,7 @@ int lemsm_kate_division_device(lemsm_ctx* ctx, const void* d_in, size_t cap_in, 
     hipLaunchKernelGGL(pl::k_kd_partial, gseg, blk, 0, st, (const uint4*)d_in, (const pl::KdRow*)d_rows, (u32)T, kp.nseg, kp.S, (const uint4*)d_tab, d_H);
     hipLaunchKernelGGL(pl::k_kd_scan, dim3((u32)T), dim3(pl::KD_CHUNKS), 0, st, d_H, (const pl::KdRow*)d_rows, kp.S, (const uint4*)d_tab);
     hipLaunchKernelGGL(pl::k_kd_finish, gseg, blk, 0, st, (const uint4*)d_in, (const pl::KdRow*)d_rows, (u32)T, kp.nseg, kp.S, (const uint4*)d_tab, (const uint4*)d_H, (uint4*)d_out);
-  }, [] { return LEMSM_OK; });
+  });
   return ws.done(rc);
 }
 
@@ -286,19 +280,14 @@ int lemsm_kate_division(lemsm_ctx* ctx, const uint64_t* in, size_t cap_in, const
     return lemsm_kate_division_device(ctx, nullptr, cap_in, index, T, b, nullptr, cap_out, bad_index);
   if (!in || (kp.need_out && !out)) return LEMSM_ERR_BAD_ARG;
   if (poly_overlap(in, cap_in * 32, out, cap_out * 32)) return fail(ctx, LEMSM_ERR_BAD_ARG, "kate_division: out overlaps in");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_in = ar.take("coefficients", kp.need_in * 32), o_out = ar.take("quotients", std::max<size_t>(kp.need_out, 1) * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ws.base + o_in, in, kp.need_in * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_kate_division_device(ctx, ws.base + o_in, kp.need_in, index, T, b, ws.base + o_out, kp.need_out, bad_index);
-  if (rc) return ws.done(rc);
-  for (size_t t = 0; t < T; t++)
-    if (kp.rows[t].len > 1)
-      HIPCHK(ctx, hipMemcpyAsync(out + 4 * kp.rows[t].off, ws.base + o_out + 32 * kp.rows[t].off, (size_t)(kp.rows[t].len - 1) * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_in = sg.take("coefficients", kp.need_in * 32), o_out = sg.take("quotients", std::max<size_t>(kp.need_out, 1) * 32);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_in, in, kp.need_in * 32);
+  sg.call([&] { return lemsm_kate_division_device(ctx, sg.at(o_in), kp.need_in, index, T, b, sg.at(o_out), kp.need_out, bad_index); });
+  for (size_t t = 0; t < T; t++)   // one copy per row: the cells between the quotients are the caller's
+    sg.download(out + 4 * kp.rows[t].off, o_out + 32 * kp.rows[t].off, (size_t)(kp.rows[t].len - 1) * 32);
+  return sg.finish();
 }
 
 int lemsm_poly_mul_device(lemsm_ctx* ctx, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t cap_out, size_t* len_out) {
@@ -315,18 +304,18 @@ int lemsm_poly_mul_device(lemsm_ctx* ctx, const void* d_a, size_t la, const void
   hipStream_t st = ctx->stream;
   const u32 len = (u32)mp.len, logN = mp.logN;
   const size_t N = (size_t)1 << logN;
-  host::fe up[33]; bool build = false; host::fe w = HFr::one();
+  PolyTable::Use tw;                       // (modes 0 and 1 need no table)
+  host::fe factor = HFr::one();
   if (mp.mode == 2) {
-    w = poly_omega(logN, false);
-    rc = poly_table_prepare(ctx, w, logN, build, up); if (rc) return rc;
-    up[32] = poly_half_pow(logN);
+    rc = ctx->poly_tab.need(ctx, poly_omega(logN, false), logN, tw); if (rc) return rc;
+    factor = poly_half_pow(logN);
   }
   Arena ar("poly_ws", ctx->opt.ws_canary != 0);
   const size_t o_pw = ar.take("powers", 32 * 32), o_sc = ar.take("scale", 32), o_buf = ar.take("transform", mp.mode == 2 ? 2 * N * 32 : 32);
-  Workspace ws;   // (behind up: the stream has read it when it goes)
+  Workspace ws;   // (behind tw and factor: the stream has read them when it goes)
   rc = ws.open(ctx, std::move(ar), ctx->poly_ws, ar.total(), st); if (rc) return rc;
-  if (build) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_pw), up, 32 * 32, hipMemcpyHostToDevice, st));
-  if (mp.mode == 2) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_sc), &up[32], 32, hipMemcpyHostToDevice, st));
+  rc = tw.upload(ctx, ws.at<u32>(o_pw), st); if (rc) return rc;
+  if (mp.mode == 2) HIPCHK(ctx, hipMemcpyAsync(ws.at<char>(o_sc), &factor, 32, hipMemcpyHostToDevice, st));
   uint4* buf = ws.at<uint4>(o_buf);
   hipError_t cerr = hipSuccess;
   rc = timed_run(ctx, st, ctx->poly_last, [&] {
@@ -337,16 +326,15 @@ int lemsm_poly_mul_device(lemsm_ctx* ctx, const void* d_a, size_t la, const void
                          (const uint4*)(a_short ? d_b : d_a), (u32)(a_short ? lb : la), (uint4*)d_out);
       return;
     }
-    if (build) poly_table_launch(ctx, st, ws.at<u32>(o_pw), logN);
+    tw.launch(st);
     hipLaunchKernelGGL(pl::k_poly_pad, dim3((u32)((4 * N + 255) / 256)), dim3(256), 0, st, (const uint4*)d_a, (u32)la, (const uint4*)d_b, (u32)lb, logN, buf);
     poly_ntt(ctx, st, (u32*)buf, 2, logN, false);
     hipLaunchKernelGGL(pl::k_poly_pointwise, dim3((u32)((N + 255) / 256)), dim3(256), 0, st, buf, (const uint4*)(buf + 2 * N), (u32)N, (const uint4*)ws.at<uint4>(o_sc));
     poly_ntt(ctx, st, (u32*)buf, 1, logN, true);
     cerr = hipMemcpyAsync(d_out, buf, mp.len * 32, hipMemcpyDeviceToDevice, st);      // the truncated copy out
-  }, [] { return LEMSM_OK; });
+  });
   if (!rc && cerr != hipSuccess) rc = fail(ctx, LEMSM_ERR_HIP, std::string("poly_mul: ") + hipGetErrorString(cerr));
-  if (!rc && build) poly_table_built(ctx, w, logN);
-  return ws.done(rc);
+  return ws.done(tw.commit(rc));
 }
 
 int lemsm_poly_mul(lemsm_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* out, size_t cap_out, size_t* len_out) {
@@ -357,18 +345,14 @@ int lemsm_poly_mul(lemsm_ctx* ctx, const uint64_t* a, size_t la, const uint64_t*
     return lemsm_poly_mul_device(ctx, nullptr, la, nullptr, lb, nullptr, cap_out, len_out);
   if (!out || (la && !a) || (lb && !b)) return LEMSM_ERR_BAD_ARG;
   if (poly_overlap(out, mp.len * 32, a, la * 32) || poly_overlap(out, mp.len * 32, b, lb * 32)) return fail(ctx, LEMSM_ERR_BAD_ARG, "poly_mul: out overlaps an operand");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  Arena ar("poly_staged", ctx->opt.ws_canary != 0);
-  const size_t o_a = ar.take("a", std::max<size_t>(la, 1) * 32), o_b = ar.take("b", std::max<size_t>(lb, 1) * 32), o_out = ar.take("product", mp.len * 32);
-  Workspace ws;
-  rc = ws.open(ctx, std::move(ar), ctx->poly_stage, ar.total(), ctx->stream); if (rc) return rc;
-  if (la) HIPCHK(ctx, hipMemcpyAsync(ws.base + o_a, a, la * 32, hipMemcpyHostToDevice, ctx->stream));
-  if (lb) HIPCHK(ctx, hipMemcpyAsync(ws.base + o_b, b, lb * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = lemsm_poly_mul_device(ctx, ws.base + o_a, la, ws.base + o_b, lb, ws.base + o_out, mp.len, len_out);
-  if (rc) return ws.done(rc);
-  HIPCHK(ctx, hipMemcpyAsync(out, ws.base + o_out, mp.len * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return ws.done(LEMSM_OK);
+  Staged sg(ctx, "poly_staged");
+  const size_t o_a = sg.take("a", std::max<size_t>(la, 1) * 32), o_b = sg.take("b", std::max<size_t>(lb, 1) * 32), o_out = sg.take("product", mp.len * 32);
+  sg.open(ctx->poly_stage);
+  sg.upload(o_a, a, la * 32);
+  sg.upload(o_b, b, lb * 32);
+  sg.call([&] { return lemsm_poly_mul_device(ctx, sg.at(o_a), la, sg.at(o_b), lb, sg.at(o_out), mp.len, len_out); });
+  sg.download(out, o_out, mp.len * 32);
+  return sg.finish();
 }
 
 int lemsm_poly_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults) { return last_stats(ctx, &lemsm_ctx::poly_last, ms, bytes, field_mults); }

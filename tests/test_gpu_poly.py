@@ -366,6 +366,71 @@ def test_entries_under_workspace_guards(ctx):
         ctx.set_option("ws_canary", 0)
 
 
+# ---- the context's twiddle table -------------------------------------------------------------------------------------------
+def _table_walk(ctx):
+    """one context, the entries that share its twiddle table in an order that crosses every transition: build, reuse,
+    another root at the same size, a larger table, a smaller one in place, two entries on one table, a refused call"""
+    def fft(logn, inverse):
+        data, omega, want = _fft_case(logn, inverse)
+        n = 1 << logn
+        buf = _filled(ctx, n, data[:n])
+        ctx.fft_device(buf.ptr, 1, logn, omega)
+        got = buf.download(np.uint8)
+        buf.free()
+        assert got[:n * 32].tobytes() == _arr(want[:n]).tobytes(), (logn, inverse)
+        assert (got[n * 32:] == 0xFF).all(), "the zone behind the data was written"
+
+    fft(11, 0)                                                                     # 1: whatever the table held, it is built
+    fft(11, 0)                                                                     # 2: reused
+    fft(11, 1)                                                                     # 3: the same size, omega^-1
+    fft(12, 0)                                                                     # 4: grows (the smallest size with a strided pass)
+    p, q = _rand(9702, 70), _rand(9703, 45)                                        # 5: the product's own root at 2^7, in place
+    rc, n, got = _mul_device(ctx, p, q, 114)
+    assert rc == _lib.LEMSM_OK and n == 114
+    assert got[:114 * 32].tobytes() == _arr([v * RI % P for v in RING.mul(_ints(p), _ints(q))]).tobytes()
+    assert (got[114 * 32:] == 0xFF).all(), "written past the product"
+    logn, logm = 8, 2                                                              # 6: two entries, one table of 2^8
+    n, m = 1 << logn, 1 << logm
+    N, g = n * m, 5
+    coeffs = _rand(9704, n)
+    w, w_ext = _std(api.omega_pow(28 - logn)), _std(api.omega_pow(28 - logn - logm))
+    want = []
+    for c in range(m):                                                             # coset c: the values at g w_ext^c w^r
+        s = g * pow(w_ext, c, P) % P
+        seq = [a * pow(s, j, P) % P for j, a in enumerate(_ints(coeffs))]
+        best_fft(seq, w, logn, P)
+        want += seq
+    d_in, ext, back = ctx.to_device(coeffs), _filled(ctx, N), _filled(ctx, N)
+    ctx.coeff_to_extended_device(d_in.ptr, n, logn, logm, _fe(g), ext.ptr, N, api.EXT_COSET_MAJOR)
+    got = ext.download(np.uint8)
+    assert got[:N * 32].tobytes() == _arr(want).tobytes() and (got[N * 32:] == 0xFF).all()
+    ctx.extended_to_coeff_device(ext.ptr, logn, logm, _fe(g), back.ptr, N, api.EXT_COSET_MAJOR)
+    got = back.download(np.uint8)
+    assert got[:N * 32].tobytes() == coeffs.tobytes() + bytes((N - n) * 32) and (got[N * 32:] == 0xFF).all()
+    for x in (d_in, ext, back):
+        x.free()
+    data, omega, _ = _fft_case(11, 0)                                              # 7: refused before any GPU work ...
+    buf = _filled(ctx, 1 << 11, data[:1 << 11])
+    before = buf.download(np.uint8).tobytes()
+    for _ in range(2):                                                             # ... over another table, then over its own
+        not_primitive = api.omega_pow(28 - 12)
+        assert ctx.lib.lemsm_fft_device(ctx.h, buf.ptr, 1, 11, not_primitive.ctypes.data, None) == BAD_ARG
+        assert buf.download(np.uint8).tobytes() == before
+        fft(11, 0)
+    buf.free()
+
+
+def test_twiddle_table_transitions(ctx):
+    """the table of (omega, logn) a context keeps between calls: every result byte for byte, whichever table the call found;
+    once more with option ws_canary = 1 (the squarings' sub-buffer is guarded like every other)"""
+    _table_walk(ctx)
+    ctx.set_option("ws_canary", 1)
+    try:
+        _table_walk(ctx)
+    finally:
+        ctx.set_option("ws_canary", 0)
+
+
 # ---- the chain: witnesses -> column a -> coefficient form -> evaluation -> opening ----------------------------------------
 def test_chain_from_resident_witnesses(ctx):
     n, base = 64, 16

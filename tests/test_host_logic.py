@@ -231,6 +231,20 @@ def test_timed_run_synchronises_on_every_exit(tmp_path):
     assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
+def test_ntt_schedule_covers_every_stage_once(tmp_path):
+    """the pass schedule of the transforms (csrc/ntt_schedule.hpp) alone (tests/ntt_schedule_check.cpp, under
+    -fsanitize=address,undefined), logN 0 to 28 in both directions: every stage in exactly one pass, one contiguous pass of
+    min(logN, 10) stages and strided ones of at most 8, forward = inverse reversed, the count equal to the closed form
+    1 + ceil((logN - 10) / 8) the plans have reported so far"""
+    import subprocess
+    exe = tmp_path / "ntt_schedule_check"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-o", str(exe), os.path.join(ROOT, "tests", "ntt_schedule_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "ntt schedule ok" in out.stdout, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
 def test_oracle_c_under_asan_ubsan():
     """the C oracle (test infrastructure) rebuilt with -fsanitize=address,undefined (`make -C oracle asan`) and the golden-vector
     tests of tests/test_oracle_golden.py run against that build in a child interpreter with libasan preloaded"""
