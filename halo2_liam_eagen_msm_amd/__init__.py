@@ -16,4 +16,5 @@ from .api import (  # noqa: F401
     column_plan, assemble_column_a, compute_poly_rlc,
     fft_plan, omega_pow, omega_pow_inv, half_pow, best_fft, kate_division, eval_polynomial, polynomial_mul,
     domain_plan, vanishing_on_cosets, EXT_INTERLEAVED, EXT_COSET_MAJOR,
+    fraction_products_geometry, permutation_plan, permutation_products,
 )

@@ -74,6 +74,8 @@ SYMBOLS = [
     "lemsm_domain_plan", "lemsm_vanishing_on_cosets", "lemsm_coset_fft_device", "lemsm_coset_ifft_device", "lemsm_coset_fft", "lemsm_coset_ifft",
     "lemsm_coeff_to_extended_device", "lemsm_extended_to_coeff_device", "lemsm_coeff_to_extended", "lemsm_extended_to_coeff",
     "lemsm_gate_plan", "lemsm_gate_eval_device", "lemsm_gate_eval",
+    "lemsm_fraction_products_geometry", "lemsm_fraction_products_device", "lemsm_fraction_products",
+    "lemsm_permutation_plan", "lemsm_permutation_product_device", "lemsm_permutation_product",
 ]
 
 
@@ -255,6 +257,12 @@ def load() -> ctypes.CDLL:
         "lemsm_gate_plan": (i, [ctypes.POINTER(GateProgram), sz, u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), szp]),
         "lemsm_gate_eval_device": (i, [vp, ctypes.POINTER(GateProgram), vp, sz] + [ctypes.c_uint32] * 4 + [u64p, u64p, vp, sz, szp]),
         "lemsm_gate_eval": (i, [vp, ctypes.POINTER(GateProgram), vp, sz] + [ctypes.c_uint32] * 4 + [u64p, u64p, u64p, sz, szp]),
+        "lemsm_fraction_products_geometry": (i, [sz, szp, szp, szp]),
+        "lemsm_fraction_products_device": (i, [vp, vp, sz, vp, sz, sz, u64p, vp, sz, u64p, szp]),
+        "lemsm_fraction_products": (i, [vp, vp, sz, vp, sz, sz, u64p, u64p, sz, u64p, szp]),
+        "lemsm_permutation_plan": (i, [ctypes.c_uint32, sz, sz, szp] + [ctypes.POINTER(ctypes.c_uint64)] * 3),
+        "lemsm_permutation_product_device": (i, [vp, vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p, sz, sz, vp, u64p, szp]),
+        "lemsm_permutation_product": (i, [vp, vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p, sz, sz, vp, u64p, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -950,6 +950,92 @@ class Context:
         self._check(rc, bad.value)
         return out[coset_begin * n:(coset_begin + count) * n].copy()
 
+    # ---- permutation and lookup grand products on resident columns ----
+    def fraction_products_device(self, d_num: Sequence[int], d_den: Sequence[int], n: int, init=None, out: Optional[DeviceBuffer] = None,
+                                 want_out: bool = True, tap: Optional[int] = None):
+        """out[r] = init prod_{i < r} (prod_j num_j[i] / prod_j den_j[i]) on n resident bn256::Fr elements per column (device
+        pointers, up to 8 a side; init None: 1): halo2's lookup product once the factor columns are formed.  tap (None: n)
+        names the row whose value comes back; tap == n is the product over all rows.  RefDivisionByZero (.index = the lowest
+        row) when a row's denominators multiply to zero.  (DeviceBuffer (n, 4) or None, tap value (4,))"""
+        ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(4)
+        if want_out and out is None:
+            out = DeviceBuffer(self, max(n * 32, 16))
+        nums = (ctypes.c_void_p * max(len(d_num), 1))(*[int(c) for c in d_num])
+        dens = (ctypes.c_void_p * max(len(d_den), 1))(*[int(c) for c in d_den])
+        tapped = np.zeros(4, np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_fraction_products_device(self.h, nums, len(d_num), dens, len(d_den), n, _ptr(ini) if ini is not None else None,
+                                                     out.ptr if want_out else None, n if tap is None else tap, _ptr(tapped), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return (out if want_out else None), tapped
+
+    def fraction_products(self, num, den, init=None, want_out: bool = True, tap: Optional[int] = None, n: Optional[int] = None):
+        """the same from host memory: num, den are sequences of (n, 4) uint64 columns (n is needed only when both are empty);
+        (products (n, 4) or None, tap value (4,))"""
+        nm = [_limbs(c, 4) if np.size(c) else np.zeros((0, 4), np.uint64) for c in num]
+        dn = [_limbs(c, 4) if np.size(c) else np.zeros((0, 4), np.uint64) for c in den]
+        if n is None:
+            n = (nm + dn)[0].shape[0] if nm or dn else 0
+        if any(c.shape[0] != n for c in nm + dn):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "a column is not n elements")
+        ini = None if init is None else np.ascontiguousarray(init, np.uint64).reshape(4)
+        nums = (ctypes.c_void_p * max(len(nm), 1))(*[_ptr(c) for c in nm])
+        dens = (ctypes.c_void_p * max(len(dn), 1))(*[_ptr(c) for c in dn])
+        out = np.zeros((n, 4), np.uint64) if want_out else None
+        tapped = np.zeros(4, np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_fraction_products(self.h, nums, len(nm), dens, len(dn), n, _ptr(ini) if ini is not None else None,
+                                              _ptr(out) if want_out and n else None, n if tap is None else tap, _ptr(tapped), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out, tapped
+
+    def _perm_args(self, beta, gamma, delta):
+        return tuple(np.ascontiguousarray(x, np.uint64).reshape(4) for x in (beta, gamma, delta))
+
+    def permutation_product_device(self, d_values: Sequence[int], d_sigmas: Sequence[int], logn: int, beta, gamma, delta, chunk_len: int,
+                                   usable_row: int, d_z: Optional[Sequence[int]] = None):
+        """The product columns of halo2's permutation argument (permutation::Argument::commit; src/config.rs:228) over
+        ncols value and permutation columns of 2^logn resident Lagrange values (device pointers):
+        z_s[r] = init_s prod_{i < r} prod_j (v_j[i] + beta delta^j w^i + gamma) / (v_j[i] + beta sigma_j[i] + gamma) over the
+        columns j of set s (chunk_len columns each), init_0 = 1, init_{s+1} = z_s[usable_row].  d_z: one device pointer per
+        set (None: allocated here).  RefDivisionByZero (.index = s 2^logn + row).  (z columns, taps (nsets, 4) = z_s[usable_row])"""
+        if len(d_values) != len(d_sigmas):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "one permutation column per value column")
+        ncols, n = len(d_values), 1 << logn
+        nsets = -(-ncols // chunk_len) if chunk_len > 0 else 0
+        b, g, d = self._perm_args(beta, gamma, delta)
+        zs = [DeviceBuffer(self, n * 32) for _ in range(nsets)] if d_z is None else list(d_z)
+        vals = (ctypes.c_void_p * max(ncols, 1))(*[int(c) for c in d_values])
+        sigs = (ctypes.c_void_p * max(ncols, 1))(*[int(c) for c in d_sigmas])
+        zp = (ctypes.c_void_p * max(len(zs), 1))(*[int(z.ptr if isinstance(z, DeviceBuffer) else z) for z in zs])
+        taps = np.zeros((max(nsets, 1), 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_permutation_product_device(self.h, vals, sigs, ncols, logn, _ptr(b), _ptr(g), _ptr(d), chunk_len, usable_row,
+                                                       zp, _ptr(taps), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return zs, taps[:nsets]
+
+    def permutation_product(self, values, sigmas, logn: int, beta, gamma, delta, chunk_len: int, usable_row: int):
+        """permutation_product_device for columns in host memory ((2^logn, 4) uint64 each): (z (nsets, 2^logn, 4), taps (nsets, 4))"""
+        n = 1 << logn
+        vs = [_limbs(c, 4) for c in values]
+        ss = [_limbs(c, 4) for c in sigmas]
+        if len(vs) != len(ss) or any(c.shape[0] != n for c in vs + ss):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "one permutation column per value column, 2^logn elements each")
+        ncols = len(vs)
+        nsets = -(-ncols // chunk_len) if chunk_len > 0 else 0
+        b, g, d = self._perm_args(beta, gamma, delta)
+        z = np.zeros((max(nsets, 1), n, 4), np.uint64)
+        vals = (ctypes.c_void_p * max(ncols, 1))(*[_ptr(c) for c in vs])
+        sigs = (ctypes.c_void_p * max(ncols, 1))(*[_ptr(c) for c in ss])
+        zp = (ctypes.c_void_p * max(nsets, 1))(*[_ptr(z[s]) for s in range(nsets)])
+        taps = np.zeros((max(nsets, 1), 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_permutation_product(self.h, vals, sigs, ncols, logn, _ptr(b), _ptr(g), _ptr(d), chunk_len, usable_row, zp,
+                                                _ptr(taps), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return z[:nsets], taps[:nsets]
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -1745,6 +1831,41 @@ def polynomial_mul(p, q, ctx: Optional[Context] = None) -> np.ndarray:
     """&p * &q of the reference's Polynomial (impl Mul, :209-216): (la + lb - 1, 4); RefArithmeticOverflow for two empty
     operands (:55)"""
     return (ctx or default_context()).poly_mul(p, q)
+
+
+def fraction_products_geometry(n: int) -> dict:
+    """the scan geometry of fraction_products* / permutation_product* for n terms (pure host:
+    lemsm_fraction_products_geometry): {"tile", "segment", "block_segments"}"""
+    lib = _lib.load()
+    t = ctypes.c_size_t(); s = ctypes.c_size_t(); b = ctypes.c_size_t()
+    rc = lib.lemsm_fraction_products_geometry(n, ctypes.byref(t), ctypes.byref(s), ctypes.byref(b))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"tile": t.value, "segment": s.value, "block_segments": b.value}
+
+
+def permutation_plan(logn: int, ncols: int, chunk_len: int) -> dict:
+    """validates (logn, ncols, chunk_len) and prices one permutation_product_device call (pure host: lemsm_permutation_plan;
+    DESIGN 7f): {"nsets", "bytes", "field_mults", "workspace_bytes"}; raises LemsmError (LEMSM_ERR_BAD_ARG) where the entry would"""
+    lib = _lib.load()
+    if logn < 0 or ncols < 0 or chunk_len < 0:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "permutation_plan: negative argument")
+    ns = ctypes.c_size_t(); by = ctypes.c_uint64(); fm = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_permutation_plan(logn, ncols, chunk_len, ctypes.byref(ns), ctypes.byref(by), ctypes.byref(fm), ctypes.byref(wb))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"nsets": ns.value, "bytes": by.value, "field_mults": fm.value, "workspace_bytes": wb.value}
+
+
+def permutation_products(columns, sigmas, beta, gamma, delta, usable_row: int, chunk_len: int, ctx: Optional[Context] = None) -> np.ndarray:
+    """the product columns z_s of halo2's permutation argument (the witness part of permutation::Argument::commit) for value
+    columns `columns` and permutation columns `sigmas` ((n, 4) raw Montgomery limbs each, n a power of two), before blinding:
+    (nsets, n, 4), z_s[0] = z_{s-1}[usable_row] (1 for s = 0); the rows above usable_row are the caller's to blind"""
+    cols = [_limbs(c, 4) for c in columns]
+    n = cols[0].shape[0] if cols else 1
+    if n & (n - 1) or n == 0:
+        raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the columns are not 2^logn elements")
+    return (ctx or default_context()).permutation_product(cols, sigmas, n.bit_length() - 1, beta, gamma, delta, chunk_len, usable_row)[0]
 
 
 def _neg_affine_raw(curve_id: int, pts: np.ndarray) -> np.ndarray:

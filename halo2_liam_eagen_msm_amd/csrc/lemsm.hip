@@ -32,6 +32,7 @@
 #include "poly.cuh"
 #include "domain.cuh"
 #include "gate.cuh"
+#include "perm.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -2783,3 +2784,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "poly_abi.inc"
 #include "domain_abi.inc"
 #include "gate_abi.inc"
+#include "perm_abi.inc"

@@ -696,8 +696,9 @@ int lemsm_extended_to_coeff(lemsm_ctx* ctx, const uint64_t* evals, uint32_t logn
    Columns: one buffer of N = m n raw Montgomery elements each, in LEMSM_EXT_COSET_MAJOR -- the only layout these entries
    take: point (c, r) = s_c w^r (the definitions above) lies at element c n + r, and a query with rotation i reads row
    (r + i) mod n of the same coset, i.e. the column's polynomial at w^i X.  bn256::Fr, the conventions of the entries
-   above.  The permutation and lookup grand products of halo2, the placement of rows and blinding stay with the caller:
-   LEMSM_GATE_PUSH_X and fixed columns make their terms expressible, nothing here builds them. */
+   above.  The placement of rows and blinding stay with the caller.  LEMSM_GATE_PUSH_X and fixed columns make the terms of
+   halo2's permutation and lookup arguments expressible; their grand product columns are built by
+   lemsm_permutation_product* and lemsm_fraction_products* below. */
 enum {  /* low 8 bits of a code word; operand = word >> 8 (zero for the opcodes that take none) */
   LEMSM_GATE_PUSH_CELL = 0,    /* q: push columns[queries[q].column] at row (r + queries[q].rotation) mod n of coset c */
   LEMSM_GATE_PUSH_CONST = 1,   /* k: push consts[k] (challenges are constants of a call) */
@@ -757,6 +758,67 @@ int lemsm_gate_eval_device(lemsm_ctx* ctx, const lemsm_gate_program* prog, const
 int lemsm_gate_eval(lemsm_ctx* ctx, const lemsm_gate_program* prog, const uint64_t* const* columns, size_t ncols, uint32_t logn, uint32_t logm,
                     uint32_t coset_begin, uint32_t coset_count, const uint64_t* shift, const uint64_t y[4], uint64_t* out, size_t cap_out,
                     size_t* bad_index);
+
+/* ---- permutation and lookup grand products on resident columns (src/config.rs:228) --------------------------
+   The product columns z of halo2's permutation and lookup arguments, built from columns resident in HBM.  bn256::Fr,
+   32-byte raw Montgomery elements, the conventions of the lemsm_fft* / lemsm_gate* entries: LEMSM_ERR_BAD_ARG leaves
+   nothing queued and the outputs untouched, field arguments must be canonical, the figures of every call go to
+   lemsm_poly_last, option ws_canary guards every carved workspace.  Field multiplication is exact, so the host entry, the
+   device entry and repeated calls give the same bytes whatever the association of the products.  The mapping to
+   halo2_proofs' plonk/permutation/prover.rs and plonk/lookup/prover.rs is stated from memory; the formulas here are the
+   contract. */
+/* Pure host: the geometry of the engine's scan for n terms (tests size their cases by it).  tile: terms one block of the
+   batched inversion owns; segment: consecutive terms one thread of the scan multiplies up; block_segments: up to this many
+   segments the one scanning block takes one per thread, beyond it several.  n >= 2^40: LEMSM_ERR_BAD_ARG. */
+int lemsm_fraction_products_geometry(size_t n, size_t* tile, size_t* segment, size_t* block_segments);
+/* The engine: running products of fractions.  d_num: n_num device pointers, d_den: n_den device pointers (each count
+   0 .. 8, an empty product is 1), n elements each, n arbitrary.  Term i is f_i = prod_j num_j[i] / prod_j den_j[i];
+   d_out[r] = init prod_{i < r} f_i for r = 0 .. n - 1, so d_out[0] = init; init == NULL means 1.  d_out may be NULL.
+   out_tap (4 limbs, optional) = d_out[tap] for tap < n and init prod_{i < n} f_i for tap == n; tap > n: LEMSM_ERR_BAD_ARG.
+   n == 0 is LEMSM_OK with out_tap = init.
+   A row i < n whose denominators multiply to zero is LEMSM_ERR_DIVISION_BY_ZERO, whatever its numerator: the lowest such
+   i goes to *bad_index (optional) and lemsm_last_bad_index, and nothing but that index is defined.  halo2's batch_invert
+   would leave the zero in place and z would die silently; here it is an error, as in lemsm_fraction_sums.  A zero
+   numerator is legal: the products are 0 from there on.
+   More than 8 columns on a side, a null column, init not canonical, or d_out overlapping the bytes of any input column:
+   LEMSM_ERR_BAD_ARG.
+   This is halo2's lookup product z[i+1] = z[i] (A_i + beta)(S_i + gamma) / ((A'_i + beta)(S'_i + gamma)) once the caller
+   has formed the four factor columns; the permuted columns A', S' stay with the caller.
+   lemsm_poly_last: bytes = 32 n (n_num + n_den + (d_out ? 1 : 0)); the products of the shipped kernels. */
+int lemsm_fraction_products_device(lemsm_ctx* ctx, const void* const* d_num, size_t n_num, const void* const* d_den, size_t n_den, size_t n,
+                                   const uint64_t* init, void* d_out, size_t tap, uint64_t* out_tap, size_t* bad_index);
+/* The same with the columns and `out` (may be NULL) in host memory. */
+int lemsm_fraction_products(lemsm_ctx* ctx, const uint64_t* const* num, size_t n_num, const uint64_t* const* den, size_t n_den, size_t n,
+                            const uint64_t* init, uint64_t* out, size_t tap, uint64_t* out_tap, size_t* bad_index);
+/* The witness part of halo2's permutation::Argument::commit (the reference's circuit enables equality on column c,
+   src/config.rs:228).  n = 2^logn rows (logn 0 .. 26), ncols <= 64 value columns v_j and permutation columns sigma_j of n
+   Lagrange values each, w = lemsm_fft_omega(logn), challenges beta, gamma and the coset multiplier delta (4 limbs each),
+   chunk_len >= 1 columns per set and the tap row u < n.  Set s covers columns s chunk_len ..
+   min(ncols, (s + 1) chunk_len) - 1; nsets = ceil(ncols / chunk_len).  The term of set s at row i is
+     f_{s,i} = prod_j (v_j[i] + beta delta^j w^i + gamma) / prod_j (v_j[i] + beta sigma_j[i] + gamma),
+   j the column's index over ALL columns (delta^j carries across sets), and the product columns are
+     z_s[r] = init_s prod_{i < r} f_{s,i},  r = 0 .. n - 1,   init_0 = 1,  init_{s+1} = z_s[u].
+   Rows above u hold the continued product; halo2 overwrites them with blinding values, and so does the caller.
+   Pure host: validates (logn, ncols, chunk_len) and prices a call.  bytes = 32 n (2 ncols + nsets): every input column is
+   read once by the shipped kernels and every z written once (the engine's own workspace traffic is not in it);
+   field_mults: the products of the shipped kernels, per set of c columns n (4 c - 2 + (logn > 8) + (logn > 16) + 6) and
+   the batched inversion and scan of DESIGN 7f; workspace_bytes: what a call reserves.  ncols == 0 gives zeros. */
+int lemsm_permutation_plan(uint32_t logn, size_t ncols, size_t chunk_len, size_t* nsets, uint64_t* bytes, uint64_t* field_mults,
+                           uint64_t* workspace_bytes);
+/* d_values, d_sigmas: ncols device pointers each; d_z: nsets device pointers of n elements each; out_taps (nsets x 4 limbs,
+   optional) = z_s[u].  A row whose denominators multiply to zero: LEMSM_ERR_DIVISION_BY_ZERO with *bad_index (optional) and
+   lemsm_last_bad_index = s n + i of the first one (sets in order, the lowest row of the first failing set); nothing but the
+   index is defined then.  ncols == 0 is LEMSM_OK with nothing written.  chunk_len == 0, u >= n, a limit exceeded, a null
+   pointer, beta / gamma / delta not canonical, or a d_z buffer overlapping any input column or another d_z:
+   LEMSM_ERR_BAD_ARG.  The sets hang on each other through z_s[u]: a host loop with one 32-byte read-back per set.
+   lemsm_poly_last reports the plan's figures and the summed device time of the sets. */
+int lemsm_permutation_product_device(lemsm_ctx* ctx, const void* const* d_values, const void* const* d_sigmas, size_t ncols, uint32_t logn,
+                                     const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4], size_t chunk_len, size_t usable_row,
+                                     void* const* d_z, uint64_t* out_taps, size_t* bad_index);
+/* The same with the columns and the z columns in host memory (uploaded, the device path, downloaded). */
+int lemsm_permutation_product(lemsm_ctx* ctx, const uint64_t* const* values, const uint64_t* const* sigmas, size_t ncols, uint32_t logn,
+                              const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4], size_t chunk_len, size_t usable_row,
+                              uint64_t* const* z, uint64_t* out_taps, size_t* bad_index);
 
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
