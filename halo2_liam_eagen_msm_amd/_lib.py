@@ -28,6 +28,7 @@ LEMSM_ERR_ARITH_OVERFLOW = 11
 LEMSM_ERR_SUM_NOT_IDENTITY = 12
 LEMSM_ERR_WOULD_NOT_TERMINATE = 13
 LEMSM_ERR_DIVISION_BY_ZERO = 14
+LEMSM_ERR_NOT_IN_TABLE = 15
 LEMSM_COMM_ID_BYTES = 128
 LEMSM_FORM_MONTGOMERY = 0
 LEMSM_FORM_CANONICAL = 1
@@ -76,6 +77,8 @@ SYMBOLS = [
     "lemsm_gate_plan", "lemsm_gate_eval_device", "lemsm_gate_eval",
     "lemsm_fraction_products_geometry", "lemsm_fraction_products_device", "lemsm_fraction_products",
     "lemsm_permutation_plan", "lemsm_permutation_product_device", "lemsm_permutation_product",
+    "lemsm_sort_field_geometry", "lemsm_lookup_permute_plan", "lemsm_sort_field_device", "lemsm_sort_field",
+    "lemsm_lookup_permute_device", "lemsm_lookup_permute", "lemsm_sort_last",
 ]
 
 
@@ -263,6 +266,13 @@ def load() -> ctypes.CDLL:
         "lemsm_permutation_plan": (i, [ctypes.c_uint32, sz, sz, szp] + [ctypes.POINTER(ctypes.c_uint64)] * 3),
         "lemsm_permutation_product_device": (i, [vp, vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p, sz, sz, vp, u64p, szp]),
         "lemsm_permutation_product": (i, [vp, vp, vp, sz, ctypes.c_uint32, u64p, u64p, u64p, sz, sz, vp, u64p, szp]),
+        "lemsm_sort_field_geometry": (i, [sz, u32p, szp, u32p]),
+        "lemsm_lookup_permute_plan": (i, [sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_sort_field_device": (i, [vp, vp, sz, vp]),
+        "lemsm_sort_field": (i, [vp, u64p, sz, u64p]),
+        "lemsm_lookup_permute_device": (i, [vp, vp, vp, sz, vp, vp, szp]),
+        "lemsm_lookup_permute": (i, [vp, u64p, u64p, sz, u64p, u64p, szp]),
+        "lemsm_sort_last": (i, [vp, u32p, u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -96,6 +96,15 @@ class RefDivisionByZero(LemsmError, ZeroDivisionError):
         self.index = index
 
 
+class NotInTable(LemsmError, LookupError):
+    """halo2: Error::ConstraintSystemFailure from permute_expression_pair -- a value of the lookup's input column is not in
+    its table column; .index = the lowest input row that holds the smallest missing value"""
+
+    def __init__(self, status, msg, index):
+        super().__init__(status, msg)
+        self.index = index
+
+
 # one Entry of prepare_scalar_witness (src/negbase_utils.rs:39-43) as the C ABI lays it out: 24 bytes
 ENTRY_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8"), ("mask", "<u4"), ("kind", "<u4")])
 ENTRY_KINDS = ("Scalar", "Bucket", "Limb")
@@ -206,6 +215,10 @@ class Context:
             if bad_index is None:
                 bad_index = int(self.lib.lemsm_last_bad_index(self.h))
             raise RefDivisionByZero(rc, msg, bad_index)
+        if rc == _lib.LEMSM_ERR_NOT_IN_TABLE:
+            if bad_index is None:
+                bad_index = int(self.lib.lemsm_last_bad_index(self.h))
+            raise NotInTable(rc, msg, bad_index)
         raise LemsmError(rc, msg)
 
     def set_option(self, name: str, value: int):
@@ -1035,6 +1048,66 @@ class Context:
                                                 _ptr(taps), ctypes.byref(bad))
         self._check(rc, bad.value)
         return z[:nsets], taps[:nsets]
+
+    # ---- lookup argument: sorted field elements and the permuted columns A', S'  ----
+    @staticmethod
+    def sort_field_geometry(n: int) -> dict:
+        """the module-level sort_field_geometry"""
+        return sort_field_geometry(n)
+
+    @staticmethod
+    def lookup_permute_plan(n: int) -> dict:
+        """the module-level lookup_permute_plan"""
+        return lookup_permute_plan(n)
+
+    def sort_field_device(self, d_in: int, n: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """out[0 .. n) = the n resident bn256::Fr elements at d_in in ascending order of their standard-form integers (Ord on
+        halo2's field type, not the order of the raw limbs), raw Montgomery limbs again.  out must not overlap d_in."""
+        if out is None:
+            out = DeviceBuffer(self, max(n * 32, 16))
+        self._check(self.lib.lemsm_sort_field_device(self.h, d_in, n, out.ptr if isinstance(out, DeviceBuffer) else out))
+        return out
+
+    def sort_field(self, column) -> np.ndarray:
+        """sort_field_device for a column in host memory ((n, 4) uint64): the sorted column"""
+        col = _limbs(column, 4) if np.size(column) else np.zeros((0, 4), np.uint64)
+        out = np.zeros_like(col)
+        self._check(self.lib.lemsm_sort_field(self.h, _ptr(col), col.shape[0], _ptr(out)))
+        return out
+
+    def lookup_permute_device(self, d_input: int, d_table: int, n: int, input_perm: Optional[DeviceBuffer] = None,
+                              table_perm: Optional[DeviceBuffer] = None):
+        """halo2's permute_expression_pair on n resident rows of the compressed input column A and table column S: A' = A in
+        ascending order; S'[r] = A'[r] where A'[r] differs from A'[r - 1] (and at r = 0), and the rest of S, ascending, handed
+        to the repeated rows from the last one down.  NotInTable (.index = the lowest row of A with the smallest value S
+        lacks).  (A', S') as DeviceBuffers"""
+        if input_perm is None:
+            input_perm = DeviceBuffer(self, max(n * 32, 16))
+        if table_perm is None:
+            table_perm = DeviceBuffer(self, max(n * 32, 16))
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_lookup_permute_device(self.h, d_input, d_table, n, input_perm.ptr if isinstance(input_perm, DeviceBuffer) else input_perm,
+                                                  table_perm.ptr if isinstance(table_perm, DeviceBuffer) else table_perm, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return input_perm, table_perm
+
+    def lookup_permute(self, input, table):
+        """lookup_permute_device for columns in host memory ((n, 4) uint64 each): (A', S')"""
+        a = _limbs(input, 4) if np.size(input) else np.zeros((0, 4), np.uint64)
+        s = _limbs(table, 4) if np.size(table) else np.zeros((0, 4), np.uint64)
+        if a.shape[0] != s.shape[0]:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "input and table columns differ in length")
+        ap, sp = np.zeros_like(a), np.zeros_like(s)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_lookup_permute(self.h, _ptr(a), _ptr(s), a.shape[0], _ptr(ap), _ptr(sp), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return ap, sp
+
+    def sort_last(self) -> Tuple[int, int]:
+        """(passes run, passes skipped) of the last sort; after lookup_permute* summed over its two sorts"""
+        run, skipped = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self.lib.lemsm_sort_last(self.h, ctypes.byref(run), ctypes.byref(skipped)))
+        return run.value, skipped.value
 
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
@@ -1866,6 +1939,49 @@ def permutation_products(columns, sigmas, beta, gamma, delta, usable_row: int, c
     if n & (n - 1) or n == 0:
         raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the columns are not 2^logn elements")
     return (ctx or default_context()).permutation_product(cols, sigmas, n.bit_length() - 1, beta, gamma, delta, chunk_len, usable_row)[0]
+
+
+def sort_field_geometry(n: int) -> dict:
+    """the geometry of sort_field* / lookup_permute* for n keys (pure host: lemsm_sort_field_geometry):
+    {"digit_bits", "tile", "max_passes"}"""
+    lib = _lib.load()
+    d = ctypes.c_uint32(); t = ctypes.c_size_t(); m = ctypes.c_uint32()
+    rc = lib.lemsm_sort_field_geometry(n, ctypes.byref(d), ctypes.byref(t), ctypes.byref(m)) if n >= 0 else _lib.LEMSM_ERR_BAD_ARG
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"digit_bits": d.value, "tile": t.value, "max_passes": m.value}
+
+
+def lookup_permute_plan(n: int) -> dict:
+    """prices one lookup_permute_device call of n rows with no pass skipped (pure host: lemsm_lookup_permute_plan):
+    {"bytes", "workspace_bytes"}"""
+    lib = _lib.load()
+    by = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_lookup_permute_plan(n, ctypes.byref(by), ctypes.byref(wb)) if n >= 0 else _lib.LEMSM_ERR_BAD_ARG
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"bytes": by.value, "workspace_bytes": wb.value}
+
+
+def permute_expression_pair(input, table, ctx: Optional[Context] = None):
+    """halo2's permute_expression_pair (plonk/lookup/prover.rs) over standard-form integers mod r: the permuted input and
+    table columns (A', S') of the usable rows `input`, `table` (equal lengths), as lists of integers.  Raises NotInTable
+    (.index = the lowest row of `input` with the smallest value `table` lacks).  Blinding the rows behind them stays with the
+    caller."""
+    R = 1 << 256
+
+    def mont(vals):
+        return np.frombuffer(b"".join((int(v) % FR_MODULUS * R % FR_MODULUS).to_bytes(32, "little") for v in vals), np.uint64).reshape(-1, 4).copy() \
+            if len(vals) else np.zeros((0, 4), np.uint64)
+
+    def std(arr):
+        b, ri = arr.tobytes(), pow(R, -1, FR_MODULUS)
+        return [int.from_bytes(b[i:i + 32], "little") * ri % FR_MODULUS for i in range(0, len(b), 32)]
+
+    if len(input) != len(table):
+        raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "input and table columns differ in length")
+    ap, sp = (ctx or default_context()).lookup_permute(mont(input), mont(table))
+    return std(ap), std(sp)
 
 
 def _neg_affine_raw(curve_id: int, pts: np.ndarray) -> np.ndarray:

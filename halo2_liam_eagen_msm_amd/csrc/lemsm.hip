@@ -33,6 +33,7 @@
 #include "domain.cuh"
 #include "gate.cuh"
 #include "perm.cuh"
+#include "lookup.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -175,6 +176,7 @@ struct lemsm_ctx {
   DevBuf poly_ws, poly_stage;        // fft / kate_division / poly_mul: call workspace, staged arrays (host entries)
   PolyTable poly_tab;                // ... and their twiddle table
   LastStats poly_last;               // lemsm_poly_last
+  u32 sort_passes_run = 0, sort_passes_skipped = 0;   // lemsm_sort_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
   int plan_world = 1;   // ranks sharing the current call's windows: > 1 pins 16-bit windows (16 split evenly over 2/4/8 ranks, 15 do not)
@@ -1836,6 +1838,7 @@ const char* lemsm_strerror(int s) {
     case LEMSM_ERR_SUM_NOT_IDENTITY: return "points do not sum to the identity";
     case LEMSM_ERR_WOULD_NOT_TERMINATE: return "the reference would loop forever";
     case LEMSM_ERR_DIVISION_BY_ZERO: return "division by zero";
+    case LEMSM_ERR_NOT_IN_TABLE: return "a lookup input value is not in the table";
     default: return "unknown status";
   }
 }
@@ -2785,3 +2788,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "domain_abi.inc"
 #include "gate_abi.inc"
 #include "perm_abi.inc"
+#include "lookup_abi.inc"

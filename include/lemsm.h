@@ -68,7 +68,8 @@ enum lemsm_status {
   LEMSM_ERR_ARITH_OVERFLOW = 11,
   LEMSM_ERR_SUM_NOT_IDENTITY = 12,
   LEMSM_ERR_WOULD_NOT_TERMINATE = 13,
-  LEMSM_ERR_DIVISION_BY_ZERO = 14
+  LEMSM_ERR_DIVISION_BY_ZERO = 14,
+  LEMSM_ERR_NOT_IN_TABLE = 15
 };
 
 /* ---- context ------------------------------------------------------------------------- */
@@ -783,7 +784,7 @@ int lemsm_fraction_products_geometry(size_t n, size_t* tile, size_t* segment, si
    More than 8 columns on a side, a null column, init not canonical, or d_out overlapping the bytes of any input column:
    LEMSM_ERR_BAD_ARG.
    This is halo2's lookup product z[i+1] = z[i] (A_i + beta)(S_i + gamma) / ((A'_i + beta)(S'_i + gamma)) once the caller
-   has formed the four factor columns; the permuted columns A', S' stay with the caller.
+   has formed the four factor columns; the permuted columns A', S' come from lemsm_lookup_permute_device below.
    lemsm_poly_last: bytes = 32 n (n_num + n_den + (d_out ? 1 : 0)); the products of the shipped kernels. */
 int lemsm_fraction_products_device(lemsm_ctx* ctx, const void* const* d_num, size_t n_num, const void* const* d_den, size_t n_den, size_t n,
                                    const uint64_t* init, void* d_out, size_t tap, uint64_t* out_tap, size_t* bad_index);
@@ -819,6 +820,57 @@ int lemsm_permutation_product_device(lemsm_ctx* ctx, const void* const* d_values
 int lemsm_permutation_product(lemsm_ctx* ctx, const uint64_t* const* values, const uint64_t* const* sigmas, size_t ncols, uint32_t logn,
                               const uint64_t beta[4], const uint64_t gamma[4], const uint64_t delta[4], size_t chunk_len, size_t usable_row,
                               uint64_t* const* z, uint64_t* out_taps, size_t* bad_index);
+
+/* ---- lookup argument: sorted field elements and the permuted columns A', S' on resident columns -------------
+   The step of halo2's lookup argument in front of its grand product: permute_expression_pair of plonk/lookup/prover.rs
+   (stated from memory; the formulas here are the contract).  The reference's own lookup is the log-derivative one
+   (src/config.rs:402-437); its running sums are lemsm_fraction_sums*.  bn256::Fr, 32-byte raw Montgomery elements, assumed
+   canonical and not checked; the conventions of the lemsm_fft* / lemsm_gate* / lemsm_permutation* entries:
+   LEMSM_ERR_BAD_ARG leaves nothing queued and the outputs untouched, the figures of every call go to lemsm_poly_last, option
+   ws_canary guards every carved workspace.
+   ORDER is the order of the standard-form integers raw R^-1 mod r (Ord on halo2's field type), NOT the order of the raw
+   limbs.  The outputs are unique functions of the inputs (equal keys are identical bytes), so the host entry, the device
+   entry and repeated calls give the same bytes.
+   Pure host: the geometry of the sort (tests size their cases by it).  digit_bits: bits of one radix digit; tile: keys one
+   block of a pass takes; max_passes = 256 / digit_bits: the passes of a sort none of which is skipped.  A digit position at
+   which all n keys agree is skipped: a column of values below 2^16 sorts in 16 / digit_bits passes.  n > 2^28:
+   LEMSM_ERR_BAD_ARG. */
+int lemsm_sort_field_geometry(size_t n, uint32_t* digit_bits, size_t* tile, uint32_t* max_passes);
+/* Pure host: prices one lemsm_lookup_permute_device call of n rows with no pass skipped.  bytes = 32 n (4 + 3 passes + 8)
+   with passes = 2 max_passes (see lemsm_lookup_permute_device); workspace_bytes: what a call reserves.  n == 0 gives zeros,
+   n > 2^28: LEMSM_ERR_BAD_ARG. */
+int lemsm_lookup_permute_plan(size_t n, uint64_t* bytes, uint64_t* workspace_bytes);
+/* d_out[0 .. n) = d_in[0 .. n) in ascending ORDER, in Montgomery form again.  n arbitrary, 0 .. 2^28 (more: LEMSM_ERR_BAD_ARG);
+   n == 0 is LEMSM_OK.  d_out must not overlap d_in; a null pointer with n > 0: LEMSM_ERR_BAD_ARG.
+   A key-only least-significant-digit-first radix sort of the standard-form keys, every pass stable.
+   lemsm_poly_last: ms; bytes = the key bytes of the kernels that ran: 32 n (2 + 3 passes_run), and 32 n 2 more when no
+   pass ran (the tile tables of a pass, 1 / 32 of its keys, are not in it); field_mults = 2 n, the two form conversions. */
+int lemsm_sort_field_device(lemsm_ctx* ctx, const void* d_in, size_t n, void* d_out);
+/* The same with `in` and `out` in host memory. */
+int lemsm_sort_field(lemsm_ctx* ctx, const uint64_t* in, size_t n, uint64_t* out);
+/* halo2's permute_expression_pair on the first n rows (n = the usable rows; the caller blinds the rest) of the compressed
+   input column A = d_input and table column S = d_table:
+     A' = d_input_perm is A in ascending ORDER.  Row r of A' is a HEAD when r == 0 or A'[r] != A'[r-1], else a REPEAT.
+     S' = d_table_perm: S'[r] = A'[r] at every head, and one instance of that value leaves the multiset of S.  What is left
+     of that multiset, in ascending ORDER, is L[0 .. R), R the number of repeats; the repeat of ascending rank j gets
+     L[R - 1 - j].  (halo2: the leftovers in BTreeMap order, each popped onto the last remaining repeated row.)
+   So A'[0] = S'[0], (A'[r] - S'[r]) (A'[r] - A'[r-1]) = 0 for r >= 1, and both pairs are equal as multisets: the lookup
+   product of lemsm_fraction_products_device over (A + beta)(S + gamma) / ((A' + beta)(S' + gamma)) is exactly 1 at tap n.
+   A value of A that is not in S: LEMSM_ERR_NOT_IN_TABLE (halo2: Error::ConstraintSystemFailure); *bad_index (optional) and
+   lemsm_last_bad_index = the lowest row of A that holds the SMALLEST missing value; the outputs are not written.
+   Rows >= n of both outputs are not written.  n == 0 is LEMSM_OK.  An output overlapping an input or the other output, a
+   null pointer (n > 0), n > 2^28: LEMSM_ERR_BAD_ARG.
+   lemsm_poly_last: ms; bytes = 32 n (4 + 3 passes_run + 8): the two conversions, the passes that ran of both sorts, and the
+   key traffic of the S' kernels with the leftovers priced at n (their u32 flag and offset words are not in it);
+   field_mults = 4 n, the two form conversions of both columns. */
+int lemsm_lookup_permute_device(lemsm_ctx* ctx, const void* d_input, const void* d_table, size_t n, void* d_input_perm, void* d_table_perm,
+                                size_t* bad_index);
+/* The same with all four columns in host memory. */
+int lemsm_lookup_permute(lemsm_ctx* ctx, const uint64_t* input, const uint64_t* table, size_t n, uint64_t* input_perm, uint64_t* table_perm,
+                         size_t* bad_index);
+/* The passes the last sort ran and skipped (run + skipped = max_passes); after lemsm_lookup_permute* summed over its two
+   sorts (run + skipped = 2 max_passes). */
+int lemsm_sort_last(const lemsm_ctx* ctx, uint32_t* passes_run, uint32_t* passes_skipped);
 
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
