@@ -17,5 +17,5 @@ from .api import (  # noqa: F401
     fft_plan, omega_pow, omega_pow_inv, half_pow, best_fft, kate_division, eval_polynomial, polynomial_mul,
     domain_plan, vanishing_on_cosets, EXT_INTERLEAVED, EXT_COSET_MAJOR,
     fraction_products_geometry, permutation_plan, permutation_products,
-    sort_field_geometry, lookup_permute_plan, permute_expression_pair, NotInTable,
+    sort_field_geometry, lookup_permute_plan, permute_expression_pair, NotInTable, debug_sort_thresholds,
 )

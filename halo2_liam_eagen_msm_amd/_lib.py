@@ -78,7 +78,7 @@ SYMBOLS = [
     "lemsm_fraction_products_geometry", "lemsm_fraction_products_device", "lemsm_fraction_products",
     "lemsm_permutation_plan", "lemsm_permutation_product_device", "lemsm_permutation_product",
     "lemsm_sort_field_geometry", "lemsm_lookup_permute_plan", "lemsm_sort_field_device", "lemsm_sort_field",
-    "lemsm_lookup_permute_device", "lemsm_lookup_permute", "lemsm_sort_last",
+    "lemsm_lookup_permute_device", "lemsm_lookup_permute", "lemsm_sort_last", "lemsm_debug_sort_thresholds",
 ]
 
 
@@ -273,6 +273,7 @@ def load() -> ctypes.CDLL:
         "lemsm_lookup_permute_device": (i, [vp, vp, vp, sz, vp, vp, szp]),
         "lemsm_lookup_permute": (i, [vp, u64p, u64p, sz, u64p, u64p, szp]),
         "lemsm_sort_last": (i, [vp, u32p, u32p]),
+        "lemsm_debug_sort_thresholds": (i, [szp, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

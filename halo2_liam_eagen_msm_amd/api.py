@@ -1060,6 +1060,11 @@ class Context:
         """the module-level lookup_permute_plan"""
         return lookup_permute_plan(n)
 
+    @staticmethod
+    def debug_sort_thresholds() -> dict:
+        """the module-level debug_sort_thresholds"""
+        return debug_sort_thresholds()
+
     def sort_field_device(self, d_in: int, n: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """out[0 .. n) = the n resident bn256::Fr elements at d_in in ascending order of their standard-form integers (Ord on
         halo2's field type, not the order of the raw limbs), raw Montgomery limbs again.  out must not overlap d_in."""
@@ -1950,6 +1955,17 @@ def sort_field_geometry(n: int) -> dict:
     if rc != _lib.LEMSM_OK:
         raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
     return {"digit_bits": d.value, "tile": t.value, "max_passes": m.value}
+
+
+def debug_sort_thresholds() -> dict:
+    """the sizes above which sort_field* / lookup_permute* take another path (pure host: lemsm_debug_sort_thresholds):
+    {"convert_keys_per_trip", "scan_top_words"}; tests size their cases by them"""
+    lib = _lib.load()
+    c = ctypes.c_size_t(); s = ctypes.c_size_t()
+    rc = lib.lemsm_debug_sort_thresholds(ctypes.byref(c), ctypes.byref(s))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"convert_keys_per_trip": c.value, "scan_top_words": s.value}
 
 
 def lookup_permute_plan(n: int) -> dict:

@@ -159,6 +159,12 @@ int lemsm_sort_last(const lemsm_ctx* ctx, uint32_t* passes_run, uint32_t* passes
   return LEMSM_OK;
 }
 
+int lemsm_debug_sort_thresholds(size_t* convert_keys_per_trip, size_t* scan_top_words) {
+  if (convert_keys_per_trip) *convert_keys_per_trip = (size_t)lk::LS_CONVERT_BLOCKS * lk::LS_THREADS;
+  if (scan_top_words) *scan_top_words = (size_t)256 * lk::SCAN_BLOCK;   // (256: the threads of k_scan_top's one block)
+  return LEMSM_OK;
+}
+
 int lemsm_sort_field_device(lemsm_ctx* ctx, const void* d_in, size_t n, void* d_out) {
   int rc = sort_check(ctx, d_in, n, d_out, "sort_field"); if (rc) return rc;
   ctx->poly_last = LastStats{0, 0, 0};

@@ -871,6 +871,12 @@ int lemsm_lookup_permute(lemsm_ctx* ctx, const uint64_t* input, const uint64_t* 
 /* The passes the last sort ran and skipped (run + skipped = max_passes); after lemsm_lookup_permute* summed over its two
    sorts (run + skipped = 2 max_passes). */
 int lemsm_sort_last(const lemsm_ctx* ctx, uint32_t* passes_run, uint32_t* passes_skipped);
+/* Pure host, no context: the two sizes above which a sort or a permuted pair takes another path (tests size their cases by
+   them; both outputs optional).  convert_keys_per_trip: the keys one trip of the conversion's grid-stride loop takes; a column
+   of more keys takes a second trip.  scan_top_words: the words above which the single block on top of the exclusive scan
+   takes more than one block sum per thread; the tile table of a sort has 2^digit_bits words per tile, the flag scan of a
+   permuted pair 2 n + 1.  Both are multiples of the geometry's tile. */
+int lemsm_debug_sort_thresholds(size_t* convert_keys_per_trip, size_t* scan_top_words);
 
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.

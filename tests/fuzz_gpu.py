@@ -15,6 +15,14 @@ the C ABI and compares with a reference that is not the library.  The families (
     fraction_sums     chained running sums of fractions against rhs_ref.fraction_sums
     regfn             RegularFunction::ev against big-integer Horner, L(f) against rhs_ref.L
     lhs_witness       compute_lhs_witness in full: host entry == device entry, the carry, the functions
+    poly, domain, gate, column, perm, lookup
+                      the resident polynomial entries (tests/fuzz_resident.py): a case is a chain of 3 to 8 calls in a drawn
+                      order -- fft / kate_division / poly_mul; coset transforms, coeff_to_extended, extended_to_coeff; random
+                      gate programs; column a and its RLC cells; fraction and permutation products with planted zero
+                      denominators; sort_field and lookup_permute with planted missing values -- every call compared at once
+                      with the references of the entries' own test modules, behind 0xFF-filled outputs.  These entries keep
+                      state between calls (the shared twiddle table, the re-carved arenas, the words a call resets), which
+                      the chains and the mix with every other family on one context exercise
 Input shapes aim at the rare branches: P next to -P with equal scalars (cancellation), repeated points
 (doubling), identity points, all-equal and tiny scalars, scalars = order-1.  The families that decompose scalars in a
 negabase (lhs, scalar_witness, rhs, lhs_witness) take their usual short list of bases in three cases out of four; in the
@@ -34,6 +42,7 @@ from halo2_liam_eagen_msm_amd import api   # noqa: E402
 from oracle import cref, pyref             # noqa: E402
 from oracle import divisor as dv           # noqa: E402
 import json                                # noqa: E402
+import fuzz_resident                       # noqa: E402
 import negbase_cases                       # noqa: E402
 import rhs_ref                             # noqa: E402
 
@@ -55,8 +64,10 @@ NAMES = list(OPTION_DRAWS)
 
 # family -> probability; what is left goes to the two oldest families, msm : lhs = 3 : 1
 FAMILY_P = [("witness", 0.12), ("scalar_witness", 0.06), ("fixed", 0.08), ("rhs", 0.04), ("fraction_sums", 0.03), ("regfn", 0.04),
-            ("lhs_witness", 0.03)]
+            ("lhs_witness", 0.03),
+            ("poly", 0.04), ("domain", 0.04), ("gate", 0.03), ("column", 0.03), ("perm", 0.04), ("lookup", 0.04)]
 NEW_FAMILIES = ("fixed", "rhs", "fraction_sums", "regfn", "lhs_witness")
+RESIDENT_FAMILIES = fuzz_resident.FAMILIES      # appended to FAMILY_P: the intervals of the families before them stay where they were
 LAST_KINDS = {}        # kinds_seen of the last main() call
 
 
@@ -602,6 +613,18 @@ def main(secs=None, seed=None, cases=None):
                     elif kind == "fraction_sums": fraction_sums_case(rng, ctx, cs)
                     elif kind == "regfn": regfn_case(rng, ctx, O, cs)
                     else: lhs_witness_case(rng, ctx, O, cs)
+                except Exception as ex:
+                    print("EXCEPTION %r %s" % (ex, cs.line()), flush=True)
+                    raise
+                kinds_seen[kind] = kinds_seen.get(kind, 0) + 1; cases += 1
+                continue
+            if kind in RESIDENT_FAMILIES:
+                # the steps are a function of (seed, case) alone (fuzz_resident.case_rng): the line reproduces the case
+                cs = Case(seed, cases, kind, opts, host_entry)
+                try:
+                    steps = fuzz_resident.draw(kind, fuzz_resident.case_rng(seed, cases))
+                    cs.desc = fuzz_resident.describe(steps)
+                    fuzz_resident.run(ctx, cs, steps)
                 except Exception as ex:
                     print("EXCEPTION %r %s" % (ex, cs.line()), flush=True)
                     raise

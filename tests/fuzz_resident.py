@@ -1,0 +1,738 @@
+"""The resident polynomial entries as families of the randomised soak (tests/fuzz_gpu.py runs them; test infrastructure):
+    poly      fft, kate_division, poly_mul against the oracle's best_fft and PolyRing (as tests/test_gpu_poly.py)
+    domain    coset_fft then coset_ifft, coeff_to_extended, extended_to_coeff against tests/domain_ref.py
+    gate      gate_ref.random_program over a drawn coset range against gate_ref.run_program
+    column    column_a and poly_rlc on synthetic witness lengths against tests/column_ref.py
+    perm      fraction_products and permutation_product against tests/perm_ref.py, planted zero denominators
+    lookup    sort_field and lookup_permute against tests/lookup_ref.py, planted missing values
+These entries keep state between calls -- the twiddle table five of them share, the arenas poly_ws and poly_stage every call
+carves anew, the words a call must reset -- so a case is not one call but a chain of 3 to 8 steps in a drawn order, on the
+soak's one long-lived context and under its drawn options.
+
+draw(family, rng) is a pure function of the generator it is given: the inputs of every step and what the step must give,
+computed by the references, no context involved (tests/test_fuzz_cases.py draws cases without a GPU).  run(...) executes the
+steps through the device entries, or their host twins when the case's host_entry flag says so, and compares every step at once,
+byte for byte; every device output is 0xFF-filled with a zone of ZONE bytes behind it, checked after the step."""
+import ctypes
+import hashlib
+import random
+
+import numpy as np
+
+from halo2_liam_eagen_msm_amd import _lib, api
+from oracle import pyref
+from oracle.divisor import PolyRing, best_fft
+
+import column_ref
+import domain_ref
+import gate_ref
+import lookup_ref
+import perm_ref
+import poly_ref
+
+FAMILIES = ("poly", "domain", "gate", "column", "perm", "lookup")
+P = pyref.R_BN254
+assert P == perm_ref.P == lookup_ref.P == pyref.GRUMPKIN.fp
+R = 1 << 256
+RI = pow(R, -1, P)
+TOP = 0x30644E72E131A029            # top limb of r: a smaller top limb makes any four limbs canonical
+ZONE = 4096
+RING = PolyRing(P, None)
+MONT, CANON = _lib.LEMSM_FORM_MONTGOMERY, _lib.LEMSM_FORM_CANONICAL
+INTER, MAJOR = _lib.LEMSM_EXT_INTERLEAVED, _lib.LEMSM_EXT_COSET_MAJOR
+GRUMPKIN = 1
+MIN_STEPS, MAX_STEPS = 3, 8
+P_ZERO_DENOMINATOR, P_MISSING_VALUE = 0.15, 0.18       # per case: one step of it gets the planted error
+KD_S = poly_ref.KD_S
+KD_BLOCK = 256 * KD_S               # coefficients one block of the quotient's kernels covers
+# the documented limits of the entries (include/lemsm.h), what tests/test_fuzz_cases.py holds every drawn size against
+LIMITS = {"fft_logn": 26, "mul_len": 1 << 26, "kate_len": 1 << 26, "ext_logn": 26, "ext_logm": 4, "ext_log": 28,
+          "gate_code": gate_ref.MAX_CODE, "gate_table": gate_ref.MAX_TABLE, "gate_cols": gate_ref.MAX_COLS, "gate_depth": gate_ref.MAX_DEPTH,
+          "perm_logn": perm_ref.MAX_LOGN, "perm_cols": perm_ref.MAX_COLS, "factors": perm_ref.MAX_FACTORS, "lookup_n": lookup_ref.MAX_N,
+          "column_rows": 1 << 28}
+
+
+# ---- helpers -------------------------------------------------------------------------------------------------------------------
+def _ints(arr):
+    b = np.ascontiguousarray(arr).tobytes()
+    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
+
+
+def _arr(vals):
+    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), np.uint64).reshape(-1, 4).copy() if len(vals) else np.zeros((0, 4), np.uint64)
+
+
+def _mont(vals):
+    """standard-form integers -> raw Montgomery limbs"""
+    return _arr([v * R % P for v in vals])
+
+
+def _fe(v):
+    return _mont([v])[0]
+
+
+def _rand(rng, n):
+    """n random canonical elements, raw limbs"""
+    a = rng.integers(0, 1 << 63, (n, 4), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (n, 4), dtype=np.uint64)
+    a[:, 3] = rng.integers(0, TOP, n, dtype=np.uint64)
+    return a
+
+
+def _fe_int(rng):
+    """a random standard-form integer below r"""
+    return _ints(_rand(rng, 1))[0]
+
+
+def _pick(rng, seq):
+    return seq[int(rng.integers(0, len(seq)))]
+
+
+def _blob(v):
+    if isinstance(v, np.ndarray):
+        return str(v.dtype).encode() + str(v.shape).encode() + v.tobytes()
+    if isinstance(v, (bytes, bytearray)):
+        return bytes(v)
+    if isinstance(v, (list, tuple)):
+        return b"[" + b",".join(_blob(x) for x in v) + b"]"
+    if isinstance(v, dict):
+        return b"{" + b",".join(k.encode() + b":" + _blob(v[k]) for k in sorted(v)) + b"}"
+    return repr(v).encode()
+
+
+class Step:
+    """one call of a case: op names the runner, note goes into the case line, sizes = [(limit name, value)], error says that the
+    step expects a status instead of a result; everything else is the step's inputs and what it must give"""
+
+    def __init__(self, op, note, sizes, error=False, **kw):
+        self.op, self.note, self.sizes, self.error = op, note, sizes, error
+        self.__dict__.update(kw)
+
+    def fingerprint(self):
+        return hashlib.sha256(_blob(self.__dict__)).hexdigest()
+
+
+def describe(steps):
+    return "steps=[%s]" % "; ".join("%s %s%s" % (s.op, s.note, " ERROR" if s.error else "") for s in steps)
+
+
+# ---- poly ----------------------------------------------------------------------------------------------------------------------
+def _gen_fft(rng):
+    logn, inverse, nseq = int(rng.integers(0, 13)), bool(rng.integers(0, 2)), int(rng.integers(1, 4))
+    n = 1 << logn
+    w = domain_ref.omega(logn)
+    if inverse:
+        w = pow(w, -1, P)
+    scale = _fe_int(rng) if rng.random() < 0.5 else None
+    data = _rand(rng, nseq * n)
+    raw, want = _ints(data), []
+    for s in range(nseq):
+        seq = raw[s * n:(s + 1) * n]
+        best_fft(seq, w, logn, P)
+        want += seq if scale is None else [v * scale % P for v in seq]
+    return Step("fft", "logn=%d nseq=%d inverse=%s scale=%s" % (logn, nseq, inverse, scale is not None), [("fft_logn", logn)],
+                logn=logn, nseq=nseq, omega=_fe(w), scale=None if scale is None else _fe(scale), data=data, want=_arr(want).tobytes())
+
+
+def _kate_length(rng):
+    return int(_pick(rng, [1, 2, KD_S - 1, KD_S, KD_S + 1, 2 * KD_S + 1, KD_BLOCK - 1, KD_BLOCK, KD_BLOCK + 1,
+                           int(rng.integers(3, 300)), int(rng.integers(3, 300)), int(rng.integers(300, 4000))]))
+
+
+def _gen_kate(rng):
+    rows, used = [], int(rng.integers(0, 8))
+    for _ in range(int(rng.integers(1, 4))):
+        length = _kate_length(rng)
+        rows.append((used, length)); used += length + int(rng.integers(0, 6))
+    b = int(_pick(rng, [0, 1, _fe_int(rng)]))
+    coeffs = _rand(rng, used)
+    assert poly_ref.segment_len(max(n for _, n in rows)) == KD_S      # (the lengths lie around the boundaries of this segment length)
+    image = np.full(used * 32, 0xFF, np.uint8)
+    quotients = []
+    for o, n in rows:
+        q = _arr(RING.kate_div(_ints(coeffs[o:o + n]), b)).tobytes() if n > 1 else b""
+        quotients.append(q)
+        image[o * 32:(o + n - 1) * 32] = np.frombuffer(q, np.uint8)
+    return Step("kate", "rows=%s b=%s" % (rows, b if b < 2 else "random"), [("kate_len", n) for _, n in rows],
+                coeffs=coeffs, index=np.array(rows, np.uintp).reshape(-1, 2), b=_fe(b), want=image.tobytes(), quotients=quotients)
+
+
+def _gen_mul(rng):
+    def length():
+        return int(_pick(rng, [0, 1, 2, 31, 32, 33, int(rng.integers(0, 1101)), int(rng.integers(0, 1101)), int(rng.integers(0, 200))]))
+    la, lb = length(), length()
+    a, b = _rand(rng, la), _rand(rng, lb)
+    if la == 0 and lb == 0:
+        return Step("mul", "la=0 lb=0", [("mul_len", 0)], error=True, a=a, b=b, want=b"", cap=4)
+    want = RING.mul(_ints(a), _ints(b))
+    assert len(want) == la + lb - 1
+    return Step("mul", "la=%d lb=%d" % (la, lb), [("mul_len", la + lb - 1)], a=a, b=b, want=_arr([v * RI % P for v in want]).tobytes(), cap=la + lb - 1)
+
+
+def _draw_poly(rng, nsteps):
+    return [_pick(rng, [_gen_fft, _gen_fft, _gen_kate, _gen_mul])(rng) for _ in range(nsteps)]
+
+
+def _run_fft(ctx, cs, k, st):
+    if cs.host_entry:
+        return _same(cs, k, st, ctx.fft(st.data, st.logn, st.omega, st.scale).tobytes(), st.want)
+    buf = _filled(ctx, st.data.shape[0], st.data)
+    ctx.fft_device(buf.ptr, st.nseq, st.logn, st.omega, st.scale)
+    _payload(cs, k, st, buf, st.want)
+
+
+def _run_kate(ctx, cs, k, st):
+    rows = [(int(o), int(n)) for o, n in st.index]
+    if cs.host_entry:
+        got = ctx.kate_division([st.coeffs[o:o + n] for o, n in rows], st.b)
+        return _same(cs, k, st, b"".join(q.tobytes() for q in got), b"".join(st.quotients))
+    cap = st.coeffs.shape[0]
+    d_in, d_out = ctx.to_device(st.coeffs), _filled(ctx, cap)
+    try:
+        ctx.kate_division_device(d_in.ptr, cap, st.index, st.b, d_out.ptr, cap)
+    finally:
+        d_in.free()
+    _payload(cs, k, st, d_out, st.want)
+
+
+def _run_mul(ctx, cs, k, st):
+    la, lb = st.a.shape[0], st.b.shape[0]
+    if cs.host_entry:
+        try:
+            got = ctx.poly_mul(st.a, st.b)
+        except api.RefArithmeticOverflow:
+            return None if st.error else cs.mismatch("step %d %s: two operands refused as empty" % (k, st.op))
+        if st.error:
+            cs.mismatch("step %d %s: two empty operands accepted" % (k, st.op))
+        return _same(cs, k, st, got.tobytes(), st.want)
+    d_a = ctx.to_device(st.a) if la else ctx.alloc(32)
+    d_b = ctx.to_device(st.b) if lb else ctx.alloc(32)
+    d_out = _filled(ctx, st.cap)
+    try:
+        n = ctx.poly_mul_device(d_a.ptr, la, d_b.ptr, lb, d_out.ptr, st.cap)
+        if st.error:
+            cs.mismatch("step %d %s: two empty operands accepted" % (k, st.op))
+        if n != la + lb - 1:
+            cs.mismatch("step %d %s: length %d" % (k, st.op, n))
+    except api.RefArithmeticOverflow:
+        if not st.error:
+            cs.mismatch("step %d %s: two operands refused as empty" % (k, st.op))
+    finally:
+        d_a.free(); d_b.free()
+    _payload(cs, k, st, d_out, st.want)
+
+
+# ---- domain --------------------------------------------------------------------------------------------------------------------
+def _shift(rng, sel=None):
+    sel = sel or _pick(rng, ["one", "order3", "random"])
+    return {"one": 1, "order3": domain_ref.order3(), "random": 2 + _fe_int(rng) % (P - 2)}[sel], sel
+
+
+def _gen_coset(rng):
+    logn, nseq = int(rng.integers(0, 12)), int(rng.integers(1, 3))
+    n = 1 << logn
+    g, gsel = _shift(rng)
+    scale = _fe_int(rng) if rng.random() < 0.5 else None
+    data = _rand(rng, nseq * n)
+    raw, fwd, back = _ints(data), [], []
+    ginv, ninv = pow(g, -1, P), pow(n, -1, P)
+    for s in range(nseq):
+        f = domain_ref.coset_fft(raw[s * n:(s + 1) * n], logn, g, 1 if scale is None else scale)
+        fwd += f
+        back += domain_ref.coset_ifft(f, logn, ginv, ninv)
+    w = domain_ref.omega(logn)
+    return Step("coset", "logn=%d nseq=%d g=%s scale=%s" % (logn, nseq, gsel, scale is not None), [("fft_logn", logn)],
+                logn=logn, nseq=nseq, data=data, omega=_fe(w), omega_inv=_fe(pow(w, -1, P)), shift=_fe(g), shift_inv=_fe(ginv),
+                scale=None if scale is None else _fe(scale), half=_fe(ninv), want=_arr(fwd).tobytes(), want_back=_arr(back).tobytes())
+
+
+def _ext_shape(rng):
+    while True:
+        logn, logm = int(rng.integers(0, 12)), int(rng.integers(0, 5))
+        if logn + logm <= 13:
+            return logn, logm
+
+
+def _to_major(vals, logn, logm):
+    return domain_ref.place(domain_ref.unplace(vals, logn, logm, domain_ref.INTERLEAVED), logn, logm, domain_ref.COSET_MAJOR)
+
+
+def _gen_c2e(rng):
+    logn, logm = _ext_shape(rng)
+    n, N = 1 << logn, 1 << (logn + logm)
+    g, gsel = _shift(rng)
+    layout = int(_pick(rng, [INTER, MAJOR]))
+    n_coeffs = int(_pick(rng, [0, 1, max(n - 1, 0), n, min(n + 1, N), N - 1, N, int(rng.integers(0, N + 1))]))
+    coeffs = _rand(rng, n_coeffs)
+    want = domain_ref.coeff_to_extended_halo2(_ints(coeffs), logn, logm, g)
+    if layout == MAJOR:
+        want = _to_major(want, logn, logm)
+    return Step("c2e", "logn=%d logm=%d n_coeffs=%d g=%s layout=%d" % (logn, logm, n_coeffs, gsel, layout),
+                [("ext_logn", logn), ("ext_logm", logm), ("ext_log", logn + logm)],
+                logn=logn, logm=logm, coeffs=coeffs, shift=_fe(g), layout=layout, want=_arr(want).tobytes())
+
+
+def _gen_e2c(rng):
+    logn, logm = _ext_shape(rng)
+    n, N = 1 << logn, 1 << (logn + logm)
+    divide = bool(rng.integers(0, 2))
+    g, gsel = _shift(rng, _pick(rng, ["order3", "random"]) if divide else None)      # (X^n - 1 vanishes on a coset of g = 1)
+    layout, form = int(_pick(rng, [INTER, MAJOR])), int(_pick(rng, [MONT, MONT, CANON]))
+    n_out = int(_pick(rng, [0, 1, n, min(3 * n, N), N, int(rng.integers(0, N + 1))]))
+    evals = _rand(rng, N)
+    inter = _ints(evals)
+    if layout == MAJOR:                                            # the values as given are coset-major: their interleaved order
+        inter = domain_ref.place(domain_ref.unplace(inter, logn, logm, domain_ref.COSET_MAJOR), logn, logm, domain_ref.INTERLEAVED)
+    want = domain_ref.extended_to_coeff_halo2(inter, logn, logm, g, divide)[:n_out]
+    if form == CANON:
+        want = [v * RI % P for v in want]
+    return Step("e2c", "logn=%d logm=%d n_out=%d g=%s layout=%d divide=%s form=%d" % (logn, logm, n_out, gsel, layout, divide, form),
+                [("ext_logn", logn), ("ext_logm", logm), ("ext_log", logn + logm)],
+                logn=logn, logm=logm, evals=evals, shift=_fe(g), layout=layout, divide=divide, form=form, n_out=n_out, want=_arr(want).tobytes())
+
+
+def _draw_domain(rng, nsteps):
+    return [_pick(rng, [_gen_coset, _gen_c2e, _gen_e2c])(rng) for _ in range(nsteps)]
+
+
+def _run_coset(ctx, cs, k, st):
+    if cs.host_entry:
+        fwd = ctx.coset_fft(st.data, st.logn, st.omega, st.shift, st.scale)
+        _same(cs, k, st, fwd.tobytes(), st.want)
+        return _same(cs, k, st, ctx.coset_ifft(fwd, st.logn, st.omega_inv, st.shift_inv, st.half).tobytes(), st.want_back)
+    buf = _filled(ctx, st.data.shape[0], st.data)
+    ctx.coset_fft_device(buf.ptr, st.nseq, st.logn, st.omega, st.shift, st.scale)
+    _payload(cs, k, st, buf, st.want, free=False)
+    ctx.coset_ifft_device(buf.ptr, st.nseq, st.logn, st.omega_inv, st.shift_inv, st.half)
+    _payload(cs, k, st, buf, st.want_back)
+
+
+def _run_c2e(ctx, cs, k, st):
+    N, nc = 1 << (st.logn + st.logm), st.coeffs.shape[0]
+    if cs.host_entry:
+        return _same(cs, k, st, ctx.coeff_to_extended(st.coeffs, st.logn, st.logm, st.shift, st.layout).tobytes(), st.want)
+    d_in, out = ctx.to_device(st.coeffs) if nc else ctx.alloc(32), _filled(ctx, N)
+    try:
+        ctx.coeff_to_extended_device(d_in.ptr, nc, st.logn, st.logm, st.shift, out.ptr, N, st.layout)
+    finally:
+        d_in.free()
+    _payload(cs, k, st, out, st.want)
+
+
+def _run_e2c(ctx, cs, k, st):
+    if cs.host_entry:
+        got = ctx.extended_to_coeff(st.evals, st.logn, st.logm, st.shift, st.n_out, st.layout, st.divide, st.form)
+        return _same(cs, k, st, got.tobytes(), st.want)
+    d_in, out = ctx.to_device(st.evals), _filled(ctx, st.n_out)
+    try:
+        ctx.extended_to_coeff_device(d_in.ptr, st.logn, st.logm, st.shift, out.ptr, st.n_out, st.layout, st.divide, st.form)
+    finally:
+        d_in.free()
+    _payload(cs, k, st, out, st.want)
+
+
+# ---- gate ----------------------------------------------------------------------------------------------------------------------
+def _gen_gate(rng):
+    pr = random.Random(int(rng.integers(1, 1 << 62)))              # gate_ref draws with the standard library's generator
+    logn, logm, ncols = int(rng.integers(4, 8)), int(rng.integers(0, 3)), int(rng.integers(1, 6))
+    n, m = 1 << logn, 1 << logm
+    with_x = bool(rng.integers(0, 2))
+    code, queries, consts = gate_ref.random_program(pr, ncols, pr.randrange(1, 12), pr.randrange(1, 6), pr.randrange(2, 50), with_x=with_x,
+                                                    max_depth=pr.choice([2, 4, 8]))
+    ok, figures = gate_ref.check_program(code, queries, consts, ncols)
+    assert ok, figures
+    cb = int(rng.integers(0, m))
+    cc = int(rng.integers(1, m - cb + 1))
+    y = int(_pick(rng, [0, 1, _fe_int(rng)]))
+    g = _shift(rng, _pick(rng, ["order3", "random"]))[0] if with_x or rng.random() < 0.3 else None
+    raw = [_rand(rng, n * m) for _ in range(ncols)]
+    cols = [[v * RI % P for v in _ints(a)] for a in raw]
+    cosets = list(range(cb, cb + cc))
+    xs = gate_ref.points(logn, logm, g, cosets) if g is not None else None
+    want = gate_ref.run_program(code, queries, consts, cols, logn, cosets, y, xs)
+    return Step("gate", "logn=%d logm=%d ncols=%d code=%d cosets=%d+%d y=%s with_x=%s" % (logn, logm, ncols, len(code), cb, cc, y if y < 2 else "random", with_x),
+                [("ext_logn", logn), ("ext_logm", logm), ("gate_code", len(code)), ("gate_table", max(len(queries), len(consts))), ("gate_cols", ncols),
+                 ("gate_depth", figures["stack_depth"])],
+                logn=logn, logm=logm, code=code, queries=queries, consts=_mont(consts), columns=raw, cb=cb, cc=cc, y=_fe(y),
+                shift=None if g is None else _fe(g), want=_mont(want).tobytes())
+
+
+def _draw_gate(rng, nsteps):
+    return [_gen_gate(rng) for _ in range(nsteps)]
+
+
+def _run_gate(ctx, cs, k, st):
+    prog = api.GateProgram(st.code, np.array(st.queries, np.int32).reshape(-1, 2), st.consts)
+    n, N = 1 << st.logn, 1 << (st.logn + st.logm)
+    if cs.host_entry:
+        return _same(cs, k, st, ctx.gate_eval(prog, st.columns, st.logn, st.logm, st.y, st.shift, st.cb, st.cc).tobytes(), st.want)
+    d_cols, out = [ctx.to_device(a) for a in st.columns], _filled(ctx, N)
+    try:
+        ctx.gate_eval_device(prog, [d.ptr for d in d_cols], st.logn, st.logm, out.ptr, N, st.y, st.shift, st.cb, st.cc)
+    finally:
+        for d in d_cols:
+            d.free()
+    image = np.full(N * 32, 0xFF, np.uint8)                        # the cosets outside the range stay as they were
+    image[st.cb * n * 32:(st.cb + st.cc) * n * 32] = np.frombuffer(st.want, np.uint8)
+    _payload(cs, k, st, out, image.tobytes())
+
+
+# ---- column --------------------------------------------------------------------------------------------------------------------
+# (len_a, len_b) of a function, as tests/test_gpu_column.py's synthetic fixture: 1, 2, 15, 16, 17, 31, 32, 33 batches (the
+# 16-batch tile's edges), an empty function, long gaps, b longer than a
+COLUMN_SHAPES = [(1, 0), (2, 0), (3, 7), (9, 2), (0, 8), (5, 15), (17, 0), (12, 16), (0, 0), (40, 1), (0, 1), (6, 20)]
+COLUMN_LONG = (2, 1024)             # 2049 batches: alone in its case
+
+
+def _draw_column(rng, nsteps):
+    """one synthetic set of functions per case: its column under drawn (batch offset, capacity, form), and RLC cells of it"""
+    T = int(_pick(rng, [1, 1, int(rng.integers(2, 10)), int(rng.integers(10, 34)), int(rng.integers(34, 83))]))
+    lens = [COLUMN_LONG] if T == 1 and rng.random() < 0.5 else [COLUMN_SHAPES[int(rng.integers(0, len(COLUMN_SHAPES)))] for _ in range(T)]
+    if not any(la or lb for la, lb in lens):
+        lens[0] = COLUMN_SHAPES[2]
+    rows, used = [], int(rng.integers(0, 9))                       # (the first function need not start the buffer)
+    for la, lb in lens:
+        rows.append((used, la, used + la + 3, lb)); used += la + lb + 5      # (and a is apart from b)
+    index = np.array(rows, np.uintp).reshape(-1, 4)
+    coeffs = _rand(rng, used)
+    ci = _ints(coeffs)
+    fns = [(ci[oa: oa + la], ci[ob: ob + lb]) for oa, la, ob, lb in rows]
+    steps = []
+    for _ in range(nsteps):
+        off = int(_pick(rng, [0, 0, 3, int(rng.integers(1, 8))]))
+        bs = T + off
+        extra = int(_pick(rng, [0, 0, int(rng.integers(1, 71))]))
+        form = int(_pick(rng, [MONT, CANON]))
+        col = column_ref.column_a(fns, off)
+        nb = len(col) + extra
+        col = col + [[0] * bs] * extra
+        flat = [v for b in col for v in b]
+        as_form = _arr(flat if form == MONT else [v * RI % P for v in flat])
+        if rng.random() < 0.5:
+            steps.append(Step("column", "T=%d off=%d batches=%d%s form=%d" % (T, off, nb, "+surplus" if extra else "", form), [("column_rows", nb * bs)],
+                              coeffs=coeffs, index=index, off=off, num_batches=nb if extra else 0, nb=nb, rows=nb * bs, form=form,
+                              want=as_form.tobytes()))
+        else:
+            F = int(_pick(rng, [1, 2, 11, bs, bs + 5, int(rng.integers(1, bs + 6))]))
+            r = int(_pick(rng, [0, 1, _fe_int(rng)]))
+            cells = column_ref.rlc_cells(col, T, off, F, r, P)
+            plan = column_ref.plan(lens, off, F, nb)
+            assert plan["cells"] == sum(len(c) for c in cells)
+            steps.append(Step("rlc", "T=%d off=%d batches=%d F=%d r=%s form=%d" % (T, off, nb, F, r if r < 2 else "random", form), [("column_rows", nb * bs)],
+                              column=as_form, T=T, off=off, F=F, nb=nb, r=_fe(r), form=form, cells=plan["cells"],
+                              want=_arr([v for c in cells for v in c]).tobytes()))
+    return steps
+
+
+def _run_column(ctx, cs, k, st):
+    if cs.host_entry:
+        fns = [(st.coeffs[oa: oa + la], st.coeffs[ob: ob + lb]) for oa, la, ob, lb in ((int(v) for v in row) for row in st.index)]
+        got, nb = ctx.column_a(GRUMPKIN, fns, st.off, st.num_batches, st.form)
+        if nb != st.nb:
+            cs.mismatch("step %d %s: %d batches" % (k, st.op, nb))
+        return _same(cs, k, st, got.tobytes(), st.want)
+    d_in, out = ctx.to_device(st.coeffs), _filled(ctx, st.rows)
+    nb = ctypes.c_size_t(0)
+    try:                                                           # (the C entry itself: the capacity is exactly the column's rows)
+        ctx._check(ctx.lib.lemsm_column_a_device(ctx.h, GRUMPKIN, d_in.ptr, st.coeffs.shape[0], st.index.ctypes.data, st.index.shape[0], st.off,
+                                                 st.num_batches, st.form, out.ptr, st.rows, ctypes.byref(nb)))
+    finally:
+        d_in.free()
+    if nb.value != st.nb:
+        cs.mismatch("step %d %s: %d batches" % (k, st.op, nb.value))
+    _payload(cs, k, st, out, st.want)
+
+
+def _run_rlc(ctx, cs, k, st):
+    if cs.host_entry:
+        return _same(cs, k, st, ctx.poly_rlc(GRUMPKIN, st.column, st.T, st.off, st.F, st.r, st.form).tobytes(), st.want)
+    d_col, out = ctx.to_device(st.column), _filled(ctx, st.cells)
+    try:
+        ctx._check(ctx.lib.lemsm_poly_rlc_device(ctx.h, GRUMPKIN, d_col.ptr, st.form, st.T, st.off, st.F, st.nb, st.r.ctypes.data, out.ptr, st.cells))
+    finally:
+        d_col.free()
+    _payload(cs, k, st, out, st.want)
+
+
+# ---- perm ----------------------------------------------------------------------------------------------------------------------
+def _fp_geometry():
+    geo = api.fraction_products_geometry(1 << 13)                  # (pure host)
+    return geo["tile"], geo["segment"], geo["block_segments"]
+
+
+def _gen_fp(rng, plant):
+    tile, seg, bsegs = _fp_geometry()
+    top = bsegs * seg + 1
+    n = int(_pick(rng, [0, 1, 2, seg - 1, seg, seg + 1, tile - 1, tile, tile + 1, top, int(rng.integers(3, 300)), int(rng.integers(3, 300)),
+                        int(rng.integers(300, top + 1))]))
+    n_num, n_den = int(rng.integers(0, 9)), int(rng.integers(0, 9))
+    if n * (n_num + n_den) > 6 * tile:                             # (the reference is a big-integer loop: many columns go with few rows)
+        n_num, n_den = n_num % 3, n_den % 3
+    if plant:
+        n, n_den = max(n, 1), max(n_den, 1)
+    nums, dens = [_rand(rng, n) for _ in range(n_num)], [_rand(rng, n) for _ in range(n_den)]
+    if plant:
+        for _ in range(int(rng.integers(1, 3))):
+            dens[int(rng.integers(0, n_den))][int(rng.integers(0, n))] = 0
+    elif n and n_num and rng.random() < 0.3:
+        nums[0][int(rng.integers(0, n))] = 0                      # a zero numerator is no error: the products are zero behind it
+    init = _pick(rng, [None, 0, 1, _fe_int(rng)])
+    tap, want_out = int(_pick(rng, [0, n, max(n - 1, 0), int(rng.integers(0, n + 1))])), bool(rng.random() < 0.7)
+    note = "n=%d nums=%d dens=%d init=%s tap=%d want_out=%s" % (n, n_num, n_den, init if init is None or init < 2 else "random", tap, want_out)
+    sizes = [("factors", n_num), ("factors", n_den), ("lookup_n", n)]
+    std = lambda cols: [[v * RI % P for v in _ints(c)] for c in cols]
+    kw = dict(nums=nums, dens=dens, n=n, init=None if init is None else _fe(init), tap=tap, want_out=want_out)
+    try:
+        out, tapped = perm_ref.fraction_products(std(nums), std(dens), n, 1 if init is None else init, tap)
+    except perm_ref.ZeroDenominator as e:
+        assert plant
+        return Step("fp", note, sizes, error=True, index=e.index, want=b"", **kw)
+    assert not plant
+    return Step("fp", note, sizes, want=_mont(out).tobytes(), want_tap=_fe(tapped).tobytes(), **kw)
+
+
+def _gen_pp(rng, plant):
+    logn, ncols, chunk = int(rng.integers(0, 10)), int(rng.integers(1, 7)), int(rng.integers(1, 6))
+    n = 1 << logn
+    u = int(_pick(rng, [0, n - 1, n // 2, int(rng.integers(0, n))]))
+    delta = int(_pick(rng, [1, perm_ref.DELTA]))
+    beta, gamma = 1 + _fe_int(rng) % (P - 1), 1 + _fe_int(rng) % (P - 1)
+    values, sigmas = [_rand(rng, n) for _ in range(ncols)], [_rand(rng, n) for _ in range(ncols)]
+    v_std, s_std = ([[v * RI % P for v in _ints(c)] for c in cols] for cols in (values, sigmas))
+    if plant:
+        for _ in range(int(rng.integers(1, 3))):
+            col, row = int(rng.integers(0, ncols)), int(rng.integers(0, n))
+            v_std[col][row] = (-beta * s_std[col][row] - gamma) % P
+            values[col][row] = _fe(v_std[col][row])
+    note = "logn=%d ncols=%d chunk=%d u=%d delta=%s" % (logn, ncols, chunk, u, "1" if delta == 1 else "halo2")
+    sizes = [("perm_logn", logn), ("perm_cols", ncols)]
+    kw = dict(values=values, sigmas=sigmas, logn=logn, beta=_fe(beta), gamma=_fe(gamma), delta=_fe(delta), chunk=chunk, u=u,
+              nsets=-(-ncols // chunk))
+    try:
+        zs, taps = perm_ref.permutation_products(v_std, s_std, logn, beta, gamma, delta, chunk, u)
+    except perm_ref.ZeroDenominator as e:
+        assert plant
+        return Step("pp", note, sizes, error=True, index=e.index, want=b"", **kw)
+    assert not plant
+    return Step("pp", note, sizes, want=[_mont(z).tobytes() for z in zs], want_taps=_mont(taps).tobytes(), **kw)
+
+
+def _draw_perm(rng, nsteps):
+    planted = int(rng.integers(0, nsteps)) if rng.random() < P_ZERO_DENOMINATOR else -1
+    return [_pick(rng, [_gen_fp, _gen_fp, _gen_pp])(rng, k == planted) for k in range(nsteps)]
+
+
+def _run_fp(ctx, cs, k, st):
+    n = st.n
+    if cs.host_entry:
+        try:
+            out, tapped = ctx.fraction_products(st.nums, st.dens, st.init, st.want_out, st.tap, n=n)
+        except api.RefDivisionByZero as e:
+            return _error(cs, k, st, e.index)
+        _no_error(cs, k, st)
+        if st.want_out:
+            _same(cs, k, st, out.tobytes(), st.want)
+        return _same(cs, k, st, tapped.tobytes(), st.want_tap)
+    d_num, d_den = [ctx.to_device(c) for c in st.nums], [ctx.to_device(c) for c in st.dens]
+    out = _filled(ctx, n) if st.want_out else None
+    try:
+        _, tapped = ctx.fraction_products_device([d.ptr for d in d_num], [d.ptr for d in d_den], n, st.init, out=out, want_out=st.want_out, tap=st.tap)
+    except api.RefDivisionByZero as e:
+        if out is not None:
+            out.free()
+        return _error(cs, k, st, e.index)
+    finally:
+        for d in d_num + d_den:
+            d.free()
+    _no_error(cs, k, st)
+    if out is not None:
+        _payload(cs, k, st, out, st.want)
+    _same(cs, k, st, tapped.tobytes(), st.want_tap)
+
+
+def _run_pp(ctx, cs, k, st):
+    n = 1 << st.logn
+    if cs.host_entry:
+        try:
+            z, taps = ctx.permutation_product(st.values, st.sigmas, st.logn, st.beta, st.gamma, st.delta, st.chunk, st.u)
+        except api.RefDivisionByZero as e:
+            return _error(cs, k, st, e.index)
+        _no_error(cs, k, st)
+        _same(cs, k, st, z.tobytes(), b"".join(st.want))
+        return _same(cs, k, st, taps.tobytes(), st.want_taps)
+    d_v, d_s = [ctx.to_device(c) for c in st.values], [ctx.to_device(c) for c in st.sigmas]
+    zs = [_filled(ctx, n) for _ in range(st.nsets)]
+    try:
+        _, taps = ctx.permutation_product_device([d.ptr for d in d_v], [d.ptr for d in d_s], st.logn, st.beta, st.gamma, st.delta, st.chunk, st.u,
+                                                 d_z=[z.ptr for z in zs])
+    except api.RefDivisionByZero as e:
+        for z in zs:
+            z.free()
+        return _error(cs, k, st, e.index)
+    finally:
+        for d in d_v + d_s:
+            d.free()
+    _no_error(cs, k, st)
+    for z, want in zip(zs, st.want):
+        _payload(cs, k, st, z, want)
+    _same(cs, k, st, taps.tobytes(), st.want_taps)
+
+
+# ---- lookup --------------------------------------------------------------------------------------------------------------------
+def _lookup_n(rng, least=0):
+    tile = lookup_ref.TILE
+    return max(least, int(_pick(rng, [0, 1, 2, tile - 1, tile, tile + 1, 2 * tile + 1, 3 * tile + 1, int(rng.integers(3, 200)), int(rng.integers(3, 200)),
+                                      int(rng.integers(200, 3 * tile + 2))])))
+
+
+def _gen_sort(rng):
+    """keys whose live byte positions are a drawn subset of the 32; the other bytes are equal in every key: non-zero, or zero"""
+    n = _lookup_n(rng)
+    nlive = int(_pick(rng, [0, 1, 1, 2, 3, int(rng.integers(0, 33)), 32]))
+    live = sorted(int(p) for p in rng.choice(32, size=nlive, replace=False))
+    rest = bytes([0x11 + (k % 7) for k in range(32)]) if rng.random() < 0.5 else bytes(32)
+    keys = np.tile(np.frombuffer(rest, np.uint8), (n, 1))
+    for p in live:
+        keys[:, p] = rng.integers(0, 0x30 if p == 31 else 0x100, n)      # (the top byte of r is 0x30: stay canonical)
+    vals = [int.from_bytes(k.tobytes(), "little") for k in keys]
+    assert all(v < P for v in vals)
+    run = len(lookup_ref.live_passes(vals))
+    assert run <= nlive
+    return Step("sort", "n=%d live=%s rest=%s passes=%d" % (n, live, "zero" if not rest[0] else "equal", run), [("lookup_n", n)],
+                keys=_mont(vals), n=n, passes=run, want=_mont(lookup_ref.sort_field(vals)).tobytes())
+
+
+def _gen_pair(rng, plant):
+    n = _lookup_n(rng, 2 if plant else 0)
+    draw = (lambda: int(rng.integers(0, 1 << 16))) if rng.random() < 0.5 else (lambda: _fe_int(rng))     # small values, as lookup columns hold in practice
+    kind = str(_pick(rng, ["few", "permutation", "unused"]))
+    if kind == "permutation":
+        S = list({draw() for _ in range(2 * n + 8)})[:n]
+        while len(S) < n:                                          # (65536 small values always suffice for 3 tiles + 1)
+            S = list(set(S) | {draw()})[:n]
+        A = [S[int(i)] for i in rng.permutation(n)]
+    else:
+        alphabet = [draw() for _ in range(int(rng.integers(1, 6)) if kind == "few" else int(rng.integers(6, 200)))]
+        S = [alphabet[int(i)] for i in rng.integers(0, len(alphabet), n)]
+        used = S[:max(1, n // 2)] if kind == "unused" else S     # "unused": the table has values the input never takes
+        A = [used[int(i)] for i in rng.integers(0, len(used), n)] if n else []
+    if plant:
+        table = set(S)
+        gone = next(v for v in (draw() + k for k in range(1 << 17)) if v % P not in table) % P
+        for row in sorted({int(rng.integers(0, n)), int(rng.integers(0, n))}):
+            A[row] = gone
+    note = "n=%d %s%s" % (n, kind, " small" if n and max(S) < 1 << 16 else "")
+    kw = dict(A=_mont(A), S=_mont(S), n=n)
+    try:
+        Ap, Sp = lookup_ref.permute_expression_pair(A, S)
+    except lookup_ref.NotInTable as e:
+        assert plant and e.index == lookup_ref.missing_row(A, S)
+        return Step("pair", note, [("lookup_n", n)], error=True, index=e.index, want=b"", **kw)
+    assert not plant
+    return Step("pair", note, [("lookup_n", n)], want=_mont(Ap).tobytes(), want_s=_mont(Sp).tobytes(),
+                passes=len(lookup_ref.live_passes(A)) + len(lookup_ref.live_passes(S)), **kw)
+
+
+def _draw_lookup(rng, nsteps):
+    planted = int(rng.integers(0, nsteps)) if rng.random() < P_MISSING_VALUE else -1
+    return [_gen_pair(rng, k == planted) if k == planted or rng.random() < 0.5 else _gen_sort(rng) for k in range(nsteps)]
+
+
+def _run_sort(ctx, cs, k, st):
+    if cs.host_entry:
+        _same(cs, k, st, ctx.sort_field(st.keys).tobytes(), st.want)
+    else:
+        d_in, out = ctx.to_device(st.keys), _filled(ctx, st.n)
+        try:
+            ctx.sort_field_device(d_in.ptr, st.n, out)
+        finally:
+            d_in.free()
+        _payload(cs, k, st, out, st.want)
+    if ctx.sort_last() != (st.passes, lookup_ref.MAX_PASSES - st.passes):
+        cs.mismatch("step %d %s: passes (run, skipped) = %s, the keys differ at %d positions" % (k, st.op, ctx.sort_last(), st.passes))
+
+
+def _run_pair(ctx, cs, k, st):
+    if cs.host_entry:
+        try:
+            ap, sp = ctx.lookup_permute(st.A, st.S)
+        except api.NotInTable as e:
+            return _error(cs, k, st, e.index)
+        _no_error(cs, k, st)
+        _same(cs, k, st, ap.tobytes(), st.want)
+        _same(cs, k, st, sp.tobytes(), st.want_s)
+    else:
+        d_a, d_s = ctx.to_device(st.A), ctx.to_device(st.S)
+        out_a, out_s = _filled(ctx, st.n), _filled(ctx, st.n)
+        try:
+            ctx.lookup_permute_device(d_a.ptr, d_s.ptr, st.n, out_a, out_s)
+        except api.NotInTable as e:
+            _error(cs, k, st, e.index)
+            _payload(cs, k, st, out_a, b"")                        # both outputs untouched
+            return _payload(cs, k, st, out_s, b"")
+        finally:
+            d_a.free(); d_s.free()
+        _no_error(cs, k, st)
+        _payload(cs, k, st, out_a, st.want)
+        _payload(cs, k, st, out_s, st.want_s)
+    if ctx.sort_last() != (st.passes, 2 * lookup_ref.MAX_PASSES - st.passes):
+        cs.mismatch("step %d %s: passes (run, skipped) = %s, expected %d run" % (k, st.op, ctx.sort_last(), st.passes))
+
+
+# ---- the comparisons -----------------------------------------------------------------------------------------------------------
+def _filled(ctx, n_elems, payload=None):
+    """a device buffer of n_elems elements + a zone, all 0xFF, with `payload` (an (n, 4) array) at its start"""
+    raw = np.full(n_elems * 32 + ZONE, 0xFF, np.uint8)
+    if payload is not None:
+        pb = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+        raw[:pb.size] = pb
+    return ctx.alloc(raw.size).upload(raw)
+
+
+def _payload(cs, k, st, buf, want, free=True):
+    """the buffer holds `want` at its start and 0xFF in every byte behind it"""
+    got = buf.download(np.uint8)
+    if free:
+        buf.free()
+    if got[:len(want)].tobytes() != want:
+        a, b = got[:len(want)].reshape(-1, 32), np.frombuffer(want, np.uint8).reshape(-1, 32)
+        cs.mismatch("step %d %s (%s): element %d differs from the reference" % (k, st.op, st.note, int(np.argmax((a != b).any(axis=1)))))
+    if not (got[len(want):] == 0xFF).all():
+        cs.mismatch("step %d %s (%s): written behind the output (byte %d)" % (k, st.op, st.note, len(want) + int(np.argmax(got[len(want):] != 0xFF))))
+
+
+def _same(cs, k, st, got, want):
+    if got != want:
+        cs.mismatch("step %d %s (%s): the host entry differs from the reference" % (k, st.op, st.note))
+
+
+def _error(cs, k, st, index):
+    if not st.error:
+        cs.mismatch("step %d %s (%s): refused at index %d, the reference accepts it" % (k, st.op, st.note, index))
+    if index != st.index:
+        cs.mismatch("step %d %s (%s): index %d reported, the reference's is %d" % (k, st.op, st.note, index, st.index))
+
+
+def _no_error(cs, k, st):
+    if st.error:
+        cs.mismatch("step %d %s (%s): accepted, the reference refuses index %d" % (k, st.op, st.note, st.index))
+
+
+DRAW = {"poly": _draw_poly, "domain": _draw_domain, "gate": _draw_gate, "column": _draw_column, "perm": _draw_perm, "lookup": _draw_lookup}
+RUN = {"fft": _run_fft, "kate": _run_kate, "mul": _run_mul, "coset": _run_coset, "c2e": _run_c2e, "e2c": _run_e2c, "gate": _run_gate,
+       "column": _run_column, "rlc": _run_rlc, "fp": _run_fp, "pp": _run_pp, "sort": _run_sort, "pair": _run_pair}
+
+
+def case_rng(seed, index):
+    """the generator of case `index` of a run: a function of (seed, index) alone"""
+    return np.random.default_rng([int(seed), int(index), 0x72657369])
+
+
+def draw(family, rng):
+    """the steps of one case of `family`: a pure function of rng"""
+    return DRAW[family](rng, int(rng.integers(MIN_STEPS, MAX_STEPS + 1)))
+
+
+def run(ctx, cs, steps):
+    """every step on ctx, compared at once; cs (fuzz_gpu.Case) names the case on a mismatch"""
+    for k, st in enumerate(steps):
+        RUN[st.op](ctx, cs, k, st)

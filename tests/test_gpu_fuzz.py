@@ -2,7 +2,8 @@
 input shapes (cancellation, doubling, identities), every tuning option incl. the workspace guards, the sharded entries
 with simulated ranks, divisor-witness forests and scalar-witness batches, fixed-base MSM under random table geometries and
 prefixes, the right-hand side (rhs, fraction_sums), RegularFunction::ev and L(f) on random forests (regfn) and
-compute_lhs_witness in full (lhs_witness) -- every case against a reference that is not the library."""
+compute_lhs_witness in full (lhs_witness), and chains of the resident polynomial entries (poly, domain, gate, column, perm,
+lookup: tests/fuzz_resident.py) -- every case against a reference that is not the library."""
 import collections
 
 import pytest
@@ -18,8 +19,8 @@ def test_fuzz_slice(seed):
 
 
 # The family of case k depends on (seed, k) alone (fuzz_gpu.case_kinds, no GPU involved): seed 71 reaches the five newer
-# families within its first 24 cases -- fixed 3, rhs 2, lhs_witness 2, regfn 1, fraction_sums 1 beside msm 7, lhs 6,
-# witness 1, scalar_witness 1.  The count-bound mode makes that hold whatever the machine's speed.
+# families within its first 24 cases -- fixed 3, rhs 2, lhs_witness 2, regfn 1, fraction_sums 1 beside msm 5, lhs 5,
+# witness 1, scalar_witness 1, poly 1, domain 1, gate 1.  The count-bound mode makes that hold whatever the machine's speed.
 COUNT_SEED, COUNT_CASES = 71, 24
 
 
@@ -31,3 +32,24 @@ def test_fuzz_count_bound_reaches_every_family():
     for k in fuzz_gpu.NEW_FAMILIES:                # every one of them ran to its comparison: a case that ends any other way exits
         assert seen.get(k, 0) == planned[k], (k, seen)
     assert sum(seen.values()) == COUNT_CASES
+
+
+# Seed 287 reaches the six resident families within its first 14 cases -- poly 2, domain 1, gate 1, column 1, perm 1, lookup 1 --
+# with msm 2, witness 2, lhs 1, regfn 1, fraction_sums 1 between them: their chains run on a context whose arenas and twiddle
+# table the older families have used in between.
+RESIDENT_SEED, RESIDENT_CASES = 287, 14
+
+
+def test_fuzz_count_bound_reaches_every_resident_family():
+    assert RESIDENT_CASES <= 48
+    kinds = fuzz_gpu.case_kinds(RESIDENT_SEED, RESIDENT_CASES)
+    planned = collections.Counter(kinds)
+    assert all(planned[k] >= 1 for k in fuzz_gpu.RESIDENT_FAMILIES), planned
+    first, last = (f(i for i, k in enumerate(kinds) if k in fuzz_gpu.RESIDENT_FAMILIES) for f in (min, max))
+    assert len({k for k in kinds[first:last] if k not in fuzz_gpu.RESIDENT_FAMILIES}) >= 3, kinds      # older families between them
+    assert fuzz_gpu.main(secs=0.0, seed=RESIDENT_SEED, cases=RESIDENT_CASES) == RESIDENT_CASES
+    seen = dict(fuzz_gpu.LAST_KINDS)
+    for k in planned:                              # every planned case of every family ran to its comparison (witness* may end in a panic both sides report)
+        got = seen.get(k, 0) + (seen.get(k + "(panic)", 0) if k in ("witness", "scalar_witness") else 0)
+        assert got == planned[k], (k, seen)
+    assert sum(seen.values()) == RESIDENT_CASES

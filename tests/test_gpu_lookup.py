@@ -1,7 +1,8 @@
 """lemsm_sort_field* and lemsm_lookup_permute* on the GPU against tests/lookup_ref.py: exact equality of every
 field element, behind 0xFF-filled outputs with a zone behind them.  The sizes come from the library's own geometry
-(lemsm_sort_field_geometry): the tile of a pass.  The references work on standard-form integers (raw value times R^-1): that
-is the order the entries sort by."""
+(lemsm_sort_field_geometry): the tile of a pass, and, in the last section, from lemsm_debug_sort_thresholds: the sizes above
+which the conversion and the scans take another path.  The references work on standard-form integers (raw value times R^-1):
+that is the order the entries sort by."""
 import ctypes
 import random
 
@@ -474,3 +475,215 @@ def test_chain_lookup_product_and_row_identity(ctx):
     assert any(broken[n - 1:])
     _, same = quotient(ctx.to_device(changed_repeat))                    # the change the row expression cannot see (the product did)
     assert not any(same[n - 1:])
+
+
+# ---- sizes past the two thresholds of the sort (lemsm_debug_sort_thresholds) ---------------------------------------------------
+# Single-block stages and capped grids of the resident entries, the size above which each takes another path, and the test that
+# crosses it (profiles/fuzz_resident/thresholds.md has the whole list, the stages without a threshold included):
+#   k_ls_convert, grid capped at LS_CONVERT_BLOCKS      n > convert_keys_per_trip     test_sort_conversion_second_trip
+#   k_scan_top, flag scan of the permuted pair          2 n + 1 > scan_top_words      test_pair_flag_scan_past_one_sum_per_thread
+#   k_scan_top, tile table of a sort                    tiles > scan_top_words / 256  test_sort_tile_table_scan_past_one_sum_per_thread
+# The sizes are the library's own, so a change of either constant moves these tests with it.  The columns are table[idx] of a
+# small table of distinct values converted once with Python integers; a sorted column is sorted_table[sort(rank[idx])].
+THR = api.debug_sort_thresholds()
+CONVERT_TRIP, SCAN_TOP = THR["convert_keys_per_trip"], THR["scan_top_words"]
+N_CONVERT = CONVERT_TRIP + TILE + 5
+N_FLAGS = SCAN_TOP // 2 + 1
+N_TABLE = (SCAN_TOP // (1 << DIGIT_BITS)) * TILE + TILE + 1
+_CACHE = {}
+
+
+def _cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+class _Table:
+    """distinct standard-form values: their Montgomery rows, the rows in ascending order, the rank of each"""
+
+    def __init__(self, vals):
+        assert len(set(vals)) == len(vals) <= 65536 and max(vals) < P
+        self.vals = list(vals)
+        self.mont = _mont(self.vals)
+        order = np.array(sorted(range(len(vals)), key=self.vals.__getitem__), np.int64)
+        self.sorted_mont = self.mont[order]
+        self.rank = np.empty(len(vals), np.int64)
+        self.rank[order] = np.arange(len(vals))
+        self.index = {v: k for k, v in enumerate(self.vals)}
+
+    def rows(self, ints):
+        """standard-form integers of the table -> their Montgomery rows"""
+        return self.mont[np.fromiter((self.index[v] for v in ints), np.int64, len(ints))]
+
+
+def _sort_rows(ctx, keys, want, run):
+    """one device sort of the Montgomery rows `keys`: `want` behind the zone, the passes, the figures"""
+    n = keys.shape[0]
+    d_in = ctx.to_device(keys)
+    out = _filled(ctx, n)
+    ctx.sort_field_device(d_in.ptr, n, out)
+    got = out.download(np.uint8)
+    passes, by = ctx.sort_last(), ctx.poly_last()[1]
+    d_in.free()
+    out.free()
+    assert passes == (run, MAX_PASSES - run), passes
+    assert by == ref.sort_bytes(n, run)
+    assert np.array_equal(got[:n * 32].view(np.uint64).reshape(n, 4), want)
+    assert (got[n * 32:] == 0xFF).all(), "written behind the output"
+    return got[:n * 32]
+
+
+def _second_trip_case(full_width):
+    """keys below convert_keys_per_trip differ in byte P0 alone; the keys behind it also in P1 (low 16 bytes) and P2 (high), or
+    they are full-width random values: only the second trip of the conversion sees those positions differ"""
+    P0, P1, P2 = 5, 11, 22
+    rng = random.Random(7600 + full_width)
+    base = int.from_bytes(bytes([0x11 + (k % 7) for k in range(32)]), "little")
+
+    def with_bytes(v, pairs):
+        for pos, b in pairs:
+            v = (v & ~(0xFF << (8 * pos))) | (b << (8 * pos))
+        return v
+
+    early = [with_bytes(base, [(P0, b)]) for b in range(256)]
+    if full_width:
+        late = list({rng.randrange(P) for _ in range(512)} - set(early))
+    else:
+        late = list({with_bytes(base, [(P0, rng.randrange(256)), (P1, rng.randrange(256)), (P2, rng.randrange(256))]) for _ in range(512)} - set(early))
+    live = ref.live_passes(late)
+    assert ref.live_passes(early) == [P0] and (len(live) == MAX_PASSES if full_width else live == [P0, P1, P2])
+    tab = _Table(early + late)
+    nrng = np.random.default_rng(7600 + full_width)
+    idx = np.concatenate([nrng.integers(0, 256, CONVERT_TRIP), nrng.integers(256, len(tab.vals), N_CONVERT - CONVERT_TRIP)])
+    assert len(set(idx[CONVERT_TRIP:].tolist())) > 256                  # (the late keys do differ in P1 and P2 among themselves)
+    return tab.mont[idx], tab.sorted_mont[np.sort(tab.rank[idx])]
+
+
+def _conversion_second_trip(ctx, full_width):
+    keys, want = _cached(("trip", full_width), lambda: _second_trip_case(full_width))
+    _sort_rows(ctx, keys, want, MAX_PASSES if full_width else 3)
+
+
+def test_thresholds_are_the_ones_the_sizes_assume():
+    assert CONVERT_TRIP % TILE == 0 and SCAN_TOP % TILE == 0 and SCAN_TOP % (2 << DIGIT_BITS) == 0
+    assert NEAR_2_17 < CONVERT_TRIP < N_CONVERT and 2 * N_FLAGS + 1 > SCAN_TOP and N_TABLE <= 1 << 28
+    assert ((N_TABLE + TILE - 1) // TILE) << DIGIT_BITS > SCAN_TOP         # the tile table of N_TABLE keys
+    assert ((NEAR_2_17 + TILE - 1) // TILE) << DIGIT_BITS <= SCAN_TOP and 2 * NEAR_2_17 + 1 <= SCAN_TOP   # ... the older sizes stay below
+
+
+@pytest.mark.parametrize("full_width", [False, True])
+def test_sort_conversion_second_trip(ctx, full_width):
+    """a conversion that folds only its first trip into the OR / AND words skips the passes of P1 and P2 (or 31 of 32): the
+    column and the pass count are both wrong; a wrong stride leaves keys unconverted"""
+    _conversion_second_trip(ctx, full_width)
+
+
+def _flag_scan_cases():
+    """name -> (A rows, S rows, A' rows, S' rows) at N_FLAGS rows, by lookup_ref on the tables' integers"""
+    n = N_FLAGS
+    nrng = np.random.default_rng(7700)
+    rng = random.Random(7700)
+    small = _Table(rng.sample(range(1 << 16), 40000))
+    si = nrng.integers(0, len(small.vals), n)
+    few = si[[1, n // 2, n - 2]]
+    ai = few[nrng.integers(0, 3, n)]
+    out = {}
+    S, A = [small.vals[k] for k in si], [small.vals[k] for k in ai]
+    wa, ws = ref.permute_expression_pair(A, S)
+    repeats = sum(1 for r in range(1, n) if wa[r] == wa[r - 1])
+    assert repeats >= n - 3
+    out["straddle"] = (small.mont[ai], small.mont[si], small.rows(wa), small.rows(ws))
+    distinct = list({rng.randrange(P) for _ in range(n + 64)})[:n]        # no repeats: every flag is 0, R = 0
+    assert len(distinct) == n
+    perm = distinct[:]
+    rng.shuffle(perm)
+    wa, ws = ref.permute_expression_pair(perm, distinct)
+    assert wa == ws
+    out["permutation"] = (_mont(perm), _mont(distinct), _mont(wa), _mont(ws))
+    return out
+
+
+def _pair_rows(ctx, a, s, want_a, want_s):
+    n = a.shape[0]
+    d_a, d_s = ctx.to_device(a), ctx.to_device(s)
+    out_a, out_s = _filled(ctx, n), _filled(ctx, n)
+    ctx.lookup_permute_device(d_a.ptr, d_s.ptr, n, out_a, out_s)
+    got = [o.download(np.uint8) for o in (out_a, out_s)]
+    run, skipped = ctx.sort_last()
+    for d in (d_a, d_s, out_a, out_s):
+        d.free()
+    assert run + skipped == 2 * MAX_PASSES and ctx.poly_last()[1] == ref.lookup_bytes(n, run)
+    for g, want, name in zip(got, (want_a, want_s), ("A'", "S'")):
+        assert np.array_equal(g[:n * 32].view(np.uint64).reshape(n, 4), want), name
+        assert (g[n * 32:] == 0xFF).all(), "written behind " + name
+
+
+@pytest.mark.parametrize("name", ["straddle", "permutation"])
+def test_pair_flag_scan_past_one_sum_per_thread(ctx, name):
+    """2 n + 1 flag words > scan_top_words: every thread of the scan's top block takes two block sums.  straddle: three values
+    of a table of small values, nearly every row a repeat, so the leftovers and the repeat ranks cross every scan block;
+    permutation: no repeat and no leftover"""
+    _pair_rows(ctx, *_cached("flags", _flag_scan_cases)[name])
+
+
+def test_pair_flag_scan_size_missing_value(ctx):
+    """at the same size: the smallest missing value stands in a row of the first scan block and in one of the last, a larger
+    missing value in a lower row still: the lowest row of the smallest one, and nothing is written"""
+    n = N_FLAGS
+    a, s, _, _ = _cached("flags", _flag_scan_cases)["straddle"]
+    gone, bigger = 1 << 17, 1 << 18                                        # above every table value (they are below 2^16)
+    scan_block = SCAN_TOP // 256
+    assert 7 < scan_block < n - 1                                          # row 7 in the first scan block, row n - 1 in the last
+    a = a.copy()
+    a[3] = _mont([bigger])[0]
+    a[7] = a[n - 1] = _mont([gone])[0]
+    d_a, d_s = ctx.to_device(a), ctx.to_device(s)
+    out_a, out_s = _filled(ctx, n), _filled(ctx, n)
+    with pytest.raises(api.NotInTable) as e:
+        ctx.lookup_permute_device(d_a.ptr, d_s.ptr, n, out_a, out_s)
+    assert e.value.index == 7
+    _untouched(out_a)
+    _untouched(out_s)
+    for d in (d_a, d_s, out_a, out_s):
+        d.free()
+
+
+def _tile_table_case():
+    """(full-width keys and their sorted column; keys below 2^16 with one large key behind them, and their sorted column)"""
+    rng = random.Random(7800)
+    nrng = np.random.default_rng(7800)
+    tab = _Table(list({rng.randrange(P) for _ in range(4200)})[:4096])
+    assert len(tab.vals) == 4096 and len(ref.live_passes(tab.vals)) == MAX_PASSES
+    idx = nrng.integers(0, 4096, N_TABLE)
+    small = _Table(rng.sample(range(1 << 16), 4096) + [P - 12345])
+    assert ref.live_passes(small.vals[:-1]) == [0, 1]
+    sidx = np.concatenate([nrng.integers(0, 4096, N_TABLE), [4096]])
+    return (tab.mont[idx], tab.sorted_mont[np.sort(tab.rank[idx])]), (small.mont[sidx], small.sorted_mont[np.sort(small.rank[sidx])])
+
+
+def _tile_table_full_width(ctx):
+    keys, want = _cached("tiles", _tile_table_case)[0]
+    _sort_rows(ctx, keys, want, MAX_PASSES)
+
+
+def test_sort_tile_table_scan_past_one_sum_per_thread(ctx):
+    """more than scan_top_words / 256 tiles: the scan of every pass's tile table takes two block sums per thread of its top
+    block.  4096 full-width values: all passes run and use every bin"""
+    _tile_table_full_width(ctx)
+
+
+def test_sort_tile_table_scan_small_values(ctx):
+    """at the same size, values below 2^16: two passes, and the same bytes as the first n rows of the full-width sort of the same
+    keys with one large key added"""
+    keys, want = _cached("tiles", _tile_table_case)[1]
+    n = N_TABLE
+    a = _sort_rows(ctx, keys[:n], want[:n], 16 // DIGIT_BITS)
+    b = _sort_rows(ctx, keys, want, MAX_PASSES)
+    assert a.tobytes() == b[:n * 32].tobytes()
+
+
+def test_past_the_thresholds_with_guards(canary):
+    _conversion_second_trip(canary, False)
+    _pair_rows(canary, *_cached("flags", _flag_scan_cases)["straddle"])
+    _tile_table_full_width(canary)

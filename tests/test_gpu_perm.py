@@ -245,6 +245,44 @@ def test_engine_host_twin_and_repeat(ctx):
     assert empty.shape == (0, 4) and tap5.tobytes() == _fe(init).tobytes()
 
 
+def _first_n_with_a_longer_segment():
+    """the smallest n whose scan segment is longer than SEG, by bisection on the library's own geometry (pure host)"""
+    lo, hi = NEAR_2_17, 1 << 26
+    assert api.fraction_products_geometry(hi)["segment"] > SEG
+    while lo + 1 < hi:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if api.fraction_products_geometry(mid)["segment"] > SEG else (mid, hi)
+    return hi
+
+
+def test_engine_longer_segments(ctx):
+    """A column is cut into a bounded number of segments, so past a size the segment itself grows: every size above runs with
+    segments of SEG rows.  The smallest n with a longer segment, plus a ragged tail; the columns are drawn from two tables of
+    64 values (converted once), the reference walks the rows' (numerator, denominator) pairs: the whole output, a tap in it, and
+    the tap of the last segment alone."""
+    n = _first_n_with_a_longer_segment() + 5
+    geo = api.fraction_products_geometry(n)
+    assert geo["segment"] > SEG and api.fraction_products_geometry(n - 6)["segment"] == SEG and geo["tile"] == TILE
+    rng, nrng = random.Random(53000), np.random.default_rng(53000)
+    num_t, den_t = [rng.randrange(P) for _ in range(64)], [rng.randrange(1, P) for _ in range(64)]
+    ni, di = nrng.integers(0, 64, n), nrng.integers(0, 64, n)
+    init = rng.randrange(1, P)
+    want, total = ref.running_products([(num_t[a], den_t[b]) for a, b in zip(ni.tolist(), di.tolist())], init, n)
+    d_num, d_den = ctx.to_device(_mont(num_t)[ni]), ctx.to_device(_mont(den_t)[di])
+    out = _filled(ctx, n)
+    tap = n // 2 + 3
+    _, got_tap = ctx.fraction_products_device([d_num.ptr], [d_den.ptr], n, _fe(init), out=out, tap=tap)
+    got = out.download(np.uint8)
+    out.free()
+    assert _ints(got_tap) == [want[tap] * R % P]
+    assert got[:n * 32].tobytes() == _mont(want).tobytes()
+    assert (got[n * 32:] == 0xFF).all(), "written behind the output"
+    for tap, value in ((n - 2, want[n - 2]), (n, total)):               # the tap alone: its segment only, and the product of all rows
+        _, got_tap = ctx.fraction_products_device([d_num.ptr], [d_den.ptr], n, _fe(init), want_out=False, tap=tap)
+        assert _ints(got_tap) == [value * R % P], tap
+    d_num.free(); d_den.free()
+
+
 @pytest.fixture
 def canary(ctx):
     ctx.set_option("ws_canary", 1)
@@ -321,6 +359,15 @@ def test_permutation_across_tiles(ctx, ncols, chunk, u, delta):
     assert (1 << logn) > TILE
     values, sigmas = _random_columns(logn, ncols)
     _perm(ctx, values, sigmas, logn, *_challenges(77 + ncols), delta, chunk, u)
+
+
+def test_permutation_third_power_table(ctx):
+    """logn 17: the row's point delta^j w^i is a product of three table entries from 2^16 rows on (csrc/domain.cuh: pow_at), of
+    two below; the sizes above stop at 2^13.  Two columns in one set, halo2's delta, u in the rows only the third table reaches"""
+    logn = 17
+    values, sigmas = _random_columns(logn, 2)
+    zs, taps = _perm(ctx, values, sigmas, logn, *_challenges(177), ref.DELTA, 2, (1 << 16) + 12345)
+    assert zs[0][0] == 1 and taps[0] == zs[0][(1 << 16) + 12345]
 
 
 @pytest.mark.parametrize("u", [37, 63])

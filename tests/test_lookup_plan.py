@@ -31,6 +31,23 @@ def test_geometry():
     assert e.value.status == BAD_ARG
 
 
+def test_sort_thresholds():
+    """lemsm_debug_sort_thresholds: no context, every output optional; both sizes are whole tiles, inside the entry's range, and
+    the GPU tests that cross them (tests/test_gpu_lookup.py) stay inside it as well"""
+    thr = api.debug_sort_thresholds()
+    assert api.Context.debug_sort_thresholds() == thr and set(thr) == {"convert_keys_per_trip", "scan_top_words"}
+    tile, bins = GEO["tile"], 1 << GEO["digit_bits"]
+    for v in thr.values():
+        assert v > 0 and v % tile == 0
+    assert thr["scan_top_words"] % (2 * bins) == 0
+    assert thr["convert_keys_per_trip"] + tile + 5 <= ref.MAX_N and (thr["scan_top_words"] // bins + 1) * tile + 1 <= ref.MAX_N
+    lib = _lib.load()
+    assert lib.lemsm_debug_sort_thresholds(None, None) == _lib.LEMSM_OK
+    c, s = ctypes.c_size_t(77), ctypes.c_size_t(77)
+    assert lib.lemsm_debug_sort_thresholds(ctypes.byref(c), None) == _lib.LEMSM_OK and lib.lemsm_debug_sort_thresholds(None, ctypes.byref(s)) == _lib.LEMSM_OK
+    assert (c.value, s.value) == (thr["convert_keys_per_trip"], thr["scan_top_words"])
+
+
 def test_plan_bytes_and_workspace():
     for n in (0, 1, 2, GEO["tile"] - 1, GEO["tile"], GEO["tile"] + 1, (1 << 17) + 37, 1 << 24, 1 << 28):
         got = api.lookup_permute_plan(n)
