@@ -18,4 +18,5 @@ from .api import (  # noqa: F401
     domain_plan, vanishing_on_cosets, EXT_INTERLEAVED, EXT_COSET_MAJOR,
     fraction_products_geometry, permutation_plan, permutation_products,
     sort_field_geometry, lookup_permute_plan, permute_expression_pair, NotInTable, debug_sort_thresholds,
+    poly_lincomb, divide_by_roots, open_quotient, lagrange_interpolate, open_plan,
 )

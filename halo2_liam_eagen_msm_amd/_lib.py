@@ -34,6 +34,8 @@ LEMSM_FORM_MONTGOMERY = 0
 LEMSM_FORM_CANONICAL = 1
 LEMSM_EXT_INTERLEAVED = 0
 LEMSM_EXT_COSET_MAJOR = 1
+LEMSM_OPEN_MAX_ROOTS = 8
+LEMSM_OPEN_MAX_POLYS = 4096
 
 BN254_G1 = 0
 GRUMPKIN = 1
@@ -79,6 +81,8 @@ SYMBOLS = [
     "lemsm_permutation_plan", "lemsm_permutation_product_device", "lemsm_permutation_product",
     "lemsm_sort_field_geometry", "lemsm_lookup_permute_plan", "lemsm_sort_field_device", "lemsm_sort_field",
     "lemsm_lookup_permute_device", "lemsm_lookup_permute", "lemsm_sort_last", "lemsm_debug_sort_thresholds",
+    "lemsm_poly_lincomb_device", "lemsm_poly_lincomb", "lemsm_poly_divide_roots_device", "lemsm_poly_divide_roots",
+    "lemsm_open_quotient_device", "lemsm_open_quotient", "lemsm_open_plan", "lemsm_lagrange_interpolate",
 ]
 
 
@@ -274,6 +278,14 @@ def load() -> ctypes.CDLL:
         "lemsm_lookup_permute": (i, [vp, u64p, u64p, sz, u64p, u64p, szp]),
         "lemsm_sort_last": (i, [vp, u32p, u32p]),
         "lemsm_debug_sort_thresholds": (i, [szp, szp]),
+        "lemsm_poly_lincomb_device": (i, [vp, vp, vp, sz, u64p, u64p, sz, vp, sz, szp]),
+        "lemsm_poly_lincomb": (i, [vp, vp, vp, sz, u64p, u64p, sz, u64p, sz, szp]),
+        "lemsm_poly_divide_roots_device": (i, [vp, vp, sz, u64p, sz, i, vp, sz, u64p, szp]),
+        "lemsm_poly_divide_roots": (i, [vp, u64p, sz, u64p, sz, i, u64p, sz, u64p, szp]),
+        "lemsm_open_quotient_device": (i, [vp, vp, vp, sz, u64p, u64p, sz, u64p, sz, i, vp, sz, szp, u64p, szp]),
+        "lemsm_open_quotient": (i, [vp, vp, vp, sz, u64p, u64p, sz, u64p, sz, i, u64p, sz, szp, u64p, szp]),
+        "lemsm_open_plan": (i, [vp, sz, sz, sz, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), szp]),
+        "lemsm_lagrange_interpolate": (i, [u64p, u64p, sz, u64p, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -846,6 +846,80 @@ class Context:
         self._check(self.lib.lemsm_poly_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
 
+    # ---- multipoint openings on resident polynomials: combine, divide by roots ----
+    @staticmethod
+    def _dev(b) -> Optional[int]:
+        return b.ptr if isinstance(b, DeviceBuffer) else b
+
+    def _open_terms(self, polys, lens, coeffs, low):
+        ptrs = (ctypes.c_void_p * max(len(polys), 1))(*[self._dev(b) for b in polys])
+        ln = np.ascontiguousarray(lens, np.uintp).reshape(-1)
+        cf = np.ascontiguousarray(coeffs, np.uint64).reshape(-1, 4)
+        if not (len(polys) == ln.size == cf.shape[0]):
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "polys, lens and coeffs differ in length")
+        lw = None if low is None else np.ascontiguousarray(low, np.uint64).reshape(-1, 4)
+        return ptrs, ln, cf, lw
+
+    def poly_lincomb(self, polys, lens, coeffs, low=None, out: Optional[DeviceBuffer] = None):
+        """out[i] = sum_{j : i < lens[j]} c_j p_j[i] - (i < k_low ? low[i] : 0) over resident polynomials: polys = J
+        DeviceBuffers (or device pointers; None for an empty one) of lens[j] coefficients (32 B, raw Montgomery), coeffs
+        (J, 4) limbs, low (k_low <= 8, 4) limbs or None.  Returns (out, length): `out` as given, or a new DeviceBuffer of
+        max(max lens, k_low) coefficients."""
+        ptrs, ln, cf, lw = self._open_terms(polys, lens, coeffs, low)
+        need = max([int(v) for v in ln] + [0 if lw is None else lw.shape[0]])
+        if out is None:
+            out = self.alloc(max(need, 1) * 32)
+        n = ctypes.c_size_t(0)
+        self._check(self.lib.lemsm_poly_lincomb_device(self.h, ptrs, _ptr(ln) if ln.size else None, ln.size, _ptr(cf) if cf.size else None,
+                                                       _ptr(lw) if lw is not None and lw.size else None, 0 if lw is None else lw.shape[0],
+                                                       self._dev(out), out.nbytes // 32, ctypes.byref(n)))
+        return out, n.value
+
+    def divide_by_roots(self, poly, length: int, roots, canonical: bool = False, out: Optional[DeviceBuffer] = None):
+        """a_0 = the `length` resident coefficients of `poly`, a_(i+1) = kate_division(a_i, roots[i]) for the k <= 8 roots
+        ((k, 4) limbs): returns (quotient, remainders) -- quotient a DeviceBuffer (`out`, or a new one) holding length - k
+        coefficients (raw Montgomery, or 32-byte standard form with canonical=True: the scalars msm_device takes), remainders
+        (k, 4) limbs a_i(roots[i]), all zero exactly when prod (X - roots[i]) divides the polynomial.  length < k:
+        RefArithmeticOverflow (.index = the stage that meets an empty polynomial)."""
+        rt = np.ascontiguousarray(roots, np.uint64).reshape(-1, 4)
+        k = rt.shape[0]
+        if out is None:
+            out = self.alloc(max(length - k, 1) * 32)
+        rem = np.zeros((max(k, 1), 4), np.uint64)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_poly_divide_roots_device(self.h, self._dev(poly), length, _ptr(rt) if k else None, k,
+                                                     _lib.LEMSM_FORM_CANONICAL if canonical else _lib.LEMSM_FORM_MONTGOMERY,
+                                                     self._dev(out), out.nbytes // 32, _ptr(rem), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out, rem[:k]
+
+    def open_quotient(self, polys, lens, coeffs, low, roots, canonical: bool = False, out: Optional[DeviceBuffer] = None):
+        """(sum_j c_j p_j - low) / prod_i (X - roots[i]) in one call (poly_lincomb into the workspace, then divide_by_roots):
+        returns (quotient DeviceBuffer, its length, remainders (k, 4))."""
+        ptrs, ln, cf, lw = self._open_terms(polys, lens, coeffs, low)
+        rt = np.ascontiguousarray(roots, np.uint64).reshape(-1, 4)
+        k = rt.shape[0]
+        need = max([int(v) for v in ln] + [0 if lw is None else lw.shape[0]]) - k
+        if out is None:
+            out = self.alloc(max(need, 1) * 32)
+        rem = np.zeros((max(k, 1), 4), np.uint64)
+        n, bad = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = self.lib.lemsm_open_quotient_device(self.h, ptrs, _ptr(ln) if ln.size else None, ln.size, _ptr(cf) if cf.size else None,
+                                                 _ptr(lw) if lw is not None and lw.size else None, 0 if lw is None else lw.shape[0],
+                                                 _ptr(rt) if k else None, k,
+                                                 _lib.LEMSM_FORM_CANONICAL if canonical else _lib.LEMSM_FORM_MONTGOMERY,
+                                                 self._dev(out), out.nbytes // 32, ctypes.byref(n), _ptr(rem), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out, n.value, rem[:k]
+
+    def lagrange_interpolate(self, points, evals) -> np.ndarray:
+        """the k <= 8 coefficients ((k, 4) limbs, lowest first) of the polynomial through (points[i], evals[i]) ((k, 4) limbs
+        each); two equal points: RefDivisionByZero (.index = the later one).  Pure host."""
+        return _lagrange_limbs(points, evals)
+
+    def open_plan(self, lens, k_low: int, k: int) -> dict:
+        return open_plan(lens, k_low, k)
+
     # ---- halo2's EvaluationDomain on resident data: coset and extended-domain transforms (DESIGN 7d) ----
     def _coset_args(self, omega, shift, scale):
         w = np.ascontiguousarray(omega, np.uint64).reshape(4)
@@ -1998,6 +2072,77 @@ def permute_expression_pair(input, table, ctx: Optional[Context] = None):
         raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "input and table columns differ in length")
     ap, sp = (ctx or default_context()).lookup_permute(mont(input), mont(table))
     return std(ap), std(sp)
+
+
+def _fr_mont(vals) -> np.ndarray:
+    R = 1 << 256
+    return np.frombuffer(b"".join((int(v) % FR_MODULUS * R % FR_MODULUS).to_bytes(32, "little") for v in vals), np.uint64).reshape(-1, 4).copy() \
+        if len(vals) else np.zeros((0, 4), np.uint64)
+
+
+def _fr_std(arr) -> List[int]:
+    b, ri = np.ascontiguousarray(arr).tobytes(), pow(1 << 256, -1, FR_MODULUS)
+    return [int.from_bytes(b[i:i + 32], "little") * ri % FR_MODULUS for i in range(0, len(b), 32)]
+
+
+def _lagrange_limbs(points, evals) -> np.ndarray:
+    x = np.ascontiguousarray(points, np.uint64).reshape(-1, 4)
+    y = np.ascontiguousarray(evals, np.uint64).reshape(-1, 4)
+    if x.shape[0] != y.shape[0]:
+        raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "points and evals differ in length")
+    out = np.zeros((max(x.shape[0], 1), 4), np.uint64)
+    bad = ctypes.c_size_t(0)
+    rc = _lib.load().lemsm_lagrange_interpolate(_ptr(x) if x.size else None, _ptr(y) if y.size else None, x.shape[0], _ptr(out), ctypes.byref(bad))
+    if rc == _lib.LEMSM_ERR_DIVISION_BY_ZERO:
+        raise RefDivisionByZero(rc, "lagrange_interpolate: two equal points", bad.value)
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, "lemsm_lagrange_interpolate: 1 .. 8 points, canonical field elements")
+    return out[:x.shape[0]]
+
+
+def open_plan(lens, k_low: int = 0, k: int = 0) -> dict:
+    """lemsm_open_plan: what open_quotient does for polynomials of these lengths, k_low low coefficients and k roots (k = 0:
+    poly_lincomb alone): the quotient's length, the bytes and field products the call is priced at, its device workspace"""
+    ln = np.ascontiguousarray(lens, np.uintp).reshape(-1)
+    n, ws = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    by, fm = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = _lib.load().lemsm_open_plan(_ptr(ln) if ln.size else None, ln.size, k_low, k, ctypes.byref(n), ctypes.byref(by), ctypes.byref(fm), ctypes.byref(ws))
+    if rc == _lib.LEMSM_ERR_ARITH_OVERFLOW:
+        raise RefArithmeticOverflow(rc, "open_plan: fewer coefficients than roots", 0)
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, "lemsm_open_plan: 1 .. 4096 lengths up to 2^28, k_low and k up to 8")
+    return {"len_out": n.value, "bytes": by.value, "field_mults": fm.value, "workspace_bytes": ws.value}
+
+
+def lagrange_interpolate(points, evals) -> List[int]:
+    """halo2's lagrange_interpolate over standard-form integers mod r: the coefficients, lowest first, of the polynomial of
+    degree < k through (points[i], evals[i]), k <= 8.  Two equal points: RefDivisionByZero (.index = the later one)."""
+    return _fr_std(_lagrange_limbs(_fr_mont(points), _fr_mont(evals)))
+
+
+def poly_lincomb(polys, coeffs, low=(), ctx: Optional[Context] = None) -> List[int]:
+    """sum_j coeffs[j] polys[j](X) - low(X) over standard-form integers mod r (polys: coefficient lists, lowest first, ragged;
+    low: at most 8 coefficients): the max(max len, len(low)) coefficients"""
+    ctx = ctx or default_context()
+    bufs = [ctx.to_device(_fr_mont(p)) if len(p) else None for p in polys]
+    out, n = ctx.poly_lincomb(bufs, [len(p) for p in polys], _fr_mont(coeffs), _fr_mont(low) if len(low) else None)
+    return _fr_std(out.download(np.uint64, n * 32))
+
+
+def divide_by_roots(a, roots, ctx: Optional[Context] = None) -> Tuple[List[int], List[int]]:
+    """successive kate_division of a (standard-form integers, lowest first) by (X - roots[i]), k <= 8: (quotient, remainders)
+    with remainders[i] the value stage i drops -- all zero exactly when prod (X - roots[i]) divides a"""
+    ctx = ctx or default_context()
+    q, rem = ctx.divide_by_roots(ctx.to_device(_fr_mont(a)) if len(a) else None, len(a), _fr_mont(roots))
+    return _fr_std(q.download(np.uint64, (len(a) - len(roots)) * 32)), _fr_std(rem)
+
+
+def open_quotient(polys, coeffs, low, roots, ctx: Optional[Context] = None) -> Tuple[List[int], List[int]]:
+    """(sum_j coeffs[j] polys[j] - low) / prod_i (X - roots[i]) over standard-form integers mod r: (quotient, remainders)"""
+    ctx = ctx or default_context()
+    bufs = [ctx.to_device(_fr_mont(p)) if len(p) else None for p in polys]
+    q, n, rem = ctx.open_quotient(bufs, [len(p) for p in polys], _fr_mont(coeffs), _fr_mont(low) if len(low) else None, _fr_mont(roots))
+    return _fr_std(q.download(np.uint64, n * 32)), _fr_std(rem)
 
 
 def _neg_affine_raw(curve_id: int, pts: np.ndarray) -> np.ndarray:

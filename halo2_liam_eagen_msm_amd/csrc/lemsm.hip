@@ -34,6 +34,7 @@
 #include "gate.cuh"
 #include "perm.cuh"
 #include "lookup.cuh"
+#include "open.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -73,7 +74,7 @@ struct Options {
   long host_threads = 0, window_bits = 0, chunk = 0, tile = 0, field = 0, accum_waves = 0, groups = 0, host_slab_bits = 0, slab_bits = 0,
        abi_points = 0, stage2x = 0, xcd_windows = 0, entry_ring = 0, validate_points = 0, pyr_fuse = 0, pyr_first2 = 0, pyr_quad = 0,
        ws_canary = 0, binsort = 0, merge_slice = 0, merge_wave_th = 0, slab_tail = 0, scatter_lean = 0, ntt_tiled = 0, dw_wrap = 0,
-       dw_fuse = 0, dw_kb = 0, dw_reuse = 0, dw_pw_lazy = 0, dw_halves = 0, dw_ntt_lazy = 0;
+       dw_fuse = 0, dw_kb = 0, dw_reuse = 0, dw_pw_lazy = 0, dw_halves = 0, dw_ntt_lazy = 0, open_group = 0;
 };
 
 // fn(Traits{}) for the curve id; callers have checked the id (check_curve, or the inline test of the context-free entries)
@@ -1924,6 +1925,7 @@ static const struct OptionRow { const char* name; long Options::*field; long lo,
   {"dw_reuse", &Options::dw_reuse, 2, 2, true},
   {"dw_wrap", &Options::dw_wrap, 2, 2, true},
   {"ntt_tiled", &Options::ntt_tiled, 2, 2, true},
+  {"open_group", &Options::open_group, 1, 5, true},           // terms of k_open_lincomb that share one reduction (A/B knob of DESIGN 7h; 0: 5)
 };
 
 int lemsm_set_option(lemsm_ctx* ctx, const char* name, long value) {
@@ -2789,3 +2791,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "gate_abi.inc"
 #include "perm_abi.inc"
 #include "lookup_abi.inc"
+#include "open_abi.inc"

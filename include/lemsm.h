@@ -125,7 +125,9 @@ size_t lemsm_last_truncated_count(const lemsm_ctx* ctx);
    soak turns it on at random), "validate_points" (1: lemsm_msm*, lemsm_lhs_msm* check y^2 = x^3 + b for every non-identity input point
    before any work and return LEMSM_ERR_BAD_ARG with the index in lemsm_last_bad_index; 0, the default, trusts the
    caller like the reference's from_raw_bytes_unchecked does -- the hot kernel tests y alone for the identity,
-   so an invalid (x != 0, y == 0) input would otherwise be skipped silently). */
+   so an invalid (x != 0, y == 0) input would otherwise be skipped silently), "open_group" (lemsm_poly_lincomb* /
+   lemsm_open_quotient*: terms of the combination that share one Montgomery reduction, 1 .. 5; 0 = 5, the most one
+   conditional subtraction allows; 1 = a reduction per term: A/B knob, the bytes do not depend on it). */
 int lemsm_set_option(lemsm_ctx* ctx, const char* name, long value);
 /* Device-time (ms, from HIP events on the context's stream) of the last MSM call: whole
    pipeline in [0], the dominant accumulate kernel in [1], its launch count in [2]. */
@@ -631,6 +633,62 @@ int lemsm_poly_mul(lemsm_ctx* ctx, const uint64_t* a, size_t la, const uint64_t*
 /* Device time (ms, HIP events around the launches on the context's stream) of the last lemsm_fft* / lemsm_kate_division* /
    lemsm_poly_mul* call, and the bytes and field multiplications it is priced at.  (:45-47, :102-129, :209-216) */
 int lemsm_poly_last(const lemsm_ctx* ctx, double* ms, uint64_t* bytes, uint64_t* field_mults);
+
+/* ---- Multipoint openings on resident polynomials: combine, divide by roots --------------------------------
+   The polynomial work of the last round of a halo2 proof (GWC or SHPLONK): q = (sum_j c_j p_j - r) / prod_i (X - z_i) over
+   polynomials that stay in HBM.  bn256::Fr, 32-byte raw Montgomery elements, the conventions of the entries above: a field
+   argument that is not canonical is LEMSM_ERR_BAD_ARG, LEMSM_ERR_BAD_ARG leaves nothing queued and the outputs untouched
+   (a capacity that is too small sets the length output first), the figures of every call go to lemsm_poly_last, option
+   ws_canary guards every carved workspace.  The arithmetic is exact and every sum runs in one fixed order: the host entry,
+   the device entry and a repeated call give the same bytes. */
+#define LEMSM_OPEN_MAX_ROOTS 8       /* roots of one division, coefficients of `low` */
+#define LEMSM_OPEN_MAX_POLYS 4096    /* polynomials of one combination */
+/* out[i] = sum_{j : i < lens[j]} c_j p_j[i] - (i < k_low ? low[i] : 0) for i < *len_out = max(max_j lens[j], k_low).
+   d_polys: J device pointers, polynomial j has lens[j] coefficients (ragged, any length up to 2^28; lens[j] == 0 is allowed
+   and its pointer may be NULL); coeffs: J x 4 limbs c_j; low: k_low <= LEMSM_OPEN_MAX_ROOTS host coefficients (the r(X) of a
+   rotation set, the single evaluation of GWC), NULL means k_low = 0.  J == 0, J > LEMSM_OPEN_MAX_POLYS, a length above
+   2^28, cap_out < *len_out (in coefficients), or the output's *len_out coefficients overlapping an operand:
+   LEMSM_ERR_BAD_ARG.  lemsm_poly_last: bytes = 32 (sum_j lens[j] + *len_out), field_mults = sum_j lens[j]. */
+int lemsm_poly_lincomb_device(lemsm_ctx* ctx, const void* const* d_polys, const size_t* lens, size_t J, const uint64_t* coeffs,
+                              const uint64_t* low, size_t k_low, void* d_out, size_t cap_out, size_t* len_out);
+/* The same with host arrays (uploaded, the device path, downloaded). */
+int lemsm_poly_lincomb(lemsm_ctx* ctx, const uint64_t* const* polys, const size_t* lens, size_t J, const uint64_t* coeffs,
+                       const uint64_t* low, size_t k_low, uint64_t* out, size_t cap_out, size_t* len_out);
+/* a_0 = the len coefficients at d_in, a_(i+1) = kate_division(a_i, z_i) for the k roots z_i (k x 4 limbs, 1 <= k <=
+   LEMSM_OPEN_MAX_ROOTS; repeated roots and 0 are legal): a_k, len - k coefficients, goes to d_out in `form`
+   (LEMSM_FORM_MONTGOMERY, or LEMSM_FORM_CANONICAL: the scalars lemsm_msm_device takes).  out_rem (host, k x 4 limbs,
+   Montgomery, optional): out_rem[i] = a_i(z_i), the remainder stage i drops; all zero exactly when prod (X - z_i) divides a.
+   The intermediate quotients live in the call's workspace; only a_k touches d_out.  len == k gives an empty quotient.
+   len < k hands stage `len` an empty polynomial, the reference's len - 1 underflow: LEMSM_ERR_ARITH_OVERFLOW, the stage
+   in *bad_index (optional) and lemsm_last_bad_index, nothing written.  k == 0, k > LEMSM_OPEN_MAX_ROOTS, len > 2^28, an
+   unknown form, cap_out < len - k, or d_out overlapping d_in: LEMSM_ERR_BAD_ARG.  lemsm_poly_last: 96 B and 2 products per
+   coefficient of every a_i, i < k (as lemsm_kate_division_device prices a row), and 64 B and 1 product per coefficient of
+   a_k for the canonical form. */
+int lemsm_poly_divide_roots_device(lemsm_ctx* ctx, const void* d_in, size_t len, const uint64_t* roots, size_t k, int form,
+                                   void* d_out, size_t cap_out, uint64_t* out_rem, size_t* bad_index);
+/* The same with host arrays. */
+int lemsm_poly_divide_roots(lemsm_ctx* ctx, const uint64_t* in, size_t len, const uint64_t* roots, size_t k, int form,
+                            uint64_t* out, size_t cap_out, uint64_t* out_rem, size_t* bad_index);
+/* q = (sum_j c_j p_j - low) / prod_i (X - z_i) in one call: the combination of lemsm_poly_lincomb_device into the call's
+   workspace, then the stages of lemsm_poly_divide_roots_device into d_out; *len_out = max(max_j lens[j], k_low) - k.  The
+   statuses and figures of both (the capacity and the overlap are those of the quotient). */
+int lemsm_open_quotient_device(lemsm_ctx* ctx, const void* const* d_polys, const size_t* lens, size_t J, const uint64_t* coeffs,
+                               const uint64_t* low, size_t k_low, const uint64_t* roots, size_t k, int form,
+                               void* d_out, size_t cap_out, size_t* len_out, uint64_t* out_rem, size_t* bad_index);
+/* The same with host arrays. */
+int lemsm_open_quotient(lemsm_ctx* ctx, const uint64_t* const* polys, const size_t* lens, size_t J, const uint64_t* coeffs,
+                        const uint64_t* low, size_t k_low, const uint64_t* roots, size_t k, int form,
+                        uint64_t* out, size_t cap_out, size_t* len_out, uint64_t* out_rem, size_t* bad_index);
+/* Pure host: what lemsm_open_quotient_device does for these lengths (k == 0: the combination alone, as
+   lemsm_poly_lincomb_device).  len = max(max_j lens[j], k_low); *len_out = len - k; *bytes = 32 (sum_j lens[j] + len) +
+   sum_{i<k} 96 (len - i); *field_mults = sum_j lens[j] + sum_{i<k} 2 (len - i) (Montgomery form); *workspace_bytes = the
+   device workspace the call reserves (without guards).  Every output is optional.  len < k: LEMSM_ERR_ARITH_OVERFLOW. */
+int lemsm_open_plan(const size_t* lens, size_t J, size_t k_low, size_t k, size_t* len_out, uint64_t* bytes, uint64_t* field_mults,
+                    size_t* workspace_bytes);
+/* Pure host: the k coefficients (k x 4 limbs, lowest first) of the polynomial of degree < k through (points[i], evals[i]),
+   1 <= k <= LEMSM_OPEN_MAX_ROOTS: the r(X) of a rotation set.  Two equal points: LEMSM_ERR_DIVISION_BY_ZERO, the later
+   index in *bad_index (optional), out_coeffs untouched. */
+int lemsm_lagrange_interpolate(const uint64_t* points, const uint64_t* evals, size_t k, uint64_t* out_coeffs, size_t* bad_index);
 
 /* ---- halo2's EvaluationDomain on resident data: coset and extended-domain transforms ---------------------
    bn256::Fr, 32-byte raw Montgomery elements, the conventions of the entries above (LEMSM_ERR_BAD_ARG leaves nothing
