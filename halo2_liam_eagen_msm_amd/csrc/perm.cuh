@@ -119,11 +119,14 @@ __global__ __launch_bounds__(FP_SCAN_THREADS) void k_fp_segscan(uint4* __restric
 }
 
 // thread g = seg0 + ...: out[r] = segoff[g] prod_{g S <= i < r} term_i for the rows r of segment g.  out may be null (nothing
-// but the tap is wanted: the host launches the one segment that holds it); tap_out gets the value of row `tap`.
+// but the tap is wanted: the host launches the one segment that holds it); tap_out gets the value of row `tap`.  err: the
+// engine's error words; k_fs_prefix, launches ago, left in err[0] the lowest row with a zero denominator: the call fails then,
+// and the caller's column stays as it was.
 __global__ __launch_bounds__(256) void k_fp_finish(const uint4* __restrict__ terms, u64 N, u64 S, u64 seg0, u64 nseg, const uint4* __restrict__ segoff,
-                                                   uint4* __restrict__ out, u64 tap, uint4* __restrict__ tap_out) {
+                                                   uint4* __restrict__ out, u64 tap, uint4* __restrict__ tap_out, const rhs::ErrWord* __restrict__ err) {
   const u64 g = seg0 + (u64)blockIdx.x * 256 + threadIdx.x;
   if (g >= nseg) return;
+  if (err[0] != ~(rhs::ErrWord)0) out = nullptr;
   const u64 i0 = g * S, i1 = min(N, i0 + S);
   fe run; F::load(run, segoff + 2 * g);
   for (u64 i = i0; i < i1; i++) {

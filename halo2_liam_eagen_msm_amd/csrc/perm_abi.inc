@@ -41,7 +41,7 @@ FpCarve fp_carve(Arena& ar, const FsGeom& g) {
 
 // One pass of the engine over g.N >= 1 terms of `src` on an open workspace: the running products from `init` into d_out (may
 // be null), *tap_val = the value of row tap (tap == N: init times every term) when want_tap, *err_den = the lowest index with
-// a zero denominator (~0: none), *ms += the kernels' device time.  `extra` enqueues what the pass needs built first.
+// a zero denominator (~0: none; with one, d_out is not written), *ms += the kernels' device time.  `extra` enqueues what the pass needs built first.
 template <class Src, class Extra>
 int fp_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const Workspace& ws, const FpCarve& c, const host::fe& init, void* d_out, u64 tap,
            bool want_tap, host::fe* tap_val, u64* err_den, double* ms, Extra&& extra) {
@@ -66,10 +66,10 @@ int fp_run(lemsm_ctx* ctx, const Src& src, const FsGeom& g, const Workspace& ws,
     hipLaunchKernelGGL(pm::k_fp_segscan, dim3(1), dim3(pm::FP_SCAN_THREADS), 0, st, seg, g.nseg, (const uint4*)d_init, d_tot);
     if (d_out)
       hipLaunchKernelGGL(pm::k_fp_finish, dim3((u32)((g.nseg + 255) / 256)), dim3(256), 0, st, (const uint4*)bufN, g.N, g.S, (u64)0, g.nseg, (const uint4*)seg,
-                         (uint4*)d_out, tap_row ? tap : ~0ull, d_tap);
+                         (uint4*)d_out, tap_row ? tap : ~0ull, d_tap, (const fs::ErrWord*)d_err);
     else if (tap_row)   // the tap alone: the one segment that holds it
       hipLaunchKernelGGL(pm::k_fp_finish, dim3(1), dim3(256), 0, st, (const uint4*)bufN, g.N, g.S, tap / g.S, tap / g.S + 1, (const uint4*)seg,
-                         (uint4*)nullptr, tap, d_tap);
+                         (uint4*)nullptr, tap, d_tap, (const fs::ErrWord*)d_err);
   }, [&] {
     HIPCHK(ctx, hipMemcpyAsync(errw, d_err, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(&tot, d_tot, 32, hipMemcpyDeviceToHost, st));

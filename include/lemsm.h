@@ -81,6 +81,8 @@ enum lemsm_status {
    reentrant.  Distinct contexts may be used concurrently from different threads, including several contexts on one
    device; lemsm_create / lemsm_destroy may run beside calls on other contexts.  Device pointers are only read by the
    entries that take them as inputs, so several contexts may read the same resident scalars / points at once.
+   The contract is tested on the resident polynomial entries too (lemsm_fft* to lemsm_open_quotient*), their cached twiddle
+   table, regrown workspaces, lemsm_poly_last / lemsm_sort_last and the error indices included.
    (tests/test_gpu_concurrency.py, tests/hostpool_race_check.cpp) */
 int lemsm_create(int device, lemsm_ctx** out);
 void lemsm_destroy(lemsm_ctx* ctx);
@@ -836,7 +838,7 @@ int lemsm_fraction_products_geometry(size_t n, size_t* tile, size_t* segment, si
    out_tap (4 limbs, optional) = d_out[tap] for tap < n and init prod_{i < n} f_i for tap == n; tap > n: LEMSM_ERR_BAD_ARG.
    n == 0 is LEMSM_OK with out_tap = init.
    A row i < n whose denominators multiply to zero is LEMSM_ERR_DIVISION_BY_ZERO, whatever its numerator: the lowest such
-   i goes to *bad_index (optional) and lemsm_last_bad_index, and nothing but that index is defined.  halo2's batch_invert
+   i goes to *bad_index (optional) and lemsm_last_bad_index; d_out is not written and out_tap is not set.  halo2's batch_invert
    would leave the zero in place and z would die silently; here it is an error, as in lemsm_fraction_sums.  A zero
    numerator is legal: the products are 0 from there on.
    More than 8 columns on a side, a null column, init not canonical, or d_out overlapping the bytes of any input column:
@@ -866,8 +868,8 @@ int lemsm_permutation_plan(uint32_t logn, size_t ncols, size_t chunk_len, size_t
                            uint64_t* workspace_bytes);
 /* d_values, d_sigmas: ncols device pointers each; d_z: nsets device pointers of n elements each; out_taps (nsets x 4 limbs,
    optional) = z_s[u].  A row whose denominators multiply to zero: LEMSM_ERR_DIVISION_BY_ZERO with *bad_index (optional) and
-   lemsm_last_bad_index = s n + i of the first one (sets in order, the lowest row of the first failing set); nothing but the
-   index is defined then.  ncols == 0 is LEMSM_OK with nothing written.  chunk_len == 0, u >= n, a limit exceeded, a null
+   lemsm_last_bad_index = s n + i of the first one (sets in order, the lowest row of the first failing set); the z columns of
+   the sets before s are written, z_s and those behind it are not, and nothing but the index is defined then.  ncols == 0 is LEMSM_OK with nothing written.  chunk_len == 0, u >= n, a limit exceeded, a null
    pointer, beta / gamma / delta not canonical, or a d_z buffer overlapping any input column or another d_z:
    LEMSM_ERR_BAD_ARG.  The sets hang on each other through z_s[u]: a host loop with one 32-byte read-back per set.
    lemsm_poly_last reports the plan's figures and the summed device time of the sets. */

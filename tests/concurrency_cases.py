@@ -1,0 +1,352 @@
+"""The inputs and expected values of scenarios 8 to 13 of tests/concurrency_child.py (the threading contract on the resident
+polynomial entries), built without a context: every builder is a pure function of its arguments, every expected value comes
+from the big-integer references the entries' own tests use (oracle.divisor's best_fft and PolyRing, tests/domain_ref.py,
+gate_ref.py, perm_ref.py, lookup_ref.py, open_ref.py, rhs_ref.py).  tests/test_concurrency_cases.py holds the builders
+without a GPU; concurrency_child.py turns a Spec into a library call on a context.  Not a test module.
+
+A Spec is one library call:
+    ins     name -> (n, 4) uint64 array: a resident input (raw limbs); the call may only read it
+    outs    [(name, capacity in elements, the bytes the call must leave at the buffer's start, the (n, 4) array the buffer
+            holds before the call or None)]: every byte behind the expected ones stays 0xFF, so a call that must leave its
+            output untouched expects b"" (or, in place, the bytes it was given)
+    small   the arrays the call returns to the host (a tap, totals, remainders, a length)
+    status  the status the call must return, index the index it must report with it (None: the entry reports none)
+    args    everything else the entry takes"""
+import hashlib
+
+import numpy as np
+
+from halo2_liam_eagen_msm_amd import _lib, api
+from oracle.divisor import best_fft
+
+import domain_ref
+import fuzz_resident as fr
+import gate_ref
+import lookup_ref
+import open_ref
+import perm_ref
+import rhs_ref
+
+P, R, RI = fr.P, fr.R, fr.RI
+SEED = 20261020
+GROUP = 5                           # terms of k_open_lincomb that share one reduction (open.cuh: OPEN_G_MAX)
+OK, BAD_ARG, OVERFLOW = _lib.LEMSM_OK, _lib.LEMSM_ERR_BAD_ARG, _lib.LEMSM_ERR_ARITH_OVERFLOW
+DIV_ZERO, NOT_IN_TABLE = _lib.LEMSM_ERR_DIVISION_BY_ZERO, _lib.LEMSM_ERR_NOT_IN_TABLE
+_ints, _arr, _mont, _fe, _rand = fr._ints, fr._arr, fr._mont, fr._fe, fr._rand
+
+
+class Spec:
+    def __init__(self, op, note, ins, outs, small=(), status=OK, index=None, **args):
+        self.op, self.note, self.ins, self.outs, self.small = op, note, ins, list(outs), [np.ascontiguousarray(a) for a in small]
+        self.status, self.index, self.args = status, index, args
+
+    @property
+    def error(self):
+        return self.status != OK
+
+    def fingerprint(self):
+        return hashlib.sha256(fr._blob(self.__dict__)).hexdigest()
+
+    def __repr__(self):
+        return "%s %s%s" % (self.op, self.note, " ERROR" if self.error else "")
+
+
+def _rng(*key):
+    return np.random.default_rng([SEED] + [int(k) for k in key])
+
+
+def _std(arr):
+    return [v * RI % P for v in _ints(arr)]
+
+
+# ---- transforms ------------------------------------------------------------------------------------------------------------------
+def fft(seed, logn, inverse=False, scale=False, nseq=1, bad_omega=False):
+    """fft_device in place; bad_omega: the generator of the 2^(logn - 1)-th roots, which best_fft's contract (a primitive
+    2^logn-th root) excludes: refused, the data untouched"""
+    rng = _rng(seed, 1)
+    n = 1 << logn
+    data = _rand(rng, nseq * n)
+    sc = fr._fe_int(rng) if scale else None
+    note = "logn=%d nseq=%d inverse=%s scale=%s" % (logn, nseq, inverse, scale)
+    if bad_omega:
+        w = domain_ref.omega(logn - 1)
+        assert pow(w, n // 2, P) == 1                                  # no primitive 2^logn-th root: w^(n / 2) is 1, not -1
+        return Spec("fft", note + " omega of order 2^%d" % (logn - 1), {}, [("data", nseq * n, data.tobytes(), data)], status=BAD_ARG,
+                    logn=logn, nseq=nseq, omega=_fe(w), scale=None)
+    w = domain_ref.omega(logn)
+    if inverse:
+        w = pow(w, -1, P)
+    assert pow(w, n // 2, P) == P - 1
+    raw, want = _ints(data), []
+    for s in range(nseq):
+        seq = raw[s * n:(s + 1) * n]
+        best_fft(seq, w, logn, P)
+        want += seq if sc is None else [v * sc % P for v in seq]
+    return Spec("fft", note, {}, [("data", nseq * n, _arr(want).tobytes(), data)], logn=logn, nseq=nseq, omega=_fe(w),
+                scale=None if sc is None else _fe(sc))
+
+
+def coset(seed, logn):
+    rng = _rng(seed, 2)
+    n = 1 << logn
+    g = 2 + fr._fe_int(rng) % (P - 2)
+    data = _rand(rng, n)
+    want = domain_ref.coset_fft(_ints(data), logn, g, 1)
+    return Spec("coset", "logn=%d" % logn, {}, [("data", n, _arr(want).tobytes(), data)], logn=logn, nseq=1,
+                omega=_fe(domain_ref.omega(logn)), shift=_fe(g), scale=None)
+
+
+def extended_pair(seed, logn, logm):
+    """coeff_to_extended_device of N - 5 coefficients, and extended_to_coeff_device of those values: the coefficients again"""
+    rng = _rng(seed, 3)
+    N = 1 << (logn + logm)
+    g = domain_ref.order3()
+    coeffs = _rand(rng, N - 5)
+    vals = domain_ref.coeff_to_extended_halo2(_ints(coeffs), logn, logm, g)
+    back = domain_ref.extended_to_coeff_halo2(vals, logn, logm, g, False)
+    assert back == _ints(coeffs) + [0] * 5
+    note = "logn=%d logm=%d" % (logn, logm)
+    evals = _arr(vals)
+    return [Spec("c2e", note + " n_coeffs=%d" % (N - 5), {"coeffs": coeffs}, [("out", N, evals.tobytes(), None)], logn=logn, logm=logm, shift=_fe(g)),
+            Spec("e2c", note + " n_out=%d" % N, {"evals": evals}, [("out", N, _arr(back).tobytes(), None)], logn=logn, logm=logm, shift=_fe(g), n_out=N)]
+
+
+def kate(seed, lengths):
+    """kate_division_device of rows of these lengths (gaps between them) by one random b"""
+    rng = _rng(seed, 4)
+    rows, used = [], 3
+    for length in lengths:
+        rows.append((used, length)); used += length + 2
+    b = fr._fe_int(rng)
+    coeffs = _rand(rng, used)
+    image = np.full(used * 32, 0xFF, np.uint8)
+    for o, n in rows:
+        image[o * 32:(o + n - 1) * 32] = np.frombuffer(_arr(fr.RING.kate_div(_ints(coeffs[o:o + n]), b)).tobytes(), np.uint8)
+    return Spec("kate", "rows=%s" % rows, {"coeffs": coeffs}, [("out", used, image.tobytes(), None)],
+                rows=np.array(rows, np.uintp).reshape(-1, 2), b=_fe(b), cap=used)
+
+
+def mul(seed, la, lb):
+    rng = _rng(seed, 5)
+    a, b = _rand(rng, la), _rand(rng, lb)
+    want = fr.RING.mul(_ints(a), _ints(b))
+    assert len(want) == la + lb - 1
+    return Spec("mul", "la=%d lb=%d" % (la, lb), {"a": a, "b": b}, [("out", la + lb - 1, _arr([v * RI % P for v in want]).tobytes(), None)],
+                small=[np.array([la + lb - 1], np.uint64)], la=la, lb=lb)
+
+
+# ---- gate ------------------------------------------------------------------------------------------------------------------------
+def gate(seed, logn=9, logm=2):
+    """a program with X(), rotations and constants over 3 columns, every coset of the extended domain"""
+    rng = _rng(seed, 6)
+    n, m = 1 << logn, 1 << logm
+    C, K, X = api.Cell, api.Const, api.X
+    k1, k2 = fr._fe_int(rng), fr._fe_int(rng)
+    exprs = [X() * C(0, 1) - C(1) * K(k1), (C(2, -1) + K(k2)) * (C(0) - C(1, 2)) + X(), C(2) * C(2) - K(7)]
+    prog = api.compile_gates(exprs)                                    # (pure host)
+    raw = [_rand(rng, n * m) for _ in range(3)]
+    cols = [_std(a) for a in raw]
+    y, g = fr._fe_int(rng), domain_ref.order3()
+    cosets = list(range(m))
+    want = gate_ref.run_trees(exprs, cols, logn, cosets, y, gate_ref.points(logn, logm, g, cosets))
+    return Spec("gate", "logn=%d logm=%d code=%d" % (logn, logm, prog.code.size), {"col%d" % k: a for k, a in enumerate(raw)},
+                [("out", n * m, _mont(want).tobytes(), None)], logn=logn, logm=logm, code=prog.code.copy(), queries=prog.queries.copy(),
+                consts=prog.consts.copy(), y=_fe(y), shift=_fe(g), ncols=3)
+
+
+# ---- scans -----------------------------------------------------------------------------------------------------------------------
+def fraction_products(seed, n, n_num=2, n_den=2, zero_at=None):
+    """zero_at: (column, row) pairs of the denominators set to zero"""
+    rng = _rng(seed, 7)
+    nums, dens = [_rand(rng, n) for _ in range(n_num)], [_rand(rng, n) for _ in range(n_den)]
+    for col, row in zero_at or ():
+        dens[col][row] = 0
+    init, tap = fr._fe_int(rng), n - 1
+    ins = dict([("num%d" % k, a) for k, a in enumerate(nums)] + [("den%d" % k, a) for k, a in enumerate(dens)])
+    note = "n=%d nums=%d dens=%d tap=%d" % (n, n_num, n_den, tap)
+    kw = dict(n=n, n_num=n_num, n_den=n_den, init=_fe(init), tap=tap)
+    try:
+        out, tapped = perm_ref.fraction_products([_std(c) for c in nums], [_std(c) for c in dens], n, init, tap)
+    except perm_ref.ZeroDenominator as e:
+        return Spec("fp", note + " zero denominators at %s" % (zero_at,), ins, [("out", n, b"", None)], status=DIV_ZERO, index=e.index, **kw)
+    return Spec("fp", note, ins, [("out", n, _mont(out).tobytes(), None)], small=[_fe(tapped)], **kw)
+
+
+def permutation_product(seed, logn, ncols, chunk):
+    rng = _rng(seed, 8)
+    n = 1 << logn
+    beta, gamma = 1 + fr._fe_int(rng) % (P - 1), 1 + fr._fe_int(rng) % (P - 1)
+    values, sigmas = [_rand(rng, n) for _ in range(ncols)], [_rand(rng, n) for _ in range(ncols)]
+    u = n - 3
+    zs, taps = perm_ref.permutation_products([_std(c) for c in values], [_std(c) for c in sigmas], logn, beta, gamma, perm_ref.DELTA, chunk, u)
+    ins = dict([("v%d" % k, a) for k, a in enumerate(values)] + [("s%d" % k, a) for k, a in enumerate(sigmas)])
+    return Spec("pp", "logn=%d ncols=%d chunk=%d u=%d" % (logn, ncols, chunk, u), ins, [("z%d" % s, n, _mont(z).tobytes(), None) for s, z in enumerate(zs)],
+                small=[_mont(taps)], logn=logn, ncols=ncols, chunk=chunk, u=u, beta=_fe(beta), gamma=_fe(gamma), delta=_fe(perm_ref.DELTA))
+
+
+def fraction_sums(seed, n, chains=1):
+    rng = _rng(seed, 9)
+    num, den = _rand(rng, n), _rand(rng, n)
+    for i in range(0, n, 97):
+        num[i] = 0                                                     # a zero numerator gives 0
+    run, tot = rhs_ref.fraction_sums(_std(num), _std(den), chains, P, None)
+    return Spec("fsums", "n=%d chains=%d" % (n, chains), {"num": num, "den": den}, [("out", n, _mont(run).tobytes(), None)], small=[_mont(tot)],
+                n=n, chains=chains)
+
+
+# ---- sorts -----------------------------------------------------------------------------------------------------------------------
+def sort(seed, n, shared_upper=False):
+    """shared_upper: the standard-form integers differ in their lowest 8 bytes only, so 24 of the 32 passes are skipped"""
+    rng = _rng(seed, 10)
+    vals = _ints(_rand(rng, n))
+    if shared_upper:
+        top = vals[0] >> 64 << 64
+        vals = [top | (v & ((1 << 64) - 1)) for v in vals]
+    assert all(v < P for v in vals)
+    passes = len(lookup_ref.live_passes(vals))
+    return Spec("sort", "n=%d passes=%d" % (n, passes), {"keys": _mont(vals)}, [("out", n, _mont(lookup_ref.sort_field(vals)).tobytes(), None)],
+                small=[np.array([passes, lookup_ref.MAX_PASSES - passes], np.uint32)], n=n, passes=passes)
+
+
+def lookup_permute(seed, n, missing_rows=None):
+    """a table of 150 values repeated, an input that takes half of them; missing_rows: rows of the input given a value the
+    table lacks (the higher row the smaller one)"""
+    rng = _rng(seed, 11)
+    alphabet = [fr._fe_int(rng) for _ in range(150)]
+    S = [alphabet[int(i)] for i in rng.integers(0, len(alphabet), n)]
+    used = S[:n // 2]
+    A = [used[int(i)] for i in rng.integers(0, len(used), n)]
+    if missing_rows:
+        table = set(S)
+        gone = sorted(v for v in (fr._fe_int(rng) for _ in range(len(missing_rows))) if v not in table)
+        for row, v in zip(sorted(missing_rows, reverse=True), gone):
+            A[row] = v
+    ins = {"A": _mont(A), "S": _mont(S)}
+    try:
+        Ap, Sp = lookup_ref.permute_expression_pair(A, S)
+    except lookup_ref.NotInTable as e:
+        return Spec("pair", "n=%d missing at %s" % (n, missing_rows), ins, [("A'", n, b"", None), ("S'", n, b"", None)], status=NOT_IN_TABLE, index=e.index, n=n)
+    passes = len(lookup_ref.live_passes(A)) + len(lookup_ref.live_passes(S))
+    return Spec("pair", "n=%d" % n, ins, [("A'", n, _mont(Ap).tobytes(), None), ("S'", n, _mont(Sp).tobytes(), None)],
+                small=[np.array([passes, 2 * lookup_ref.MAX_PASSES - passes], np.uint32)], n=n, passes=passes)
+
+
+# ---- openings --------------------------------------------------------------------------------------------------------------------
+def _open_terms(rng, lens, k_low):
+    polys = [_rand(rng, n) for n in lens]
+    coeffs = [fr._fe_int(rng) for _ in lens]
+    low = _rand(rng, k_low)
+    ins = {"p%d" % j: a for j, a in enumerate(polys) if a.shape[0]}
+    return polys, coeffs, low, ins
+
+
+def lincomb(seed, lens, k_low, short_by=0):
+    """short_by = 1: a capacity one element below the combination's length, refused with the output untouched"""
+    rng = _rng(seed, 12)
+    polys, coeffs, low, ins = _open_terms(rng, lens, k_low)
+    want = open_ref.lincomb([_ints(a) for a in polys], coeffs, _ints(low), P)
+    kw = dict(lens=list(lens), coeffs=_mont(coeffs), low=low if k_low else None)
+    note = "lens=%s k_low=%d" % (list(lens), k_low)
+    if short_by:
+        return Spec("lincomb", note + " capacity %d" % (len(want) - short_by), ins, [("out", len(want) - short_by, b"", None)], status=BAD_ARG, **kw)
+    return Spec("lincomb", note, ins, [("out", len(want), _arr(want).tobytes(), None)], small=[np.array([len(want)], np.uint64)], **kw)
+
+
+def divide_by_roots(seed, length, k):
+    rng = _rng(seed, 13)
+    a = _rand(rng, length)
+    roots = [fr._fe_int(rng) for _ in range(k)]
+    kw = dict(length=length, roots=_mont(roots))
+    note = "length=%d k=%d" % (length, k)
+    try:
+        q, rems = open_ref.divide_roots(_ints(a), roots, P)
+    except OverflowError as e:
+        return Spec("divide", note, {"a": a}, [("out", max(length, 1), b"", None)], status=OVERFLOW, index=e.args[0], **kw)
+    return Spec("divide", note, {"a": a}, [("out", length - k, _arr(q).tobytes(), None)], small=[_arr(rems)], **kw)
+
+
+def open_quotient(seed, lens, k_low, k):
+    rng = _rng(seed, 14)
+    polys, coeffs, low, ins = _open_terms(rng, lens, k_low)
+    roots = [fr._fe_int(rng) for _ in range(k)]
+    q, rems = open_ref.open_quotient([_ints(a) for a in polys], coeffs, _ints(low), roots, P)
+    return Spec("quotient", "lens=%s k_low=%d k=%d" % (list(lens), k_low, k), ins, [("out", len(q), _arr(q).tobytes(), None)],
+                small=[np.array([len(q)], np.uint64), _arr(rems)], lens=list(lens), coeffs=_mont(coeffs), low=low if k_low else None, roots=_mont(roots))
+
+
+def term_groups(lens, group=GROUP):
+    """the non-empty terms' lengths in the kernel's order (longest first), cut into the groups that share one reduction"""
+    order = sorted((n for n in lens if n), reverse=True)
+    return [order[i:i + group] for i in range(0, len(order), group)]
+
+
+def straddles(lens, group=GROUP):
+    """a run of equal lengths reaches from one group of terms into the next, and the first group holds terms of different
+    lengths: inside one reduction some terms have ended and others have not"""
+    groups = term_groups(lens, group)
+    return len(groups) >= 2 and any(a[-1] == b[0] for a, b in zip(groups, groups[1:])) and len(set(groups[0])) >= 2
+
+
+# ---- the scenarios ---------------------------------------------------------------------------------------------------------------
+OPEN_LENS = [300, 16385, 4097, 300, 9000, 17, 300]                     # ragged; sorted: 16385 9000 4097 300 300 | 300 17
+
+
+def transform_users(seed):
+    """scenario 8, thread A (and scenario 13's long-lived thread): (omega, logn) changes from call to call"""
+    c2e, e2c = extended_pair(seed + 3, 10, 2)
+    return [fft(seed, 12), fft(seed + 1, 11, inverse=True, scale=True), coset(seed + 2, 10), c2e, e2c,
+            kate(seed + 4, [16385]), mul(seed + 5, 300, 257), mul(seed + 6, 31, 40)]
+
+
+def scans_and_sorts(seed):
+    """scenario 8, thread B"""
+    return [fraction_products(seed, 8193), permutation_product(seed + 1, 10, 3, 2), sort(seed + 2, 5000), lookup_permute(seed + 3, 4096),
+            fraction_sums(seed + 4, 4097), open_quotient(seed + 5, OPEN_LENS, 3, 3)]
+
+
+def scenario8():
+    return {"A": transform_users(800), "B": scans_and_sorts(850)}
+
+
+def scenario9():
+    """the same transforms, the same combination; A first alternates two sizes and then repeats one, B the other way round; A
+    sorts keys that share their upper limbs, B random ones"""
+    t11, t12 = fft(900, 11), fft(901, 12, inverse=True, scale=True)
+    lc = lincomb(902, [700, 2049, 0, 700, 33, 2049, 5], 2)
+    alternate, repeat = [t11, t12, t11, t12], [t12, t12, t12, t12]
+    return {"A": alternate + [lc, sort(903, 3000, shared_upper=True)] + repeat, "B": repeat + [lc, sort(904, 3000)] + alternate,
+            "options": {"A": {"open_group": 1}, "B": {}}}
+
+
+def scenario10(k):
+    """context k's list, before its cyclic shift (the msm_device call is made by the child: its oracle is the C one)"""
+    s = 1000 + 20 * k
+    return [fft(s, 10), extended_pair(s + 1, 9, 1)[0], gate(s + 2, 9, 2), fraction_products(s + 3, 3000, 1, 1), lookup_permute(s + 4, 1500),
+            open_quotient(s + 5, [600, 2100, 600, 0, 50, 600, 600], 2, 2), kate(s + 6, [3000, 65])]
+
+
+def scenario11():
+    return [gate(1100, 9, 2), lincomb(1101, OPEN_LENS, 3), open_quotient(1102, [2000, 4100, 2000, 2000, 9, 2000], 1, 2), lookup_permute(1103, 2048),
+            fraction_products(1104, 4097), kate(1105, [5000, 1, 130])]
+
+
+def scenario12():
+    """A: good calls and refusals in turn; B: good calls only"""
+    n_pair, n_fp = 2500, 5000
+    a = [fft(1200, 10),
+         lookup_permute(1201, n_pair, missing_rows=[2222, 40]),                      # the smaller value in the higher row
+         lookup_permute(1201, n_pair),
+         fraction_products(1202, n_fp, zero_at=[(1, 4711), (0, 1234), (1, 1234)]),
+         fraction_products(1202, n_fp),
+         divide_by_roots(1203, 2, 4),
+         divide_by_roots(1204, 700, 4),
+         fft(1205, 11, bad_omega=True),
+         fft(1205, 11),                                                              # (the table held is logn 10's: built anew)
+         lincomb(1206, [100, 1025, 64], 1, short_by=1),
+         lincomb(1206, [100, 1025, 64], 1)]
+    b = [fft(1250, 11, inverse=True, scale=True), lookup_permute(1251, 2000), fraction_products(1252, 3000), open_quotient(1253, [1500, 40, 1500], 2, 3)]
+    return {"A": a, "B": b}
+
+
+def scenario13():
+    return {"L": [fft(1300, 10), open_quotient(1301, [1000, 2500, 1000], 2, 2)], "A": transform_users(1350)}

@@ -1,7 +1,8 @@
 """Child process of tests/test_gpu_concurrency.py: one scenario of the per-context threading contract (include/lemsm.h,
 "Threading") on device 0.  Usage: python concurrency_child.py ROOT SCENARIO.  Not a test module.
 
-Every expected value comes from the oracle (oracle/cref.py, tests/rhs_ref.py, tests/column_ref.py, oracle/divisor.py) and is
+Every expected value comes from the oracle (oracle/cref.py, tests/rhs_ref.py, tests/column_ref.py, oracle/divisor.py; for
+scenarios 8-13, the resident polynomial entries, from the big-integer references tests/concurrency_cases.py builds on) and is
 computed single-threaded before any thread starts.  The threads are threading.Thread; ctypes releases the GIL for the
 duration of a CDLL call, so the library calls of different threads do overlap; all threads leave one threading.Barrier
 before their first call and every call's (start, end) on time.perf_counter() is kept.  Every context has ws_canary = 1.
@@ -10,10 +11,13 @@ Scenarios 1-4 first make every thread's call list serially, on the same contexts
 first serial output of every call is checked against the oracle, every later output -- serial or concurrent -- must equal it
 limb for limb (raw Jacobian limbs, raw coefficient arrays).  The Jacobian outputs of an entry named in CANON_ONLY are compared
 in canonical form instead: two serial runs of it already differ in raw limbs (profiles/concurrency/NOTES.md says why); its
-other outputs stay limb-exact.  The last line printed is "RESULT <json>": rounds, calls, the share of
-calls that overlapped a call of another thread, and the wall time of the concurrent phase and of the serial one.
+other outputs stay limb-exact.  Scenarios 8-11 run the same way; every output of the resident entries is limb-exact, and a
+call's raw outputs there include the guard zone behind each output buffer, its status and its reported index.  The last line
+printed is "RESULT <json>": rounds, calls, the share of calls that overlapped a call of another thread, the wall time of the
+concurrent phase and of the serial one, and how long each thread ran in the concurrent phase.
 
 Exit status 0 and the RESULT line: the scenario held.  Anything else: the first failure's message on stderr."""
+import ctypes
 import json
 import os
 import sys
@@ -29,6 +33,7 @@ from halo2_liam_eagen_msm_amd import Context, _lib, api       # noqa: E402
 from oracle import cref, pyref                                 # noqa: E402
 from oracle import divisor as dv                               # noqa: E402
 import column_ref                                              # noqa: E402
+import concurrency_cases as cases                              # noqa: E402
 import rhs_ref                                                 # noqa: E402
 
 BN, GR = pyref.BN254_G1, pyref.GRUMPKIN
@@ -279,6 +284,7 @@ def finish(scenario, lanes, wall, serial_wall=None, need_overlap=True):
     print("RESULT " + json.dumps({"scenario": scenario, "threads": len(lanes), "rounds": [ln.rounds for ln in lanes],
                                   "calls": [len(ln.times) for ln in lanes], "overlapped": per,
                                   "overlap_share": round(hit / max(total, 1), 3), "concurrent_s": round(wall, 3),
+                                  "lane_s": [round(ln.times[-1][1] - ln.times[0][0], 3) if ln.times else 0.0 for ln in lanes],
                                   "serial_s": None if serial_wall is None else round(serial_wall, 3),
                                   "canonical_only": sorted(CANON_ONLY)}))
 
@@ -556,9 +562,294 @@ def scenario7():
     finish(7, lanes + [closer], time.perf_counter() - t0, need_overlap=False)
 
 
+# ---- scenarios 8-13: the resident polynomial entries ---------------------------------------------------------------------------------
+# A Spec of tests/concurrency_cases.py (inputs and expected values, built there without a context) becomes a Call here.  Every
+# input and every output stands in a 0xFF-filled device buffer with a zone of ZONE bytes behind it; an output buffer is filled
+# anew before every call, so a call that must leave it untouched is seen to, and so is a write behind an output.  The raw
+# outputs of a call are the whole output buffers (zones included), what the entry hands back on the host, and (status, index).
+ZONE = 4096
+NO_INDEX = -1
+
+
+def filled(ctx, n_elems, payload, keep):
+    """(a device buffer of n_elems elements + the zone, 0xFF, with `payload` at its start; the bytes it was given)"""
+    raw = np.full(n_elems * 32 + ZONE, 0xFF, np.uint8)
+    if payload is not None:
+        pb = np.ascontiguousarray(payload).view(np.uint8).reshape(-1)
+        raw[:pb.size] = pb
+    b = ctx.alloc(raw.size).upload(raw); keep.append(b)
+    return b, raw
+
+
+def upload_inputs(ctx, sp, keep):
+    """name -> (buffer, the bytes it holds) of a Spec's resident inputs"""
+    return {k: filled(ctx, a.shape[0], a, keep) for k, a in sp.ins.items()}
+
+
+def _open_args(sp, ins):
+    J = len(sp.args["lens"])
+    ptrs = (ctypes.c_void_p * J)(*[ins["p%d" % j][0].ptr if n else None for j, n in enumerate(sp.args["lens"])])
+    ln = np.array(sp.args["lens"], np.uintp)
+    low = sp.args["low"]
+    return ptrs, ln, J, sp.args["coeffs"], (low.ctypes.data if low is not None else None), (0 if low is None else low.shape[0])
+
+
+def launcher(ctx, sp, ins, o):
+    """the thunk that makes the Spec's one library call on ctx (ins: its resident inputs, o: its output buffers) and returns
+    what the entry hands back on the host"""
+    a, p = sp.args, {k: b.ptr for k, (b, _) in ins.items()}
+    lib, MONT = ctx.lib, _lib.LEMSM_FORM_MONTGOMERY
+    if sp.op == "fft":
+        return lambda: ctx.fft_device(o[0].ptr, a["nseq"], a["logn"], a["omega"], a["scale"]) or []
+    if sp.op == "coset":
+        return lambda: ctx.coset_fft_device(o[0].ptr, a["nseq"], a["logn"], a["omega"], a["shift"], a["scale"]) or []
+    if sp.op == "c2e":
+        N = 1 << (a["logn"] + a["logm"])
+        return lambda: ctx.coeff_to_extended_device(p["coeffs"], sp.ins["coeffs"].shape[0], a["logn"], a["logm"], a["shift"], o[0].ptr, N) or []
+    if sp.op == "e2c":
+        return lambda: ctx.extended_to_coeff_device(p["evals"], a["logn"], a["logm"], a["shift"], o[0].ptr, a["n_out"]) or []
+    if sp.op == "kate":
+        return lambda: ctx.kate_division_device(p["coeffs"], a["cap"], a["rows"], a["b"], o[0].ptr, a["cap"]) or []
+    if sp.op == "mul":
+        return lambda: [np.array([ctx.poly_mul_device(p["a"], a["la"], p["b"], a["lb"], o[0].ptr, a["la"] + a["lb"] - 1)], np.uint64)]
+    if sp.op == "gate":
+        prog = api.GateProgram(a["code"], a["queries"], a["consts"])
+        cols, N = [p["col%d" % k] for k in range(a["ncols"])], 1 << (a["logn"] + a["logm"])
+        return lambda: ctx.gate_eval_device(prog, cols, a["logn"], a["logm"], o[0].ptr, N, a["y"], a["shift"]) or []
+    if sp.op == "fp":
+        nums, dens = [p["num%d" % k] for k in range(a["n_num"])], [p["den%d" % k] for k in range(a["n_den"])]
+        return lambda: [ctx.fraction_products_device(nums, dens, a["n"], a["init"], out=o[0], want_out=True, tap=a["tap"])[1]]
+    if sp.op == "pp":
+        vals, sigs = [p["v%d" % k] for k in range(a["ncols"])], [p["s%d" % k] for k in range(a["ncols"])]
+        return lambda: [ctx.permutation_product_device(vals, sigs, a["logn"], a["beta"], a["gamma"], a["delta"], a["chunk"], a["u"], d_z=[z.ptr for z in o])[1]]
+    if sp.op == "fsums":
+        return lambda: [ctx.fraction_sums_device(1, p["num"], p["den"], a["n"], a["chains"], None, out=o[0])[1]]
+    if sp.op == "sort":
+        def run_sort():
+            ctx.sort_field_device(p["keys"], a["n"], o[0])
+            return [np.array(ctx.sort_last(), np.uint32)]
+        return run_sort
+    if sp.op == "pair":
+        def run_pair():
+            ctx.lookup_permute_device(p["A"], p["S"], a["n"], o[0], o[1])
+            return [np.array(ctx.sort_last(), np.uint32)]
+        return run_pair
+    cap = sp.outs[0][1]                                                # the C entries themselves: the capacity is the Spec's, exactly
+    if sp.op == "lincomb":
+        ptrs, ln, J, cf, lwp, k_low = _open_args(sp, ins)
+
+        def run_lincomb():
+            n = ctypes.c_size_t(0)
+            ctx._check(lib.lemsm_poly_lincomb_device(ctx.h, ptrs, ln.ctypes.data, J, cf.ctypes.data, lwp, k_low, o[0].ptr, cap, ctypes.byref(n)))
+            return [np.array([n.value], np.uint64)]
+        return run_lincomb
+    rt = sp.args["roots"]
+    k = rt.shape[0]
+    if sp.op == "divide":
+        def run_divide():
+            rem, bad = np.zeros((k, 4), np.uint64), ctypes.c_size_t(0)
+            ctx._check(lib.lemsm_poly_divide_roots_device(ctx.h, p["a"], a["length"], rt.ctypes.data, k, MONT, o[0].ptr, cap, rem.ctypes.data, ctypes.byref(bad)),
+                       bad.value)
+            return [rem]
+        return run_divide
+    assert sp.op == "quotient", sp.op
+    ptrs, ln, J, cf, lwp, k_low = _open_args(sp, ins)
+
+    def run_quotient():
+        rem, n, bad = np.zeros((k, 4), np.uint64), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        ctx._check(lib.lemsm_open_quotient_device(ctx.h, ptrs, ln.ctypes.data, J, cf.ctypes.data, lwp, k_low, rt.ctypes.data, k, MONT, o[0].ptr, cap,
+                                                  ctypes.byref(n), rem.ctypes.data, ctypes.byref(bad)), bad.value)
+        return [np.array([n.value], np.uint64), rem]
+    return run_quotient
+
+
+def check_spec(sp, raw, who=""):
+    """the raw outputs of one call against the Spec: limb for limb, the zones, the status and the index"""
+    what = "%s%s (%s):" % (who, sp.op, sp.note)
+    st, idx = (int(v) for v in raw[-1])
+    need(st == sp.status, what, "status %d, the reference says %d" % (st, sp.status))
+    need(idx == (NO_INDEX if sp.index is None else sp.index), what, "index %d reported, the reference's is %s" % (idx, sp.index))
+    for (name, cap, want, _), img in zip(sp.outs, raw):
+        need(img.size == cap * 32 + ZONE, what, "size of", name)
+        if img[:len(want)].tobytes() != want:
+            g, w = img[:len(want)].reshape(-1, 32), np.frombuffer(want, np.uint8).reshape(-1, 32)
+            need(False, what, "element %d of %s differs from the reference" % (int(np.argmax((g != w).any(axis=1))), name))
+        rest = img[len(want):]
+        need((rest == 0xFF).all(), what, "%s written at byte %d, behind what the call may write" % (name, len(want) + int(np.argmax(rest != 0xFF))))
+    small = raw[len(sp.outs):-1]
+    need(len(small) == len(sp.small), what, "%d host outputs, expected %d" % (len(small), len(sp.small)))
+    for k, (g, w) in enumerate(zip(small, sp.small)):
+        need(np.ascontiguousarray(g).tobytes() == w.tobytes(), what, "host output %d differs from the reference" % k)
+
+
+def resident_call(ctx, sp, ins=None, keep=None, who=""):
+    """the Call of a Spec on ctx; ins: resident inputs uploaded already (shared ones), else they are uploaded through ctx"""
+    keep = KEEP if keep is None else keep
+    ins = upload_inputs(ctx, sp, keep) if ins is None else ins
+    outs = [filled(ctx, cap, init, keep) for _, cap, _, init in sp.outs]
+    launch = launcher(ctx, sp, ins, [b for b, _ in outs])
+
+    def fn():
+        for b, image in outs:
+            b.upload(image)
+        st, idx, small = _lib.LEMSM_OK, NO_INDEX, []
+        try:
+            small = launch()
+        except api.LemsmError as e:
+            st, idx = e.status, getattr(e, "index", None)
+            idx = NO_INDEX if idx is None else idx
+        return [b.download(np.uint8) for b, _ in outs] + [np.ascontiguousarray(s) for s in small] + [np.array([st, idx], np.int64)]
+    return Call("%s %s" % (sp.op, sp.note), sp.op, fn, lambda raw: check_spec(sp, raw, who))
+
+
+def resident_calls(ctx, specs, who=""):
+    return [resident_call(ctx, sp, who=who) for sp in specs]
+
+
+def scenario8():
+    case = cases.scenario8()
+    a, b = new_ctx(), new_ctx()
+    serial_then_concurrent(8, [Lane("A: transforms, quotient, product", resident_calls(a, case["A"]), ROUNDS[8][0]),
+                               Lane("B: scans, sorts, opening", resident_calls(b, case["B"]), ROUNDS[8][1])])
+    a.close(); b.close()
+
+
+def figures_of(ctx):
+    """(bytes, field_mults) of lemsm_poly_last and lemsm_sort_last"""
+    return ctx.poly_last()[1:] + ctx.sort_last()
+
+
+def scenario9():
+    case = cases.scenario9()
+    lanes, alone, lists = [], {}, {}
+    for name in ("A", "B"):
+        c = new_ctx()
+        for opt, v in case["options"][name].items():
+            c.set_option(opt, v)
+        calls = resident_calls(c, case[name], who="context %s: " % name)
+        alone[name] = []
+        for rnd in range(2):                                           # what each call leaves when made alone; the second round is the loop's steady state
+            alone[name] = []
+            for call in calls:
+                call.fn()
+                alone[name].append(figures_of(c))
+        for k, call in enumerate(calls):
+            def after(raw, r, c=c, k=k, name=name, call=call):
+                got = figures_of(c)
+                need(got == alone[name][k], "context %s, %s: poly_last / sort_last %s are not this context's own %s" % (name, call.name, got, alone[name][k]))
+            call.after = after
+        lists[name] = calls
+        lanes.append(Lane("context %s %s" % (name, case["options"][name]), calls, ROUNDS[9][len(lanes)]))
+    differ = [k for k, (x, y) in enumerate(zip(alone["A"], alone["B"])) if x != y]
+    sorts = [k for k, sp in enumerate(case["A"]) if sp.op == "sort"]
+    need(len(differ) >= 4 and set(sorts) <= set(differ) and all(alone["A"][k][2:] != alone["B"][k][2:] for k in sorts),
+         "the two contexts leave the same figures: the check could not tell them apart", alone)
+    serial_then_concurrent(9, lanes)
+    for k, sp in enumerate(case["A"]):                                 # open_group = 1 and the default: the same bytes
+        if sp.op == "lincomb":
+            need(case["B"][k] is sp and np.array_equal(lists["A"][k].ref[0], lists["B"][k].ref[0]), "poly_lincomb: open_group = 1 and the default give different bytes")
+
+
+def scenario10():
+    lanes = []
+    for k in range(4):
+        c = new_ctx()
+        fam = resident_calls(c, cases.scenario10(k), who="context %d: " % k) + [msm_call(c, 0, 1000, msm_inputs(0, 1000, 10100 + 10 * k))]
+        lanes.append(Lane("context %d" % k, fam[2 * k:] + fam[:2 * k], ROUNDS[10][k]))
+    serial_then_concurrent(10, lanes)
+
+
+def scenario11():
+    specs = cases.scenario11()
+    a, b = new_ctx(), new_ctx()
+    shared = [upload_inputs(a, sp, KEEP) for sp in specs]              # uploaded once through A; both contexts read the same pointers
+    lanes = []
+    for k, c in enumerate((a, b)):
+        calls = [resident_call(c, sp, ins=ins, who="context %d: " % k) for sp, ins in zip(specs, shared)]
+        lanes.append(Lane("context %d" % k, calls[3 * k:] + calls[:3 * k], ROUNDS[11][k]))
+    serial_then_concurrent(11, lanes)
+    for sp, ins in zip(specs, shared):
+        for name, (buf, image) in ins.items():
+            need(np.array_equal(buf.download(np.uint8), image), "%s (%s): the shared input %s, or the zone behind it, was written" % (sp.op, sp.note, name))
+    b.close(); a.close()
+
+
+def scenario12():
+    case = cases.scenario12()
+    a, b = new_ctx(), new_ctx()
+    steps = resident_calls(a, case["A"], who="A: ")
+    alone = []
+    for rnd in range(2):                                               # what each step leaves in A's context when A is alone
+        alone = []
+        for call in steps:
+            call.verify(call.fn())
+            alone.append(state_of(a))
+    bad = [k for k, sp in enumerate(case["A"]) if sp.error]
+    need(len(bad) == 5 and len({alone[k][0] for k in bad}) == 5 and all(alone[k][0] for k in bad), "alone: the failing calls do not leave five messages", alone)
+
+    def a_fn(k):
+        def fn():
+            raw = steps[k].fn()
+            steps[k].verify(raw)                                       # status, index, outputs (untouched ones included) against the reference
+            got = state_of(a)
+            need(got == alone[k], "A: after '%s' the context holds %s, alone it held %s" % (steps[k].name, got, alone[k]))
+            return []
+        return fn
+    calls_a = [Call("A step %d: %s" % (k, steps[k].name), "errors", a_fn(k), None) for k in range(len(steps))]
+    for c in calls_a:
+        c.ref = False
+    calls_b = resident_calls(b, case["B"], who="B: ")
+    for c in calls_b:
+        def after(raw, r, c=c):
+            c.verify(raw)                                              # every one of B's results against the reference
+            got = state_of(b)
+            need(int(raw[-1][0]) == 0 and got == ("", 0, 0), "B: a context that only made good calls returned status %d and holds" % int(raw[-1][0]), got)
+        c.after = after
+    lanes = [Lane("A: good and failing calls", calls_a, ROUNDS[12][0]), Lane("B: good calls", calls_b, ROUNDS[12][1])]
+    wall = run_concurrent(lanes)
+    finish(12, lanes, wall)
+    a.close(); b.close()
+
+
+def scenario13():
+    case = cases.scenario13()
+    a = new_ctx()
+    calls_a = resident_calls(a, case["A"], who="A: ")
+    for c in calls_a:
+        raw = c.fn(); c.verify(raw); c.ref = raw
+    box = {}
+
+    def create():
+        box["ctx"], box["bufs"] = new_ctx(), []
+        box["calls"] = [resident_call(box["ctx"], sp, keep=box["bufs"], who="short-lived context: ") for sp in case["L"]]
+        return []
+
+    def step(k):
+        def fn():
+            c = box["calls"][k]
+            c.verify(c.fn()); return []
+        return fn
+
+    def destroy():
+        for buf in box.pop("bufs"):
+            buf.free()
+        box.pop("calls"); box.pop("ctx").close()
+        return []
+    named = [("lemsm_create", create)] + [("%s %s" % (sp.op, sp.note), step(k)) for k, sp in enumerate(case["L"])] + [("lemsm_destroy", destroy)]
+    calls_l = [Call(nm, "lifetime", f, None) for nm, f in named]
+    for c in calls_l:
+        c.ref = False
+    lanes = [Lane("L: create, fft, open_quotient, destroy", calls_l, ROUNDS[13][0]), Lane("A: transforms, quotient, product", calls_a, ROUNDS[13][1])]
+    wall = run_concurrent(lanes)
+    finish(13, lanes, wall)
+    a.close()
+
+
 # rounds of each thread's list (chosen so that the threads of a scenario run about equally long: profiles/concurrency/NOTES.md)
-ROUNDS = {1: (40, 3), 2: (25, 25), 3: (10, 10, 10, 10), 4: (25, 25), 5: (12, 60), 6: (10, 30)}
-SCENARIOS = {1: scenario1, 2: scenario2, 3: scenario3, 4: scenario4, 5: scenario5, 6: scenario6, 7: scenario7}
+ROUNDS = {1: (40, 3), 2: (25, 25), 3: (10, 10, 10, 10), 4: (25, 25), 5: (12, 60), 6: (10, 30),
+          8: (90, 30), 9: (40, 35), 10: (15, 15, 15, 15), 11: (40, 40), 12: (26, 50), 13: (10, 43)}
+SCENARIOS = {1: scenario1, 2: scenario2, 3: scenario3, 4: scenario4, 5: scenario5, 6: scenario6, 7: scenario7,
+             8: scenario8, 9: scenario9, 10: scenario10, 11: scenario11, 12: scenario12, 13: scenario13}
 
 if __name__ == "__main__":
     which = int(sys.argv[2])

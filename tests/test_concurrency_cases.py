@@ -1,0 +1,141 @@
+"""The inputs and expected values of the concurrency scenarios 8 to 13 (tests/concurrency_cases.py) without a GPU: every
+builder gives the same case when called again, the references refuse every planted failure of scenario 12 at the index the
+scenario expects and accept every other call, the two sort columns of scenario 9 run different numbers of passes, and the
+opening of scenario 8 has terms of equal length on both sides of a group of five."""
+import time
+
+import pytest
+
+import concurrency_cases as cc
+import lookup_ref
+import open_ref
+import perm_ref
+
+P, RI = cc.P, cc.RI
+BUILDERS = {"8": cc.scenario8, "9": cc.scenario9, "10": lambda: {str(k): cc.scenario10(k) for k in range(4)}, "11": lambda: {"shared": cc.scenario11()},
+            "12": cc.scenario12, "13": cc.scenario13}
+
+
+def _specs(case):
+    return [sp for name in sorted(case) if name != "options" for sp in case[name]]
+
+
+@pytest.fixture(scope="module")
+def built():
+    t0 = time.perf_counter()
+    made = {name: fn() for name, fn in BUILDERS.items()}
+    made["seconds"] = time.perf_counter() - t0
+    return made
+
+
+def test_builders_are_deterministic_and_quick(built):
+    print("scenarios 8-13 built in %.2f s" % built["seconds"])
+    assert built["seconds"] < 30                                            # (measured: profiles/concurrency/NOTES.md)
+    for name, fn in BUILDERS.items():
+        again = _specs(fn())
+        assert [sp.fingerprint() for sp in again] == [sp.fingerprint() for sp in _specs(built[name])], name
+    prints = [sp.fingerprint() for name in BUILDERS if name != "9" for sp in _specs(built[name])]
+    assert len(set(prints)) == len(prints)                                  # no two calls alike ...
+    assert len({sp.fingerprint() for sp in _specs(built["9"])}) == 5       # ... but in scenario 9: two transforms, one combination, two sorts
+    assert len({sp.fingerprint() for k in range(4) for sp in built["10"][str(k)]}) == 4 * 7        # every context of scenario 10 has inputs of its own
+
+
+def test_every_call_fits_its_buffers(built):
+    for name in BUILDERS:
+        for sp in _specs(built[name]):
+            for out, cap, want, init in sp.outs:
+                assert len(want) % 32 == 0 and len(want) <= cap * 32, (name, sp, out)
+                assert init is None or init.nbytes <= cap * 32
+                assert not sp.error or want == (b"" if init is None else init.tobytes()), (name, sp, out)   # a refused call leaves its output as it was
+            assert sp.error or sp.index is None
+            assert not (sp.error and sp.small)
+
+
+def _ints_of(sp, name):
+    return cc._ints(sp.ins[name])
+
+
+def test_planted_failures_of_scenario_12(built):
+    a, b = built["12"]["A"], built["12"]["B"]
+    assert not any(sp.error for sp in b) and sorted(sp.op for sp in b) == ["fft", "fp", "pair", "quotient"]
+    assert [sp.error for sp in a] == [False, True, False, True, False, True, False, True, False, True, False]
+    bad = {sp.op: sp for sp in a if sp.error}
+    assert sorted(bad) == ["divide", "fft", "fp", "lincomb", "pair"]
+    for k in range(1, len(a), 2):                                           # every refusal is followed by the good call of the same entry
+        assert a[k].op == a[k + 1].op and not a[k + 1].error
+    # lookup_permute: the lowest row of the smallest missing value, which is not the lowest row that misses
+    sp = bad["pair"]
+    A, S = [v * RI % P for v in _ints_of(sp, "A")], [v * RI % P for v in _ints_of(sp, "S")]
+    missing = [r for r, v in enumerate(A) if v not in set(S)]
+    assert missing == [40, 2222] and A[2222] < A[40]
+    with pytest.raises(lookup_ref.NotInTable) as e:
+        lookup_ref.permute_expression_pair(A, S)
+    assert e.value.index == sp.index == lookup_ref.missing_row(A, S) == 2222 and sp.status == cc.NOT_IN_TABLE
+    # fraction_products: zero denominators at rows 1234 (two columns) and 4711
+    sp = bad["fp"]
+    nums = [[v * RI % P for v in _ints_of(sp, "num%d" % k)] for k in range(sp.args["n_num"])]
+    dens = [[v * RI % P for v in _ints_of(sp, "den%d" % k)] for k in range(sp.args["n_den"])]
+    assert [r for r in range(sp.args["n"]) if any(c[r] == 0 for c in dens)] == [1234, 4711]
+    with pytest.raises(perm_ref.ZeroDenominator) as e:
+        perm_ref.fraction_products(nums, dens, sp.args["n"], 1, sp.args["tap"])
+    assert e.value.index == sp.index == 1234 and sp.status == cc.DIV_ZERO
+    # divide_by_roots: 2 coefficients, 4 roots: stage 2 meets the empty polynomial
+    sp = bad["divide"]
+    with pytest.raises(OverflowError) as e:
+        open_ref.divide_roots(_ints_of(sp, "a"), [v * RI % P for v in cc._ints(sp.args["roots"])], P)
+    assert e.value.args[0] == sp.index == sp.args["length"] == 2 < sp.args["roots"].shape[0] and sp.status == cc.OVERFLOW
+    # fft: omega is no primitive 2^logn-th root
+    sp = bad["fft"]
+    w, logn = cc._ints(sp.args["omega"])[0] * RI % P, sp.args["logn"]
+    assert pow(w, 1 << logn, P) == 1 and pow(w, 1 << (logn - 1), P) != P - 1 and sp.status == cc.BAD_ARG and sp.index is None
+    good = a[a.index(sp) + 1]
+    w = cc._ints(good.args["omega"])[0] * RI % P
+    assert good.args["logn"] == logn and pow(w, 1 << (logn - 1), P) == P - 1 and good.outs[0][3].tobytes() == sp.outs[0][3].tobytes()
+    assert a[0].op == "fft" and a[0].args["logn"] != logn                  # the table the context holds before is another size's
+    # poly_lincomb: a capacity one element below the combination's length
+    sp = bad["lincomb"]
+    good = a[a.index(sp) + 1]
+    assert sp.outs[0][1] == max(sp.args["lens"]) - 1 == good.outs[0][1] - 1 and sp.status == cc.BAD_ARG and len(good.outs[0][2]) == 32 * good.outs[0][1]
+
+
+def test_good_calls_are_accepted(built):
+    """every call that is not a planted failure: the reference gave a full result"""
+    for name in BUILDERS:
+        for sp in _specs(built[name]):
+            if not sp.error:
+                assert sp.status == cc.OK and all(len(want) for _, _, want, _ in sp.outs), (name, sp)
+    sp = [s for s in built["12"]["A"] if s.op == "pair" and not s.error][0]
+    A, S = [v * RI % P for v in _ints_of(sp, "A")], [v * RI % P for v in _ints_of(sp, "S")]
+    assert lookup_ref.missing_row(A, S) is None
+    assert cc._mont(lookup_ref.permute_closed_form(A, S)[1]).tobytes() == sp.outs[1][2]              # (the closed form against the pop loop)
+
+
+def test_sort_columns_of_scenario_9(built):
+    case = built["9"]
+    (ka, sa), = [(k, sp) for k, sp in enumerate(case["A"]) if sp.op == "sort"]
+    (kb, sb), = [(k, sp) for k, sp in enumerate(case["B"]) if sp.op == "sort"]
+    assert ka == kb and sa.args["n"] == sb.args["n"]
+    pa = lookup_ref.live_passes([v * RI % P for v in _ints_of(sa, "keys")])
+    pb = lookup_ref.live_passes([v * RI % P for v in _ints_of(sb, "keys")])
+    assert pa == list(range(8)) and len(pb) == lookup_ref.MAX_PASSES        # upper limbs shared: 24 passes skipped; random keys: none
+    assert lookup_ref.sort_bytes(sa.args["n"], len(pa)) != lookup_ref.sort_bytes(sb.args["n"], len(pb))
+    # the transforms: where one context alternates two sizes the other repeats one, and halfway they change places
+    logn = {name: [sp.args["logn"] if sp.op == "fft" else None for sp in case[name]] for name in "AB"}
+    assert logn["A"] == [11, 12, 11, 12, None, None, 12, 12, 12, 12] and logn["B"] == [12, 12, 12, 12, None, None, 11, 12, 11, 12]
+    assert case["A"][4] is case["B"][4] and case["A"][4].op == "lincomb" and case["options"] == {"A": {"open_group": 1}, "B": {}}
+
+
+def test_open_case_of_scenario_8(built):
+    (sp,) = [s for s in built["8"]["B"] if s.op == "quotient"]
+    lens = sp.args["lens"]
+    assert len(lens) == 7 and max(lens) == 16385 and len(set(lens)) >= 4 and sp.args["low"].shape[0] == 3 and sp.args["roots"].shape[0] == 3
+    groups = cc.term_groups(lens)
+    assert [len(g) for g in groups] == [5, 2]
+    assert groups[0][-1] == groups[1][0] and len(set(groups[0])) >= 2 and len(set(groups[1])) >= 2 and cc.straddles(lens)
+    assert not cc.straddles([9, 9, 9, 9, 9, 4, 4]) and not cc.straddles([7, 7, 7, 7, 7, 7])
+    # the sizes the issue names for the single-block stages
+    a = {s.op + str(k): s for k, s in enumerate(built["8"]["A"])}
+    assert [int(n) for _, n in a["kate5"].args["rows"]] == [16385] and (a["mul6"].args["la"], a["mul6"].args["lb"]) == (300, 257)
+    assert (a["mul7"].args["la"], a["mul7"].args["lb"]) == (31, 40) and a["fft0"].args["logn"] == 12
+    b = {s.op: s for s in built["8"]["B"]}
+    assert b["fp"].args["n"] == 8193 and b["sort"].args["n"] == 5000 and b["pair"].args["n"] == 4096 and b["fsums"].args["n"] == 4097

@@ -1,6 +1,8 @@
 """The per-context threading contract of the C ABI (include/lemsm.h, "Threading") on one GPU: any host thread may call, a
 context serves one call at a time, distinct contexts may be used concurrently -- several of them on device 0, more of them
-than the process has hardware queues -- and device pointers may be read by several contexts at once.
+than the process has hardware queues -- and device pointers may be read by several contexts at once.  Scenarios 1 to 7 run
+the MSM, witness and column entries, scenarios 8 to 13 the resident polynomial entries (fft to open_quotient) with the state
+they keep per context: the cached twiddle table, the regrown workspaces, the device error words, poly_last and sort_last.
 
 Each scenario runs in a fresh child interpreter (tests/concurrency_child.py, which documents how a scenario is run and what
 it compares): contexts on device 0, every expected value from the oracle before a thread starts, threading.Thread workers
@@ -106,3 +108,58 @@ def test_7_hand_off_between_threads():
     other; closed from yet another thread"""
     res = _run(7)
     assert res["threads"] == 4 and res["calls"] == [1, 1, 1, 1]
+
+
+def test_8_resident_families_side_by_side():
+    """thread A: fft_device (logn 12, and 11 inverse with a scale), coset_fft_device, coeff_to_extended_device and back,
+    kate_division_device of 16 385 coefficients, poly_mul_device on both paths -- its twiddle table is rebuilt by every call;
+    thread B: fraction_products_device (n = 8193), permutation_product_device, sort_field_device, lookup_permute_device,
+    fraction_sums_device and an open_quotient over 7 ragged polynomials; limb for limb against the big-integer references
+    and against the same lists made serially"""
+    res = _run(8)
+    assert res["threads"] == 2 and res["serial_s"] is not None
+    _overlapped(res)
+
+
+def test_9_same_entries_in_different_states():
+    """two contexts, the same inputs: one rebuilds its twiddle table on every call while the other runs on the cached one,
+    then the other way round; poly_lincomb under open_group = 1 and the default gives the same bytes; a sort that skips 24
+    passes beside one that runs all; after every call poly_last and sort_last are those of the same call made alone"""
+    res = _run(9)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_10_resident_entries_on_more_contexts_than_hardware_queues():
+    """four contexts on four threads, each a different cyclic shift of fft, coeff_to_extended, gate_eval, fraction_products,
+    lookup_permute, open_quotient, kate_division and one msm_device (n = 1000) on its own inputs"""
+    res = _run(10)
+    assert res["threads"] == 4
+    _overlapped(res)
+
+
+def test_11_shared_read_only_resident_columns():
+    """one set of resident columns and polynomials, two contexts running gate_eval, poly_lincomb, open_quotient,
+    lookup_permute, fraction_products and kate_division on the same pointers into buffers of their own; the shared inputs
+    and the zones behind them hold their uploaded bytes at the end"""
+    res = _run(11)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_12_resident_errors_stay_where_they_happen():
+    """thread A alternates good calls with a missing lookup value, a zero denominator, a division with fewer coefficients
+    than roots, an omega of the wrong order and a capacity one element short: status, index and last_error are its own
+    call's after every call, every refused call leaves its output untouched, the transform behind the refused one is
+    correct; thread B, good calls only, never sees a status or a message"""
+    res = _run(12)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_13_context_lifetime_beside_resident_calls():
+    """one thread creates a context, runs an fft and an open_quotient against the reference and destroys the context (its
+    twiddle table, workspace and staging with it), 10 times, while another runs scenario 8's transform list"""
+    res = _run(13)
+    assert res["threads"] == 2 and res["rounds"][0] == 10
+    _overlapped(res)

@@ -159,17 +159,18 @@ def test_engine_zero_numerator_in_the_middle(ctx):
 
 def test_engine_zero_denominators(ctx):
     """two rows with a zero denominator, one in the last partial tile: the lowest index is reported, and a zero numerator at
-    the same row does not excuse it"""
+    the same row does not excuse it; the refused call leaves the output column as it was"""
     n = TILE + 100
     lo, hi = 1000, TILE + 50
     num_raw, den_raw = _column(8, n)[0].copy(), _column(9, n)[0].copy()
     den2 = _column(11, n)
     den_raw[hi] = 0
     d_num, d_den, d_den2 = ctx.to_device(num_raw), ctx.to_device(den_raw), ctx.to_device(den2[0])
-    out = ctx.alloc(n * 32)
+    out = _filled(ctx, n)
     with pytest.raises(api.RefDivisionByZero) as e:                  # the one in the last partial tile, alone
         ctx.fraction_products_device([d_num.ptr], [d_den2.ptr, d_den.ptr], n, out=out)
     assert e.value.index == hi and ctx.lib.lemsm_last_bad_index(ctx.h) == hi
+    _untouched(out)
     num_raw[lo] = 0
     den_raw[lo] = 0
     d_num.upload(num_raw)
@@ -177,6 +178,7 @@ def test_engine_zero_denominators(ctx):
     with pytest.raises(api.RefDivisionByZero) as e:
         ctx.fraction_products_device([d_num.ptr], [d_den2.ptr, d_den.ptr], n, out=out)
     assert e.value.index == lo and ctx.lib.lemsm_last_bad_index(ctx.h) == lo
+    _untouched(out)
     with pytest.raises(ref.ZeroDenominator) as r:
         ref.fraction_products([_std(num_raw)], [den2[1], _std(den_raw)], n)
     assert r.value.index == lo
