@@ -18,5 +18,6 @@ from .api import (  # noqa: F401
     domain_plan, vanishing_on_cosets, EXT_INTERLEAVED, EXT_COSET_MAJOR,
     fraction_products_geometry, permutation_plan, permutation_products,
     sort_field_geometry, lookup_permute_plan, permute_expression_pair, NotInTable, debug_sort_thresholds,
+    lookup_multiplicities_plan, lookup_multiplicities,
     poly_lincomb, divide_by_roots, open_quotient, lagrange_interpolate, open_plan,
 )

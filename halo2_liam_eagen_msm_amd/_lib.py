@@ -81,6 +81,7 @@ SYMBOLS = [
     "lemsm_permutation_plan", "lemsm_permutation_product_device", "lemsm_permutation_product",
     "lemsm_sort_field_geometry", "lemsm_lookup_permute_plan", "lemsm_sort_field_device", "lemsm_sort_field",
     "lemsm_lookup_permute_device", "lemsm_lookup_permute", "lemsm_sort_last", "lemsm_debug_sort_thresholds",
+    "lemsm_lookup_multiplicities_plan", "lemsm_lookup_multiplicities_device", "lemsm_lookup_multiplicities",
     "lemsm_poly_lincomb_device", "lemsm_poly_lincomb", "lemsm_poly_divide_roots_device", "lemsm_poly_divide_roots",
     "lemsm_open_quotient_device", "lemsm_open_quotient", "lemsm_open_plan", "lemsm_lagrange_interpolate",
 ]
@@ -278,6 +279,9 @@ def load() -> ctypes.CDLL:
         "lemsm_lookup_permute": (i, [vp, u64p, u64p, sz, u64p, u64p, szp]),
         "lemsm_sort_last": (i, [vp, u32p, u32p]),
         "lemsm_debug_sort_thresholds": (i, [szp, szp]),
+        "lemsm_lookup_multiplicities_plan": (i, [szp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "lemsm_lookup_multiplicities_device": (i, [vp, ctypes.POINTER(ctypes.c_void_p), szp, sz, vp, sz, i, vp, szp]),
+        "lemsm_lookup_multiplicities": (i, [vp, ctypes.POINTER(ctypes.c_void_p), szp, sz, u64p, sz, i, u64p, szp]),
         "lemsm_poly_lincomb_device": (i, [vp, vp, vp, sz, u64p, u64p, sz, vp, sz, szp]),
         "lemsm_poly_lincomb": (i, [vp, vp, vp, sz, u64p, u64p, sz, u64p, sz, szp]),
         "lemsm_poly_divide_roots_device": (i, [vp, vp, sz, u64p, sz, i, vp, sz, u64p, szp]),

@@ -98,7 +98,8 @@ class RefDivisionByZero(LemsmError, ZeroDivisionError):
 
 class NotInTable(LemsmError, LookupError):
     """halo2: Error::ConstraintSystemFailure from permute_expression_pair -- a value of the lookup's input column is not in
-    its table column; .index = the lowest input row that holds the smallest missing value"""
+    its table column; .index = the lowest input row that holds the smallest missing value (lookup_multiplicities*: the lowest
+    position of the concatenated input columns)"""
 
     def __init__(self, status, msg, index):
         super().__init__(status, msg)
@@ -1188,6 +1189,44 @@ class Context:
         self._check(self.lib.lemsm_sort_last(self.h, ctypes.byref(run), ctypes.byref(skipped)))
         return run.value, skipped.value
 
+    # ---- log-derivative lookup: the multiplicity column m ----
+    @staticmethod
+    def lookup_multiplicities_plan(lens, t: int) -> dict:
+        """the module-level lookup_multiplicities_plan"""
+        return lookup_multiplicities_plan(lens, t)
+
+    def lookup_multiplicities_device(self, d_inputs, lens, d_table, t: int, form: int = FORM_MONTGOMERY, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """m[0 .. t) of the resident table column d_table under the k resident input columns d_inputs of lens[c] rows each
+        (device pointers or DeviceBuffers; None for a column of no rows): m[j] = how many cells of the concatenated inputs hold
+        T[j] at the lowest table row with that value, 0 at every later one.  form: FORM_MONTGOMERY (what fraction_sums_device
+        takes as num) or FORM_CANONICAL (plain little-endian counts).  NotInTable (.index = the lowest position of the
+        concatenation with the smallest value T lacks).  m as a DeviceBuffer"""
+        k = len(lens)
+        if out is None:
+            out = DeviceBuffer(self, max(t * 32, 16))
+        raw = lambda p: p.ptr if isinstance(p, DeviceBuffer) else p
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[raw(p) for p in d_inputs])
+        ls = (ctypes.c_size_t * max(k, 1))(*[int(n) for n in lens])
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_lookup_multiplicities_device(self.h, ptrs, ls, k, raw(d_table), t, form, raw(out), ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out
+
+    def lookup_multiplicities(self, inputs, table, form: int = FORM_MONTGOMERY) -> np.ndarray:
+        """lookup_multiplicities_device for columns in host memory (a list of (len, 4) uint64 columns and a (t, 4) table): m as
+        (t, 4) uint64"""
+        cols = [_limbs(c, 4) if np.size(c) else np.zeros((0, 4), np.uint64) for c in inputs]
+        tab = _limbs(table, 4) if np.size(table) else np.zeros((0, 4), np.uint64)
+        k = len(cols)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[_ptr(c) if c.shape[0] else None for c in cols])
+        ls = (ctypes.c_size_t * max(k, 1))(*[c.shape[0] for c in cols])
+        out = np.zeros_like(tab)
+        bad = ctypes.c_size_t(0)
+        rc = self.lib.lemsm_lookup_multiplicities(self.h, ptrs, ls, k, _ptr(tab) if tab.shape[0] else None, tab.shape[0], form,
+                                                  _ptr(out) if tab.shape[0] else None, ctypes.byref(bad))
+        self._check(rc, bad.value)
+        return out
+
     def debug_ntt(self, data, logn: int, inverse: bool = False) -> np.ndarray:
         a = _limbs(data, 4)
         assert a.shape[0] % (1 << logn) == 0
@@ -2072,6 +2111,30 @@ def permute_expression_pair(input, table, ctx: Optional[Context] = None):
         raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "input and table columns differ in length")
     ap, sp = (ctx or default_context()).lookup_permute(mont(input), mont(table))
     return std(ap), std(sp)
+
+
+def lookup_multiplicities_plan(lens, t: int) -> dict:
+    """prices one lookup_multiplicities_device call of len(lens) input columns of lens[c] rows over a table of t rows with no
+    pass skipped (pure host: lemsm_lookup_multiplicities_plan): {"bytes", "field_mults", "workspace_bytes"}"""
+    lib = _lib.load()
+    by = ctypes.c_uint64(); fm = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    k = len(lens)
+    ok = t >= 0 and all(n >= 0 for n in lens)
+    ls = (ctypes.c_size_t * max(k, 1))(*[int(n) for n in lens]) if ok else None
+    rc = lib.lemsm_lookup_multiplicities_plan(ls, k, t, ctypes.byref(by), ctypes.byref(fm), ctypes.byref(wb)) if ok else _lib.LEMSM_ERR_BAD_ARG
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"bytes": by.value, "field_mults": fm.value, "workspace_bytes": wb.value}
+
+
+def lookup_multiplicities(inputs, table, ctx: Optional[Context] = None) -> List[int]:
+    """the multiplicity column of the log-derivative lookup over standard-form integers mod r: `inputs` is a list of columns,
+    `table` a column; m[j] = how many cells of all the inputs hold table[j] at the lowest row j with that value, 0 at every later
+    one, as plain counts.  Raises NotInTable (.index = the lowest position of the concatenated inputs with the smallest value
+    `table` lacks)."""
+    m = (ctx or default_context()).lookup_multiplicities([_fr_mont(c) for c in inputs], _fr_mont(table), FORM_CANONICAL)
+    b = m.tobytes()
+    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
 
 
 def _fr_mont(vals) -> np.ndarray:

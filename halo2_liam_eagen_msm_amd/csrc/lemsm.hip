@@ -34,6 +34,7 @@
 #include "gate.cuh"
 #include "perm.cuh"
 #include "lookup.cuh"
+#include "logup.cuh"
 #include "open.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
@@ -2791,4 +2792,5 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "gate_abi.inc"
 #include "perm_abi.inc"
 #include "lookup_abi.inc"
+#include "logup_abi.inc"
 #include "open_abi.inc"

@@ -938,6 +938,52 @@ int lemsm_sort_last(const lemsm_ctx* ctx, uint32_t* passes_run, uint32_t* passes
    permuted pair 2 n + 1.  Both are multiples of the geometry's tile. */
 int lemsm_debug_sort_thresholds(size_t* convert_keys_per_trip, size_t* scan_top_words);
 
+/* ---- log-derivative lookup: the multiplicity column m on resident columns (src/config.rs:402-437) -----------
+   The reference's lookup argument states c[i+1] - c[i] = 1 / (v - b[i+1]) on the lookup rows and c[0] - c[-1] =
+   -b[0] / (v - t[0]) on the table rows (:421-424): cell b[0] of a table row is the MULTIPLICITY of that table entry.  The two
+   running sums are lemsm_fraction_sums*; this is the column that makes them meet.  The same column is m(X) of the halo2 forks
+   with the log-derivative ("mv") lookup, where several input expressions share one table (stated from memory; the formula
+   here is the contract).  The conventions of the lookup section above: bn256::Fr, 32-byte raw Montgomery elements, assumed
+   canonical and not checked; ORDER is the order of the standard-form integers; LEMSM_ERR_BAD_ARG leaves nothing queued and
+   the outputs untouched; the figures of every call go to lemsm_poly_last; option ws_canary guards every carved workspace.
+     Column c of the k input columns has lens[c] rows; position sum_{c' < c} lens[c'] + r of their concatenation A[0 .. N) is
+     row r of column c.  The table is T[0 .. t).
+     m[j] = the number of positions i with A[i] == T[j] if j is the LOWEST row of T that holds that value, else 0.
+   So sum_j m[j] = N, and for every v outside T: sum_i 1 / (v - A[i]) = sum_j m[j] / (v - T[j]).
+   The output is a unique function of the inputs: the host entry, the device entry and repeated calls give the same bytes.
+   Pure host: prices one call with no pass skipped.  bytes = 32 (3 N + 6 t + 3 max_passes (N + t)), field_mults = N + 3 t (see
+   lemsm_lookup_multiplicities_device); N == 0: bytes = 32 t, field_mults = 0.  workspace_bytes: what a call reserves (0 when
+   N == 0).  N == t == 0 gives zeros.  Every output is optional.  The refusals of the entry that need no pointer: k == 0,
+   k > 16, lens == NULL, N or t above 2^28: LEMSM_ERR_BAD_ARG. */
+int lemsm_lookup_multiplicities_plan(const size_t* lens, size_t k, size_t t, uint64_t* bytes, uint64_t* field_mults,
+                                     uint64_t* workspace_bytes);
+/* d_out_m[0 .. t) = m as 32-byte elements: form LEMSM_FORM_MONTGOMERY writes each count as a raw Montgomery element (what
+   column b holds and what lemsm_fraction_sums_device takes as d_num), LEMSM_FORM_CANONICAL as a standard-form little-endian
+   integer (the scalars lemsm_msm_device takes); any other form: LEMSM_ERR_BAD_ARG.  Rows >= t are not written.
+   k = 1 .. 16; every lens[c] >= 0, and a column of no rows may have a NULL pointer; N <= 2^28 and t <= 2^28, independent
+   of each other.  N == 0 gives all-zero m; t == 0 with N == 0 is LEMSM_OK and writes nothing.
+   A value of A that T lacks (every value when t == 0 < N): LEMSM_ERR_NOT_IN_TABLE; *bad_index (optional) and
+   lemsm_last_bad_index = the lowest POSITION OF THE CONCATENATION that holds the SMALLEST missing value; the output is not
+   written.
+   k == 0, k > 16, a null pointer with rows behind it, the output overlapping the table or an input column, N or t above
+   2^28: LEMSM_ERR_BAD_ARG.
+   The k columns are converted into one buffer of N standard-form keys and sorted, the table likewise (key-only); every
+   table row in its own order finds its value's run in the sorted table and the lowest row of a run wins (a minimum of row
+   indices); m is zeroed, and every run of the sorted table writes the length of its value's run in the sorted inputs to the
+   winner's row.
+   lemsm_sort_last: passes run and skipped, summed over the sorts the call ran (the inputs' when N > 0, the table's when N > 0
+   and t > 0: run + skipped = max_passes times that number).
+   lemsm_poly_last: ms; bytes = 32 (3 N + 6 t + 3 (N passes_run_inputs + t passes_run_table)): the conversions, the passes that
+   ran, As read for the missing values, T read for the lowest rows, m zeroed, the sorted table read and the counts written
+   priced at t (the probes of the binary searches and the u32 words are
+   not in it); field_mults = N + 3 t as the plan prices them (the conversions, each table row's standard form again, the counts to
+   Montgomery form: priced at t and in both forms).  N == 0: bytes = 32 t, field_mults = 0. */
+int lemsm_lookup_multiplicities_device(lemsm_ctx* ctx, const void* const* d_inputs, const size_t* lens, size_t k,
+                                       const void* d_table, size_t t, int form, void* d_out_m, size_t* bad_index);
+/* The same with every column in host memory. */
+int lemsm_lookup_multiplicities(lemsm_ctx* ctx, const uint64_t* const* inputs, const size_t* lens, size_t k,
+                                const uint64_t* table, size_t t, int form, uint64_t* out_m, size_t* bad_index);
+
 /* ---- challenge post-processing helpers (src/config.rs:166-187) ------------------------ */
 /* Host-side (a handful of field operations each); field elements are raw Montgomery limbs of the BASE field of `curve`.
    to_curve_x (:166-175): returns c itself when c^3 + b is a square; the reference's loop never changes x (:170-173), so
