@@ -1,8 +1,9 @@
-"""The inputs and expected values of scenarios 8 to 13 of tests/concurrency_child.py (the threading contract on the resident
-polynomial entries), built without a context: every builder is a pure function of its arguments, every expected value comes
-from the big-integer references the entries' own tests use (oracle.divisor's best_fft and PolyRing, tests/domain_ref.py,
-gate_ref.py, perm_ref.py, lookup_ref.py, open_ref.py, rhs_ref.py).  tests/test_concurrency_cases.py holds the builders
-without a GPU; concurrency_child.py turns a Spec into a library call on a context.  Not a test module.
+"""The inputs and expected values of scenarios 8 to 16 of tests/concurrency_child.py (the threading contract on the resident
+polynomial entries; 14 to 16: on the multiplicity entry), built without a context: every builder is a pure function of its
+arguments, every expected value comes from the big-integer references the entries' own tests use (oracle.divisor's best_fft and
+PolyRing, tests/domain_ref.py, gate_ref.py, perm_ref.py, lookup_ref.py, logup_ref.py, open_ref.py, rhs_ref.py).
+tests/test_concurrency_cases.py holds the builders without a GPU; concurrency_child.py turns a Spec into a library call on a
+context.  Not a test module.
 
 A Spec is one library call:
     ins     name -> (n, 4) uint64 array: a resident input (raw limbs); the call may only read it
@@ -22,6 +23,7 @@ from oracle.divisor import best_fft
 import domain_ref
 import fuzz_resident as fr
 import gate_ref
+import logup_ref
 import lookup_ref
 import open_ref
 import perm_ref
@@ -32,6 +34,7 @@ SEED = 20261020
 GROUP = 5                           # terms of k_open_lincomb that share one reduction (open.cuh: OPEN_G_MAX)
 OK, BAD_ARG, OVERFLOW = _lib.LEMSM_OK, _lib.LEMSM_ERR_BAD_ARG, _lib.LEMSM_ERR_ARITH_OVERFLOW
 DIV_ZERO, NOT_IN_TABLE = _lib.LEMSM_ERR_DIVISION_BY_ZERO, _lib.LEMSM_ERR_NOT_IN_TABLE
+MONT, CANON = fr.MONT, fr.CANON
 _ints, _arr, _mont, _fe, _rand = fr._ints, fr._arr, fr._mont, fr._fe, fr._rand
 
 
@@ -287,6 +290,42 @@ def straddles(lens, group=GROUP):
     return len(groups) >= 2 and any(a[-1] == b[0] for a, b in zip(groups, groups[1:])) and len(set(groups[0])) >= 2
 
 
+# ---- multiplicities --------------------------------------------------------------------------------------------------------------
+def multiplicities(seed, lens, t, form=MONT, below=None, use=None, missing=(), columns=None, out_at=None):
+    """lookup_multiplicities_device over len(lens) resident columns of lens[c] rows and a table of t rows drawn from about t / 2
+    values (below: values under that bound; else full-width ones).  Every non-empty column and the table are resident inputs
+    ("c0", "c1", .., "T"); the call takes the columns `use` names (default: all of them).  missing: (column, row) cells given
+    values the table lacks, the first cell the smallest one.  columns: the call's own (input name, rows) list in place of the
+    drawn columns (k = 17 has no reference); out_at: (input name, element) -- the output pointer the call passes in place of its
+    own buffer, which must stay as it was"""
+    rng = _rng(seed, 15)
+    draw = (lambda: int(rng.integers(0, below))) if below else (lambda: fr._fe_int(rng))
+    alphabet = sorted({draw() for _ in range(max(1, t // 2))})
+    table = [alphabet[int(i)] for i in rng.integers(0, len(alphabet), t)]
+    inputs = [[table[int(i)] for i in rng.integers(0, t, n)] if n else [] for n in lens]
+    have = set(table)
+    gone = sorted(v for v in (draw() + 1 + j for j in range(4 * len(missing))) if v % P not in have)
+    for (col, row), v in zip(missing, gone):
+        inputs[col][row] = v % P
+    ins = dict([("c%d" % c, _mont(col)) for c, col in enumerate(inputs) if col] + [("T", _mont(table))])
+    use = list(range(len(lens))) if use is None else list(use)
+    cols = [("c%d" % c if inputs[c] else None, len(inputs[c])) for c in use] if columns is None else list(columns)
+    kw = dict(cols=[name for name, _ in cols], lens=[n for _, n in cols], t=t, form=form, out_at=out_at)
+    note = "lens=%s t=%d form=%d%s" % (kw["lens"], t, form, " keys below %d" % below if below else "")
+    if columns is not None or out_at is not None:
+        why = "k = %d" % len(cols) if columns is not None else "the output at %s + %d" % out_at
+        return Spec("mult", note + " " + why, ins, [("m", t, b"", None)], status=BAD_ARG, **kw)
+    taken = [inputs[c] for c in use]
+    pos = logup_ref.missing_position(taken, table)
+    if pos is not None:
+        return Spec("mult", note + " missing at %s" % (list(missing),), ins, [("m", t, b"", None)], status=NOT_IN_TABLE, index=pos, **kw)
+    m = logup_ref.multiplicities(taken, table)
+    N = sum(kw["lens"])
+    pa, ps = len(logup_ref.live_passes(logup_ref.concat(taken))), len(logup_ref.live_passes(table))
+    return Spec("mult", note, ins, [("m", t, (_mont(m) if form == MONT else _arr(m)).tobytes(), None)],
+                small=[np.array([pa + ps, logup_ref.sorts(N, t) * logup_ref.MAX_PASSES - pa - ps], np.uint32)], passes=(pa, ps), **kw)
+
+
 # ---- the scenarios ---------------------------------------------------------------------------------------------------------------
 OPEN_LENS = [300, 16385, 4097, 300, 9000, 17, 300]                     # ragged; sorted: 16385 9000 4097 300 300 | 300 17
 
@@ -350,3 +389,43 @@ def scenario12():
 
 def scenario13():
     return {"L": [fft(1300, 10), open_quotient(1301, [1000, 2500, 1000], 2, 2)], "A": transform_users(1350)}
+
+
+MULT_LENS, MULT_T = [2500, 570, 1029], 1025                           # N = 4099 in 3 ragged columns under t = 1025 rows with duplicates
+
+
+def scenario14():
+    """A: m in Montgomery form, a lookup_permute, a sort of keys that share their upper limbs; B: m of the same inputs in canonical
+    form, an open_quotient, m over keys below 2^16 (its sorts skip 30 of 32 passes each)"""
+    assert sum(MULT_LENS) == 4099
+    return {"A": [multiplicities(1400, MULT_LENS, MULT_T, MONT), lookup_permute(1401, 3000), sort(1402, 3000, shared_upper=True)],
+            "B": [multiplicities(1400, MULT_LENS, MULT_T, CANON), open_quotient(1451, [1500, 0, 2100, 40], 2, 3),
+                  multiplicities(1452, [1200, 0, 900], 700, MONT, below=1 << 16)]}
+
+
+SHARED_LENS, SHARED_T = [900, 1300, 0, 257, 1024, 600], 1500
+
+
+def scenario15():
+    """one table and one set of six input columns (one of no rows); context "0" and context "1" take different subsets of the
+    columns, each once in either form"""
+    subsets = {"0": ([0, 2, 4], [1, 2, 3, 5]), "1": ([1, 3], [0, 1, 2, 3, 4, 5])}
+    return {name: [multiplicities(1500, SHARED_LENS, SHARED_T, MONT, use=x), multiplicities(1500, SHARED_LENS, SHARED_T, CANON, use=y)]
+            for name, (x, y) in subsets.items()}
+
+
+def scenario16():
+    """A: good calls and refusals in turn -- a missing value; two missing values, the smaller one in a later column (a later launch
+    of k_lu_find_pos reports it); k = 17; an output that overlaps the table.  B: good calls only"""
+    lens, t = [700, 0, 900, 300], 800
+    a = [multiplicities(1600, lens, t, MONT),
+         multiplicities(1601, lens, t, MONT, missing=[(0, 123)]),
+         multiplicities(1601, lens, t, CANON),
+         multiplicities(1602, lens, t, CANON, missing=[(2, 77), (0, 5), (3, 299)]),
+         multiplicities(1602, lens, t, MONT),
+         multiplicities(1603, lens, t, MONT, columns=[("c0", 1)] * 17),
+         multiplicities(1603, lens, t, CANON),
+         multiplicities(1604, lens, t, MONT, out_at=("T", 1)),
+         multiplicities(1604, lens, t, MONT)]
+    b = [multiplicities(1650, [1000, 300], 600, MONT), multiplicities(1651, [0, 1500], 333, CANON, below=1 << 16), multiplicities(1652, [2049], 1025, MONT)]
+    return {"A": a, "B": b}

@@ -2,7 +2,7 @@
 "Threading") on device 0.  Usage: python concurrency_child.py ROOT SCENARIO.  Not a test module.
 
 Every expected value comes from the oracle (oracle/cref.py, tests/rhs_ref.py, tests/column_ref.py, oracle/divisor.py; for
-scenarios 8-13, the resident polynomial entries, from the big-integer references tests/concurrency_cases.py builds on) and is
+scenarios 8-16, the resident polynomial entries, from the big-integer references tests/concurrency_cases.py builds on) and is
 computed single-threaded before any thread starts.  The threads are threading.Thread; ctypes releases the GIL for the
 duration of a CDLL call, so the library calls of different threads do overlap; all threads leave one threading.Barrier
 before their first call and every call's (start, end) on time.perf_counter() is kept.  Every context has ws_canary = 1.
@@ -11,8 +11,8 @@ Scenarios 1-4 first make every thread's call list serially, on the same contexts
 first serial output of every call is checked against the oracle, every later output -- serial or concurrent -- must equal it
 limb for limb (raw Jacobian limbs, raw coefficient arrays).  The Jacobian outputs of an entry named in CANON_ONLY are compared
 in canonical form instead: two serial runs of it already differ in raw limbs (profiles/concurrency/NOTES.md says why); its
-other outputs stay limb-exact.  Scenarios 8-11 run the same way; every output of the resident entries is limb-exact, and a
-call's raw outputs there include the guard zone behind each output buffer, its status and its reported index.  The last line
+other outputs stay limb-exact.  Scenarios 8-11, 14 and 15 run the same way; every output of the resident entries is limb-exact,
+and a call's raw outputs there include the guard zone behind each output buffer, its status and its reported index.  The last line
 printed is "RESULT <json>": rounds, calls, the share of calls that overlapped a call of another thread, the wall time of the
 concurrent phase and of the serial one, and how long each thread ran in the concurrent phase.
 
@@ -634,7 +634,15 @@ def launcher(ctx, sp, ins, o):
             ctx.lookup_permute_device(p["A"], p["S"], a["n"], o[0], o[1])
             return [np.array(ctx.sort_last(), np.uint32)]
         return run_pair
-    cap = sp.outs[0][1]                                                # the C entries themselves: the capacity is the Spec's, exactly
+    if sp.op == "mult":
+        cols = [p[name] if name else None for name in a["cols"]]
+        out = o[0].ptr if a["out_at"] is None else p[a["out_at"][0]] + 32 * a["out_at"][1]
+
+        def run_mult():
+            ctx.lookup_multiplicities_device(cols, a["lens"], p["T"], a["t"], a["form"], out)
+            return [np.array(ctx.sort_last(), np.uint32)]
+        return run_mult
+    cap = sp.outs[0][1]                                              # the C entries themselves: the capacity is the Spec's, exactly
     if sp.op == "lincomb":
         ptrs, ln, J, cf, lwp, k_low = _open_args(sp, ins)
 
@@ -719,12 +727,14 @@ def figures_of(ctx):
     return ctx.poly_last()[1:] + ctx.sort_last()
 
 
-def scenario9():
-    case = cases.scenario9()
+def lanes_with_own_figures(case, rounds):
+    """contexts A and B with their lists: (lanes, alone, lists), alone[name][k] = the figures call k leaves when its context is
+    alone; after every later call the context must hold exactly those"""
     lanes, alone, lists = [], {}, {}
     for name in ("A", "B"):
         c = new_ctx()
-        for opt, v in case["options"][name].items():
+        options = case.get("options", {}).get(name, {})
+        for opt, v in options.items():
             c.set_option(opt, v)
         calls = resident_calls(c, case[name], who="context %s: " % name)
         alone[name] = []
@@ -739,7 +749,13 @@ def scenario9():
                 need(got == alone[name][k], "context %s, %s: poly_last / sort_last %s are not this context's own %s" % (name, call.name, got, alone[name][k]))
             call.after = after
         lists[name] = calls
-        lanes.append(Lane("context %s %s" % (name, case["options"][name]), calls, ROUNDS[9][len(lanes)]))
+        lanes.append(Lane("context %s %s" % (name, options), calls, rounds[len(lanes)]))
+    return lanes, alone, lists
+
+
+def scenario9():
+    case = cases.scenario9()
+    lanes, alone, lists = lanes_with_own_figures(case, ROUNDS[9])
     differ = [k for k, (x, y) in enumerate(zip(alone["A"], alone["B"])) if x != y]
     sorts = [k for k, sp in enumerate(case["A"]) if sp.op == "sort"]
     need(len(differ) >= 4 and set(sorts) <= set(differ) and all(alone["A"][k][2:] != alone["B"][k][2:] for k in sorts),
@@ -845,11 +861,119 @@ def scenario13():
     a.close()
 
 
+# ---- scenarios 14-16: the multiplicity entry ------------------------------------------------------------------------------------------
+def scenario14():
+    case = cases.scenario14()
+    lanes, alone, lists = lanes_with_own_figures(case, ROUNDS[14])
+    # the figures the check tells apart: no two calls of a list leave the same ones, and three different sort_last stand side by
+    # side (64 passes of the full-width keys, 8 of A's keys that share their upper limbs, 4 of B's keys below 2^16)
+    for name in ("A", "B"):
+        need(len(set(alone[name])) == len(alone[name]), "context %s: two calls leave the same figures" % name, alone[name])
+    need(len({f[2:] for f in alone["A"] + alone["B"]}) >= 3 and alone["A"][2][2:] != alone["B"][2][2:] and alone["A"][0] == alone["B"][0],
+         "the two contexts leave figures the check could not tell apart", alone)
+    for name in ("A", "B"):                                            # ... and they are the reference's
+        for sp, got in zip(case[name], alone[name]):
+            if sp.op == "mult":
+                N, t, (pa, ps) = sum(sp.args["lens"]), sp.args["t"], sp.args["passes"]
+                want = (cases.logup_ref.logup_bytes(N, t, pa, ps), cases.logup_ref.field_mults(N, t), pa + ps, 2 * cases.logup_ref.MAX_PASSES - pa - ps)
+                need(got == want, "context %s, %s: figures %s, the reference's are %s" % (name, sp, got, want))
+    serial_then_concurrent(14, lanes)
+
+
+def scenario15():
+    case = cases.scenario15()
+    a, b = new_ctx(), new_ctx()
+    first = case["0"][0]
+    for sp in case["0"] + case["1"]:
+        need(sorted(sp.ins) == sorted(first.ins) and all(np.array_equal(sp.ins[k], first.ins[k]) for k in sp.ins), "the specs do not share their inputs")
+    shared = upload_inputs(a, first, KEEP)                             # uploaded once through A; both contexts read the same pointers
+    lanes = []
+    for k, c in enumerate((a, b)):
+        calls = [resident_call(c, sp, ins=shared, who="context %d: " % k) for sp in case[str(k)]]
+        lanes.append(Lane("context %d" % k, calls, ROUNDS[15][k]))
+    serial_then_concurrent(15, lanes)
+    for name, (buf, image) in shared.items():
+        need(np.array_equal(buf.download(np.uint8), image), "the shared input %s, or the zone behind it, was written" % name)
+    b.close(); a.close()
+
+
+def scenario16():
+    case = cases.scenario16()
+    a = new_ctx()
+    ins_a = [upload_inputs(a, sp, KEEP) for sp in case["A"]]
+    steps = [resident_call(a, sp, ins=ins, who="A: ") for sp, ins in zip(case["A"], ins_a)]
+    alone = []
+    for rnd in range(2):                                               # what each step leaves in A's context when A is alone
+        alone = []
+        for call in steps:
+            call.verify(call.fn())
+            alone.append(state_of(a))
+    bad = [k for k, sp in enumerate(case["A"]) if sp.error]
+    need(len(bad) == 4 and len({alone[k][0] for k in bad}) == 4 and all(alone[k][0] for k in bad), "alone: the failing calls do not leave four messages", alone)
+    for k in bad:
+        if case["A"][k].index is not None:
+            need(alone[k][1] == case["A"][k].index, "alone: last_bad_index %d after '%s'" % (alone[k][1], steps[k].name))
+
+    def a_fn(k):
+        def fn():
+            raw = steps[k].fn()
+            steps[k].verify(raw)                                       # status, index, the output (untouched when refused) against the reference
+            got = state_of(a)
+            need(got == alone[k], "A: after '%s' the context holds %s, alone it held %s" % (steps[k].name, got, alone[k]))
+            return []
+        return fn
+    calls_a = [Call("A step %d: %s" % (k, steps[k].name), "errors", a_fn(k), None) for k in range(len(steps))]
+    # B: a long-lived context first; in its last SHORT_LIVED rounds a context created and destroyed per round
+    rounds_b = ROUNDS[16][1]
+    long_lived = new_ctx()
+    box = {"round": -1, "ctx": long_lived, "own": False}
+    box["calls"] = [resident_call(long_lived, sp, who="B: ") for sp in case["B"]]
+
+    def enter():
+        box["round"] += 1
+        if box["round"] >= rounds_b - SHORT_LIVED:
+            box["ctx"], box["bufs"], box["own"] = new_ctx(), [], True
+            box["calls"] = [resident_call(box["ctx"], sp, keep=box["bufs"], who="B, short-lived context: ") for sp in case["B"]]
+        return []
+
+    def b_step(k):
+        def fn():
+            c = box["calls"][k]
+            raw = c.fn()
+            c.verify(raw)                                              # every one of B's results against the reference
+            got = state_of(box["ctx"])
+            need(int(raw[-1][0]) == 0 and got == ("", 0, 0), "B: a context that only made good calls returned status %d and holds" % int(raw[-1][0]), got)
+            return []
+        return fn
+
+    def leave():
+        if box["own"]:
+            for buf in box.pop("bufs"):
+                buf.free()
+            box.pop("calls"); box.pop("ctx").close()
+        return []
+    named = [("enter", enter)] + [("%s %s" % (sp.op, sp.note), b_step(k)) for k, sp in enumerate(case["B"])] + [("leave", leave)]
+    calls_b = [Call(nm, "lifetime", f, None) for nm, f in named]
+    for c in calls_a + calls_b:
+        c.ref = False                                                  # (nothing to compare: the step checks itself)
+    lanes = [Lane("A: good and failing calls", calls_a, ROUNDS[16][0]), Lane("B: good calls, then a context per round", calls_b, rounds_b)]
+    wall = run_concurrent(lanes)
+    need(box["round"] == rounds_b - 1 and box["own"] and "ctx" not in box, "B did not end on a short-lived context")
+    finish(16, lanes, wall)
+    for sp, ins in zip(case["A"], ins_a):
+        for name, (buf, image) in ins.items():
+            need(np.array_equal(buf.download(np.uint8), image), "A: %s (%s): the input %s, or the zone behind it, was written" % (sp.op, sp.note, name))
+    a.close(); long_lived.close()
+
+
+SHORT_LIVED = 10
 # rounds of each thread's list (chosen so that the threads of a scenario run about equally long: profiles/concurrency/NOTES.md)
 ROUNDS = {1: (40, 3), 2: (25, 25), 3: (10, 10, 10, 10), 4: (25, 25), 5: (12, 60), 6: (10, 30),
-          8: (90, 30), 9: (40, 35), 10: (15, 15, 15, 15), 11: (40, 40), 12: (26, 50), 13: (10, 43)}
+          8: (90, 30), 9: (40, 35), 10: (15, 15, 15, 15), 11: (40, 40), 12: (26, 50), 13: (10, 43),
+          14: (40, 40), 15: (30, 30), 16: (16, 30)}
 SCENARIOS = {1: scenario1, 2: scenario2, 3: scenario3, 4: scenario4, 5: scenario5, 6: scenario6, 7: scenario7,
-             8: scenario8, 9: scenario9, 10: scenario10, 11: scenario11, 12: scenario12, 13: scenario13}
+             8: scenario8, 9: scenario9, 10: scenario10, 11: scenario11, 12: scenario12, 13: scenario13,
+             14: scenario14, 15: scenario15, 16: scenario16}
 
 if __name__ == "__main__":
     which = int(sys.argv[2])

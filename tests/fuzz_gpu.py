@@ -15,11 +15,12 @@ the C ABI and compares with a reference that is not the library.  The families (
     fraction_sums     chained running sums of fractions against rhs_ref.fraction_sums
     regfn             RegularFunction::ev against big-integer Horner, L(f) against rhs_ref.L
     lhs_witness       compute_lhs_witness in full: host entry == device entry, the carry, the functions
-    poly, domain, gate, column, perm, lookup
+    poly, domain, gate, column, perm, lookup, open, logup
                       the resident polynomial entries (tests/fuzz_resident.py): a case is a chain of 3 to 8 calls in a drawn
                       order -- fft / kate_division / poly_mul; coset transforms, coeff_to_extended, extended_to_coeff; random
                       gate programs; column a and its RLC cells; fraction and permutation products with planted zero
-                      denominators; sort_field and lookup_permute with planted missing values -- every call compared at once
+                      denominators; sort_field and lookup_permute with planted missing values; poly_lincomb, poly_divide_roots
+                      and open_quotient; lookup_multiplicities with planted missing values -- every call compared at once
                       with the references of the entries' own test modules, behind 0xFF-filled outputs.  These entries keep
                       state between calls (the shared twiddle table, the re-carved arenas, the words a call resets), which
                       the chains and the mix with every other family on one context exercise
@@ -65,7 +66,8 @@ NAMES = list(OPTION_DRAWS)
 # family -> probability; what is left goes to the two oldest families, msm : lhs = 3 : 1
 FAMILY_P = [("witness", 0.12), ("scalar_witness", 0.06), ("fixed", 0.08), ("rhs", 0.04), ("fraction_sums", 0.03), ("regfn", 0.04),
             ("lhs_witness", 0.03),
-            ("poly", 0.04), ("domain", 0.04), ("gate", 0.03), ("column", 0.03), ("perm", 0.04), ("lookup", 0.04)]
+            ("poly", 0.04), ("domain", 0.04), ("gate", 0.03), ("column", 0.03), ("perm", 0.04), ("lookup", 0.04),
+            ("open", 0.03), ("logup", 0.03)]
 NEW_FAMILIES = ("fixed", "rhs", "fraction_sums", "regfn", "lhs_witness")
 RESIDENT_FAMILIES = fuzz_resident.FAMILIES      # appended to FAMILY_P: the intervals of the families before them stay where they were
 LAST_KINDS = {}        # kinds_seen of the last main() call

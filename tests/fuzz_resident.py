@@ -5,17 +5,27 @@
     column    column_a and poly_rlc on synthetic witness lengths against tests/column_ref.py
     perm      fraction_products and permutation_product against tests/perm_ref.py, planted zero denominators
     lookup    sort_field and lookup_permute against tests/lookup_ref.py, planted missing values
+    open      poly_lincomb, poly_divide_roots and open_quotient against tests/open_ref.py: ragged and empty polynomials, equal and
+              zero roots, exact and inexact dividends, either form, option open_group drawn per step, divisions whose stages lie
+              on both sides of the one-segment-per-thread limit of k_kd_scan
+    logup     lookup_multiplicities against tests/logup_ref.py: ragged and NULL columns, tables laden with duplicates, a planted
+              missing value with a good call behind it in the same chain
 These entries keep state between calls -- the twiddle table five of them share, the arenas poly_ws and poly_stage every call
-carves anew, the words a call must reset -- so a case is not one call but a chain of 3 to 8 steps in a drawn order, on the
-soak's one long-lived context and under its drawn options.
+carves anew, the words a call must reset, the figures poly_last and sort_last that several families record into -- so a case is
+not one call but a chain of 3 to 8 steps in a drawn order, on the soak's one long-lived context and under its drawn options.
 
 draw(family, rng) is a pure function of the generator it is given: the inputs of every step and what the step must give,
 computed by the references, no context involved (tests/test_fuzz_cases.py draws cases without a GPU).  run(...) executes the
 steps through the device entries, or their host twins when the case's host_entry flag says so, and compares every step at once,
-byte for byte; every device output is 0xFF-filled with a zone of ZONE bytes behind it, checked after the step."""
+byte for byte; every device output is 0xFF-filled with a zone of ZONE bytes behind it, checked after the step.
+
+soak(family, seconds, seed) is the time-bound loop of one family alone on a context of its own (tests/fuzz_open.py and
+tests/fuzz_logup.py are its command lines): case k is drawn from case_rng(seed, k), and a failure prints the
+`seed=... case=...` line that draws it again."""
 import ctypes
 import hashlib
 import random
+import time
 
 import numpy as np
 
@@ -26,13 +36,15 @@ from oracle.divisor import PolyRing, best_fft
 import column_ref
 import domain_ref
 import gate_ref
+import logup_ref
 import lookup_ref
+import open_ref
 import perm_ref
 import poly_ref
 
-FAMILIES = ("poly", "domain", "gate", "column", "perm", "lookup")
+FAMILIES = ("poly", "domain", "gate", "column", "perm", "lookup", "open", "logup")
 P = pyref.R_BN254
-assert P == perm_ref.P == lookup_ref.P == pyref.GRUMPKIN.fp
+assert P == perm_ref.P == lookup_ref.P == logup_ref.P == pyref.GRUMPKIN.fp
 R = 1 << 256
 RI = pow(R, -1, P)
 TOP = 0x30644E72E131A029            # top limb of r: a smaller top limb makes any four limbs canonical
@@ -49,7 +61,9 @@ KD_BLOCK = 256 * KD_S               # coefficients one block of the quotient's k
 LIMITS = {"fft_logn": 26, "mul_len": 1 << 26, "kate_len": 1 << 26, "ext_logn": 26, "ext_logm": 4, "ext_log": 28,
           "gate_code": gate_ref.MAX_CODE, "gate_table": gate_ref.MAX_TABLE, "gate_cols": gate_ref.MAX_COLS, "gate_depth": gate_ref.MAX_DEPTH,
           "perm_logn": perm_ref.MAX_LOGN, "perm_cols": perm_ref.MAX_COLS, "factors": perm_ref.MAX_FACTORS, "lookup_n": lookup_ref.MAX_N,
-          "column_rows": 1 << 28}
+          "column_rows": 1 << 28, "open_polys": _lib.LEMSM_OPEN_MAX_POLYS, "open_roots": _lib.LEMSM_OPEN_MAX_ROOTS, "open_len": 1 << 28,
+          "logup_cols": logup_ref.MAX_COLS, "logup_rows": 1 << 28}
+assert open_ref.MAX_ROOTS == _lib.LEMSM_OPEN_MAX_ROOTS and logup_ref.MAX_COLS == 16 and logup_ref.MAX_N == 1 << 28
 
 
 # ---- helpers -------------------------------------------------------------------------------------------------------------------
@@ -678,6 +692,273 @@ def _run_pair(ctx, cs, k, st):
         cs.mismatch("step %d %s: passes (run, skipped) = %s, expected %d run" % (k, st.op, ctx.sort_last(), st.passes))
 
 
+# ---- open ----------------------------------------------------------------------------------------------------------------------
+OPEN_MAX_LEN = 1 << 12
+KD_ONE_EACH = KD_S * poly_ref.KD_CHUNKS            # 16384 coefficients: above it a thread of k_kd_scan owns more than one segment
+P_NEAR_ONE_EACH = 0.125                            # per division step: a length in [KD_ONE_EACH - 8, KD_ONE_EACH + 9]
+
+
+def _open_length(rng):
+    """log-uniform up to OPEN_MAX_LEN, with the lengths around a block of 256 threads and the empty polynomial over-represented"""
+    r = rng.random()
+    if r < 0.1:
+        return 0
+    if r < 0.3:
+        return int(_pick(rng, [1, 2, 255, 256, 257, 511, 512, 513]))
+    return min(OPEN_MAX_LEN, int(2 ** rng.uniform(0, 12)))
+
+
+def _open_divide_length(rng):
+    return int(rng.integers(KD_ONE_EACH - 8, KD_ONE_EACH + 10)) if rng.random() < P_NEAR_ONE_EACH else _open_length(rng)
+
+
+def _open_scalar(rng):
+    r = rng.random()
+    return 0 if r < 0.1 else 1 if r < 0.15 else P - 1 if r < 0.2 else _fe_int(rng)
+
+
+def _open_roots(rng, k):
+    z = [_fe_int(rng) for _ in range(k)]
+    for i in range(1, k):
+        r = rng.random()
+        if r < 0.2:
+            z[i] = z[int(rng.integers(0, i))]
+        elif r < 0.3:
+            z[i] = 0
+    return z
+
+
+def straddles_one_each(length, k):
+    """the stages of a division of `length` coefficients by k roots (lengths length, length - 1, ..) lie on both sides of KD_ONE_EACH"""
+    return length > KD_ONE_EACH >= length - (k - 1)
+
+
+def _open_figures(step_op, lens, k_low, k, n_out, form):
+    """(bytes, field_mults) of lemsm_poly_last behind the step, from open_ref.plan (tests/test_open_plan.py holds it against
+    lemsm_open_plan): a division alone has no combination in it; the canonical form reads and writes the quotient once more"""
+    plan = open_ref.plan(lens, k_low, k)
+    by, fm = plan["bytes"], plan["field_mults"]
+    if step_op == "divide":
+        by, fm = by - 64 * lens[0], fm - lens[0]
+    if k and form == CANON:
+        by, fm = by + 64 * n_out, fm + n_out
+    return by, fm
+
+
+def _gen_open(rng, op):
+    form = CANON if rng.random() < 0.4 else MONT
+    group = int(_pick(rng, [0, 0, 0, 1, 2, 3, 4, 5]))
+    if op == "divide":
+        k = int(rng.integers(1, open_ref.MAX_ROOTS + 1))
+        roots = _open_roots(rng, k)
+        n = max(_open_divide_length(rng), k)
+        exact = bool(rng.random() < 0.5 and n > k)
+        a = _ints(_rand(rng, n - k if exact else n))
+        for z in roots if exact else ():
+            a = open_ref.poly_mul_linear(a, z, P)
+        polys, coeffs, low = [_arr(a)], [1], []
+        q, rems = open_ref.divide_roots(a, roots, P)
+        assert not exact or not any(rems)
+    else:
+        J = int(rng.integers(1, 13))
+        polys = [_rand(rng, _open_length(rng) if rng.random() < 0.7 else int(rng.integers(0, 64))) for _ in range(J)]
+        coeffs = [_open_scalar(rng) for _ in range(J)]
+        low = _ints(_rand(rng, int(_pick(rng, [0, 0, 1, 2, 3, 8]))))
+        roots, exact = [], False
+        if op == "quotient":
+            k = int(rng.integers(1, open_ref.MAX_ROOTS + 1))
+            if rng.random() < P_NEAR_ONE_EACH:
+                polys[int(rng.integers(0, J))] = _rand(rng, int(rng.integers(KD_ONE_EACH - 8, KD_ONE_EACH + 10)))
+            if max([p.shape[0] for p in polys] + [len(low)]) < k:
+                polys[0] = _rand(rng, k + int(rng.integers(0, 40)))
+            roots = _open_roots(rng, k)
+            ip = [_ints(p) for p in polys]
+            if rng.random() < 0.5 and len(low) <= k <= max(len(p) for p in ip):      # low = the combination's remainder: the division is exact
+                comb = open_ref.lincomb(ip, coeffs, [], P)
+                back = open_ref.divide_roots(comb, roots, P)[0]
+                for z in roots:
+                    back = open_ref.poly_mul_linear(back, z, P)
+                low, exact = [(c - b) % P for c, b in zip(comb[:k], back[:k])], True
+            q, rems = open_ref.open_quotient(ip, coeffs, low, roots, P)
+            assert not exact or not any(rems)
+        else:
+            form = MONT
+            q, rems = open_ref.lincomb([_ints(p) for p in polys], coeffs, low, P), []
+    lens, k = [p.shape[0] for p in polys], len(roots)
+    n = max(lens + [len(low)])
+    want = [v * RI % P for v in q] if (k and form == CANON) else q
+    sizes = [("open_polys", len(polys)), ("open_roots", k), ("open_roots", len(low))] + [("open_len", v) for v in lens]
+    note = "lens=%s k_low=%d k=%d%s form=%d group=%d" % (lens, len(low), k, " exact" if exact else "", form, group)
+    return Step(op, note, sizes, polys=polys, lens=lens, coeffs=_mont(coeffs), low=_arr(low) if low else None, roots=_mont(roots), k=k, form=form,
+                group=group, n_out=len(want), want=_arr(want).tobytes(), want_rem=_arr(rems).tobytes(), exact=exact, empty=lens.count(0),
+                straddle=bool(k) and straddles_one_each(n, k), figures=_open_figures(op, lens, len(low), k, len(want), form))
+
+
+def _draw_open(rng, nsteps):
+    return [_gen_open(rng, str(_pick(rng, ["lincomb", "divide", "quotient"]))) for _ in range(nsteps)]
+
+
+def _run_open(ctx, cs, k, st):
+    """the C entries themselves: the capacity is the result's length, exactly (one element where the host twin needs a pointer)"""
+    lib, J, nk, n_out = ctx.lib, len(st.polys), st.k, st.n_out
+    ln = np.array(st.lens, np.uintp)
+    lwp, k_low = (st.low.ctypes.data, st.low.shape[0]) if st.low is not None else (None, 0)
+    rem = np.full((max(nk, 1), 4), 0xFFFFFFFFFFFFFFFF, np.uint64)
+    n, bad = ctypes.c_size_t(n_out), ctypes.c_size_t(0)
+    rt = st.roots.ctypes.data if nk else None
+    ctx.set_option("open_group", st.group)
+    try:
+        if cs.host_entry:
+            out = np.zeros((max(n_out, 1), 4), np.uint64)
+            hp = (ctypes.c_void_p * J)(*[a.ctypes.data if a.shape[0] else None for a in st.polys])
+            before = [a.tobytes() for a in st.polys]
+            if st.op == "lincomb":
+                rc = lib.lemsm_poly_lincomb(ctx.h, hp, ln.ctypes.data, J, st.coeffs.ctypes.data, lwp, k_low, out.ctypes.data, out.shape[0], ctypes.byref(n))
+            elif st.op == "divide":
+                rc = lib.lemsm_poly_divide_roots(ctx.h, st.polys[0].ctypes.data, st.lens[0], rt, nk, st.form, out.ctypes.data, out.shape[0], rem.ctypes.data,
+                                                 ctypes.byref(bad))
+            else:
+                rc = lib.lemsm_open_quotient(ctx.h, hp, ln.ctypes.data, J, st.coeffs.ctypes.data, lwp, k_low, rt, nk, st.form, out.ctypes.data, out.shape[0],
+                                             ctypes.byref(n), rem.ctypes.data, ctypes.byref(bad))
+            ctx._check(rc, bad.value)
+            _same(cs, k, st, out[:n_out].tobytes(), st.want)
+            if [a.tobytes() for a in st.polys] != before:
+                cs.mismatch("step %d %s (%s): an operand changed" % (k, st.op, st.note))
+        else:
+            bufs = [_filled(ctx, a.shape[0], a) if a.shape[0] else None for a in st.polys]
+            d_out = _filled(ctx, n_out)
+            dp = (ctypes.c_void_p * J)(*[b.ptr if b is not None else None for b in bufs])
+            try:
+                if st.op == "lincomb":
+                    rc = lib.lemsm_poly_lincomb_device(ctx.h, dp, ln.ctypes.data, J, st.coeffs.ctypes.data, lwp, k_low, d_out.ptr, n_out, ctypes.byref(n))
+                elif st.op == "divide":
+                    rc = lib.lemsm_poly_divide_roots_device(ctx.h, bufs[0].ptr, st.lens[0], rt, nk, st.form, d_out.ptr, n_out, rem.ctypes.data, ctypes.byref(bad))
+                else:
+                    rc = lib.lemsm_open_quotient_device(ctx.h, dp, ln.ctypes.data, J, st.coeffs.ctypes.data, lwp, k_low, rt, nk, st.form, d_out.ptr, n_out,
+                                                        ctypes.byref(n), rem.ctypes.data, ctypes.byref(bad))
+                ctx._check(rc, bad.value)
+            except Exception:
+                for b in bufs + [d_out]:
+                    if b is not None:
+                        b.free()
+                raise
+            _payload(cs, k, st, d_out, st.want)
+            for b, a in zip(bufs, st.polys):                       # the operands and their zones are as they were uploaded
+                if b is not None:
+                    _payload(cs, k, st, b, a.tobytes())
+    finally:
+        ctx.set_option("open_group", 0)
+    if n.value != n_out:
+        cs.mismatch("step %d %s (%s): length %d reported, the reference's is %d" % (k, st.op, st.note, n.value, n_out))
+    if rem[:nk].tobytes() != st.want_rem:
+        cs.mismatch("step %d %s (%s): the remainders differ from the reference" % (k, st.op, st.note))
+    plan = api.open_plan(st.lens, k_low, nk)                       # (pure host)
+    if plan["len_out"] != n_out or ctx.poly_last()[1:] != st.figures:
+        cs.mismatch("step %d %s (%s): plan %s, poly_last %s, the reference prices the call at %s" % (k, st.op, st.note, plan, ctx.poly_last()[1:], st.figures))
+    want_plan = _open_figures("quotient", st.lens, k_low, nk, n_out, MONT)
+    if (plan["bytes"], plan["field_mults"]) != want_plan:
+        cs.mismatch("step %d %s (%s): open_plan %s, the reference's is %s" % (k, st.op, st.note, plan, want_plan))
+
+
+# ---- logup ---------------------------------------------------------------------------------------------------------------------
+LOGUP_MAX_ROWS = 1 << 12
+LOGUP_COLS = (1, 1, 2, 3, 5, 16)
+
+
+def _logup_length(rng):
+    """log-uniform up to LOGUP_MAX_ROWS, with the lengths around a tile of the sort and the empty column over-represented"""
+    r = rng.random()
+    if r < 0.2:
+        return 0
+    if r < 0.4:
+        return int(_pick(rng, [1, 2, 255, 256, 257, 1023, 1024, 1025, 2049]))
+    return min(LOGUP_MAX_ROWS, int(2 ** rng.uniform(0, 12)))
+
+
+def _logup_pool(rng):
+    """small values, values that share their upper bytes, or full-width ones; 0, 1, r - 1 beside them"""
+    kind, size = rng.random(), int(_pick(rng, [1, 2, 5, 40, 700]))
+    if kind < 0.3:
+        vals = [int(rng.integers(0, 1 << 16)) for _ in range(size)]
+    elif kind < 0.5:
+        top = _fe_int(rng) & ~0xFFFF
+        vals = [(top | int(rng.integers(0, 1 << 16))) % P for _ in range(size)]
+    else:
+        vals = _ints(_rand(rng, size))
+    return vals + [0, 1, P - 1][:int(rng.integers(0, 4))]
+
+
+def _gen_mult(rng, plant):
+    pool = _logup_pool(rng)
+    t = _logup_length(rng)
+    if plant and rng.random() < 0.8:
+        t = max(t, 1)                                              # (a fifth of the planted steps may meet an empty table)
+    table = [pool[int(i)] for i in rng.integers(0, len(pool), t)]
+    k = int(_pick(rng, LOGUP_COLS))
+    lens = [_logup_length(rng) if t else 0 for _ in range(k)]
+    inputs = [[table[int(i)] for i in rng.integers(0, t, n)] if n else [] for n in lens]
+    if plant:
+        if not sum(lens):
+            inputs[int(rng.integers(0, k))] = _ints(_rand(rng, 1 + _logup_length(rng)))
+        have = set(table)
+        gone = [v for v in (_fe_int(rng), int(rng.integers(0, 1 << 17)), 2, P - 2) if v not in have]
+        filled = [c for c in inputs if c]
+        for v in gone[:int(rng.integers(1, 3))]:
+            for _ in range(int(rng.integers(1, 4))):
+                col = filled[int(rng.integers(0, len(filled)))]
+                col[int(rng.integers(0, len(col)))] = v
+    lens = [len(c) for c in inputs]
+    N, form = sum(lens), int(_pick(rng, [MONT, CANON]))
+    pa = len(logup_ref.live_passes(logup_ref.concat(inputs))) if N else 0
+    ps = len(logup_ref.live_passes(table)) if N and t else 0
+    kw = dict(inputs=[_mont(c) for c in inputs], lens=lens, table=_mont(table), t=t, form=form, empty=lens.count(0),
+              passes=(pa + ps, logup_ref.sorts(N, t) * logup_ref.MAX_PASSES - pa - ps), figures=(logup_ref.logup_bytes(N, t, pa, ps), logup_ref.field_mults(N, t)))
+    note = "lens=%s t=%d pool=%d form=%d" % (lens, t, len(set(pool)), form)
+    sizes = [("logup_cols", k), ("logup_rows", t), ("logup_rows", N)]
+    pos = logup_ref.missing_position(inputs, table)
+    assert (pos is not None) == plant
+    if plant:
+        return Step("mult", note, sizes, error=True, index=pos, want=b"", **kw)
+    m = logup_ref.multiplicities(inputs, table)
+    return Step("mult", note, sizes, want=(_mont(m) if form == MONT else _arr(m)).tobytes(), **kw)
+
+
+def _draw_logup(rng, nsteps):
+    """one step of the case may get the planted missing value; never the last one: a good call follows it in the same chain"""
+    planted = int(rng.integers(0, nsteps - 1)) if rng.random() < P_MISSING_VALUE else -1
+    return [_gen_mult(rng, k == planted) for k in range(nsteps)]
+
+
+def _run_mult(ctx, cs, k, st):
+    if cs.host_entry:
+        try:
+            got = ctx.lookup_multiplicities(st.inputs, st.table, st.form)
+        except api.NotInTable as e:
+            _error(cs, k, st, e.index)
+        else:
+            _no_error(cs, k, st)
+            _same(cs, k, st, got.tobytes(), st.want)
+    else:
+        bufs = [_filled(ctx, c.shape[0], c) if c.shape[0] else None for c in st.inputs]
+        d_t = _filled(ctx, st.t, st.table) if st.t else None
+        out = _filled(ctx, st.t)
+        try:
+            ctx.lookup_multiplicities_device([b.ptr if b else None for b in bufs], st.lens, d_t.ptr if d_t else None, st.t, st.form, out)
+        except api.NotInTable as e:
+            _error(cs, k, st, e.index)
+            if ctx.lib.lemsm_last_bad_index(ctx.h) != st.index:
+                cs.mismatch("step %d %s (%s): last_bad_index %d, the reference's is %d" % (k, st.op, st.note, ctx.lib.lemsm_last_bad_index(ctx.h), st.index))
+        else:
+            _no_error(cs, k, st)
+        finally:
+            _payload(cs, k, st, out, st.want)                      # (a refusal: the whole output and its zone are still 0xFF)
+            for b, a in zip(bufs + [d_t], st.inputs + [st.table]):
+                if b is not None:
+                    _payload(cs, k, st, b, a.tobytes())
+    if ctx.sort_last() != st.passes or ctx.poly_last()[1:] != st.figures:
+        cs.mismatch("step %d %s (%s): sort_last %s, poly_last %s; the reference gives %s, %s" % (k, st.op, st.note, ctx.sort_last(), ctx.poly_last()[1:], st.passes, st.figures))
+
+
 # ---- the comparisons -----------------------------------------------------------------------------------------------------------
 def _filled(ctx, n_elems, payload=None):
     """a device buffer of n_elems elements + a zone, all 0xFF, with `payload` (an (n, 4) array) at its start"""
@@ -717,9 +998,11 @@ def _no_error(cs, k, st):
         cs.mismatch("step %d %s (%s): accepted, the reference refuses index %d" % (k, st.op, st.note, st.index))
 
 
-DRAW = {"poly": _draw_poly, "domain": _draw_domain, "gate": _draw_gate, "column": _draw_column, "perm": _draw_perm, "lookup": _draw_lookup}
+DRAW = {"poly": _draw_poly, "domain": _draw_domain, "gate": _draw_gate, "column": _draw_column, "perm": _draw_perm, "lookup": _draw_lookup,
+        "open": _draw_open, "logup": _draw_logup}
 RUN = {"fft": _run_fft, "kate": _run_kate, "mul": _run_mul, "coset": _run_coset, "c2e": _run_c2e, "e2c": _run_e2c, "gate": _run_gate,
-       "column": _run_column, "rlc": _run_rlc, "fp": _run_fp, "pp": _run_pp, "sort": _run_sort, "pair": _run_pair}
+       "column": _run_column, "rlc": _run_rlc, "fp": _run_fp, "pp": _run_pp, "sort": _run_sort, "pair": _run_pair,
+       "lincomb": _run_open, "divide": _run_open, "quotient": _run_open, "mult": _run_mult}
 
 
 def case_rng(seed, index):
@@ -736,3 +1019,55 @@ def run(ctx, cs, steps):
     """every step on ctx, compared at once; cs (fuzz_gpu.Case) names the case on a mismatch"""
     for k, st in enumerate(steps):
         RUN[st.op](ctx, cs, k, st)
+
+
+# ---- one family alone --------------------------------------------------------------------------------------------------------------
+class Mismatch(AssertionError):
+    pass
+
+
+class ChainCase:
+    """what soak() hands to run() in place of fuzz_gpu.Case: the line that draws the case again; a mismatch raises"""
+
+    def __init__(self, seed, index, family, opts, host_entry, desc):
+        self.seed, self.index, self.family, self.opts, self.host_entry, self.desc = seed, index, family, opts, host_entry, desc
+
+    def line(self):
+        return "seed=%d case=%d %s %s host_entry=%s opts=%s" % (self.seed, self.index, self.family, self.desc, self.host_entry, self.opts)
+
+    def mismatch(self, what):
+        print("MISMATCH %s: %s" % (self.line(), what), flush=True)
+        raise Mismatch("seed=%d case=%d %s: %s" % (self.seed, self.index, self.family, what))
+
+
+def soak_case(family, seed, index):
+    """(steps, options, host_entry) of case `index` of soak(family, .., seed): a function of (family, seed, index) alone"""
+    rng = case_rng(seed, index)
+    steps = draw(family, rng)
+    return steps, {"ws_canary": int(rng.random() < 0.3)}, bool(rng.random() < 0.3)
+
+
+def soak(family, seconds, seed, ctx=None):
+    """cases of `family` completed in `seconds`, on `ctx` or a context of its own"""
+    own = ctx is None
+    ctx = ctx or api.Context(0)
+    done, end = 0, time.monotonic() + seconds
+    try:
+        while time.monotonic() < end:
+            steps, opts, host_entry = soak_case(family, seed, done)
+            cs = ChainCase(seed, done, family, opts, host_entry, describe(steps))
+            for name, value in opts.items():
+                ctx.set_option(name, value)
+            try:
+                run(ctx, cs, steps)
+            except Mismatch:
+                raise
+            except Exception as ex:
+                print("EXCEPTION %r %s" % (ex, cs.line()), flush=True)
+                raise
+            done += 1
+    finally:
+        ctx.set_option("ws_canary", 0)
+        if own:
+            ctx.close()
+    return done

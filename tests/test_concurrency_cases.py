@@ -1,19 +1,21 @@
-"""The inputs and expected values of the concurrency scenarios 8 to 13 (tests/concurrency_cases.py) without a GPU: every
-builder gives the same case when called again, the references refuse every planted failure of scenario 12 at the index the
-scenario expects and accept every other call, the two sort columns of scenario 9 run different numbers of passes, and the
-opening of scenario 8 has terms of equal length on both sides of a group of five."""
+"""The inputs and expected values of the concurrency scenarios 8 to 16 (tests/concurrency_cases.py) without a GPU: every
+builder gives the same case when called again, the references refuse every planted failure of scenarios 12 and 16 at the index
+the scenario expects and accept every other call, the two sort columns of scenario 9 run different numbers of passes, the
+opening of scenario 8 has terms of equal length on both sides of a group of five, the multiplicity calls of scenario 14 have
+the sizes and the pass counts the scenario is about, and those of scenario 15 share their inputs."""
 import time
 
 import pytest
 
 import concurrency_cases as cc
+import logup_ref
 import lookup_ref
 import open_ref
 import perm_ref
 
 P, RI = cc.P, cc.RI
 BUILDERS = {"8": cc.scenario8, "9": cc.scenario9, "10": lambda: {str(k): cc.scenario10(k) for k in range(4)}, "11": lambda: {"shared": cc.scenario11()},
-            "12": cc.scenario12, "13": cc.scenario13}
+            "12": cc.scenario12, "13": cc.scenario13, "14": cc.scenario14, "15": cc.scenario15, "16": cc.scenario16}
 
 
 def _specs(case):
@@ -29,7 +31,7 @@ def built():
 
 
 def test_builders_are_deterministic_and_quick(built):
-    print("scenarios 8-13 built in %.2f s" % built["seconds"])
+    print("scenarios 8-16 built in %.2f s" % built["seconds"])
     assert built["seconds"] < 30                                            # (measured: profiles/concurrency/NOTES.md)
     for name, fn in BUILDERS.items():
         again = _specs(fn())
@@ -139,3 +141,77 @@ def test_open_case_of_scenario_8(built):
     assert (a["mul7"].args["la"], a["mul7"].args["lb"]) == (31, 40) and a["fft0"].args["logn"] == 12
     b = {s.op: s for s in built["8"]["B"]}
     assert b["fp"].args["n"] == 8193 and b["sort"].args["n"] == 5000 and b["pair"].args["n"] == 4096 and b["fsums"].args["n"] == 4097
+
+
+def _mult_columns(sp):
+    """(the columns the call takes, the table) of a multiplicity Spec, standard form"""
+    cols = [[v * RI % P for v in _ints_of(sp, name)] if name else [] for name in sp.args["cols"]]
+    return cols, [v * RI % P for v in _ints_of(sp, "T")]
+
+
+def test_multiplicity_calls_of_scenario_14(built):
+    a, b = built["14"]["A"], built["14"]["B"]
+    assert [sp.op for sp in a] == ["mult", "pair", "sort"] and [sp.op for sp in b] == ["mult", "quotient", "mult"]
+    assert not any(sp.error for sp in a + b)
+    ma, mb, small = a[0], b[0], b[2]
+    assert ma.args["lens"] == mb.args["lens"] and len(ma.args["lens"]) == 3 and sum(ma.args["lens"]) == 4099 and len(set(ma.args["lens"])) == 3
+    assert ma.args["t"] == mb.args["t"] == 1025 and (ma.args["form"], mb.args["form"]) == (cc.MONT, cc.CANON)
+    assert sorted(ma.ins) == sorted(mb.ins) and all(ma.ins[k].tobytes() == mb.ins[k].tobytes() for k in ma.ins)      # the same inputs
+    cols, table = _mult_columns(ma)
+    assert len(set(table)) < len(table) and [len(c) for c in cols] == ma.args["lens"]                              # duplicates in the table
+    m = logup_ref.multiplicities(cols, table)
+    assert sum(m) == 4099 and cc._mont(m).tobytes() == ma.outs[0][2] and cc._arr(m).tobytes() == mb.outs[0][2] != ma.outs[0][2]
+    assert ma.args["passes"] == (logup_ref.MAX_PASSES, logup_ref.MAX_PASSES)                                        # full-width keys: no pass skipped
+    cols, table = _mult_columns(small)
+    assert max(table) < 1 << 16 and small.args["passes"] == (2, 2) and None in small.args["cols"]                  # keys below 2^16, a NULL column
+    assert list(small.small[0]) == [4, 2 * logup_ref.MAX_PASSES - 4] and list(ma.small[0]) == [2 * logup_ref.MAX_PASSES, 0]
+    assert list(a[2].small[0]) == [8, logup_ref.MAX_PASSES - 8]                                                     # A's sort: upper limbs shared
+
+
+def test_shared_inputs_of_scenario_15(built):
+    specs = built["15"]["0"] + built["15"]["1"]
+    first = specs[0]
+    assert sorted(first.ins) == ["T", "c0", "c1", "c3", "c4", "c5"]                                                 # (column 2 has no rows)
+    subsets = []
+    for sp in specs:
+        assert sorted(sp.ins) == sorted(first.ins) and all(sp.ins[k].tobytes() == first.ins[k].tobytes() for k in sp.ins)
+        cols, table = _mult_columns(sp)
+        m = logup_ref.multiplicities(cols, table)
+        assert sum(m) == sum(sp.args["lens"]) and (cc._mont(m) if sp.args["form"] == cc.MONT else cc._arr(m)).tobytes() == sp.outs[0][2]
+        subsets.append(tuple(sp.args["cols"]))
+    assert len(set(subsets)) == 4 and any(None in s for s in subsets)                                               # different subsets, a NULL column among them
+    assert {sp.args["form"] for sp in built["15"]["0"]} == {sp.args["form"] for sp in built["15"]["1"]} == {cc.MONT, cc.CANON}
+    assert len({sp.outs[0][2] for sp in specs}) == 4
+
+
+def test_planted_failures_of_scenario_16(built):
+    a, b = built["16"]["A"], built["16"]["B"]
+    assert not any(sp.error for sp in b) and all(sp.op == "mult" for sp in a + b) and len(b) == 3
+    assert [sp.error for sp in a] == [False, True, False, True, False, True, False, True, False]
+    one, later, k17, overlap = [sp for sp in a if sp.error]
+    # one missing value
+    cols, table = _mult_columns(one)
+    assert [(c, r) for c, col in enumerate(cols) for r, v in enumerate(col) if v not in set(table)] == [(0, 123)]
+    assert one.index == logup_ref.missing_position(cols, table) == 123 and one.status == cc.NOT_IN_TABLE
+    # three missing values: the smallest one in column 2, behind a larger one in column 0 -- the position lies in a later column
+    cols, table = _mult_columns(later)
+    gone = [(c, r, v) for c, col in enumerate(cols) for r, v in enumerate(col) if v not in set(table)]
+    assert [(c, r) for c, r, _ in gone] == [(0, 5), (2, 77), (3, 299)] and min(gone, key=lambda g: g[2])[:2] == (2, 77)
+    lens = later.args["lens"]
+    assert lens[1] == 0 and later.args["cols"][1] is None
+    assert later.index == logup_ref.missing_position(cols, table) == lens[0] + lens[1] + 77 and later.status == cc.NOT_IN_TABLE
+    with pytest.raises(logup_ref.NotInTable) as e:
+        logup_ref.multiplicities(cols, table)
+    assert e.value.index == later.index
+    # k = 17: one column above the limit, every pointer and length legal
+    assert len(k17.args["lens"]) == len(k17.args["cols"]) == logup_ref.MAX_COLS + 1 and k17.status == cc.BAD_ARG and k17.index is None
+    assert all(n == 1 for n in k17.args["lens"]) and all(k17.ins[name].shape[0] >= 1 for name in k17.args["cols"])
+    assert logup_ref.plan(k17.args["lens"], k17.args["t"]) is None and logup_ref.plan(k17.args["lens"][:16], k17.args["t"]) is not None
+    # the output one element into the table: t elements from there end inside the table's buffer and its 4096-byte zone
+    name, at = overlap.args["out_at"]
+    assert name == "T" and 0 < at and 32 * at <= 4096 and overlap.ins["T"].shape[0] == overlap.args["t"] and overlap.status == cc.BAD_ARG
+    for k in range(1, len(a), 2):                                           # the good call behind every refusal
+        good = a[k + 1]
+        cols, table = _mult_columns(good)
+        assert not good.error and logup_ref.missing_position(cols, table) is None and len(good.outs[0][2]) == 32 * good.args["t"]
+        assert good.args["lens"] == a[0].args["lens"] and a[k].outs[0][2] == b""

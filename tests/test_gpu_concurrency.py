@@ -3,6 +3,8 @@ context serves one call at a time, distinct contexts may be used concurrently --
 than the process has hardware queues -- and device pointers may be read by several contexts at once.  Scenarios 1 to 7 run
 the MSM, witness and column entries, scenarios 8 to 13 the resident polynomial entries (fft to open_quotient) with the state
 they keep per context: the cached twiddle table, the regrown workspaces, the device error words, poly_last and sort_last.
+Scenarios 14 to 16 run the multiplicity entry (lookup_multiplicities), which carves the same workspace and records into the
+same sort_last, poly_last and bad_index as the sorts, the lookup and every polynomial entry.
 
 Each scenario runs in a fresh child interpreter (tests/concurrency_child.py, which documents how a scenario is run and what
 it compares): contexts on device 0, every expected value from the oracle before a thread starts, threading.Thread workers
@@ -162,4 +164,33 @@ def test_13_context_lifetime_beside_resident_calls():
     twiddle table, workspace and staging with it), 10 times, while another runs scenario 8's transform list"""
     res = _run(13)
     assert res["threads"] == 2 and res["rounds"][0] == 10
+    _overlapped(res)
+
+
+def test_14_multiplicities_side_by_side_in_different_states():
+    """thread A: lookup_multiplicities_device in Montgomery form over 3 ragged columns (N = 4099, t = 1025 with duplicates), a
+    lookup_permute_device, a sort_field_device; thread B: the same multiplicity inputs in canonical form, an
+    open_quotient_device, a multiplicity call over keys below 2^16 whose sorts skip 30 passes each; after every call poly_last
+    and sort_last of each context are those of the same call made alone, and they are the reference's"""
+    res = _run(14)
+    assert res["threads"] == 2 and res["serial_s"] is not None
+    _overlapped(res)
+
+
+def test_15_multiplicities_over_shared_read_only_residents():
+    """one resident table and one set of six input columns; two contexts compute m for different subsets of the columns, in
+    either form, against the same pointers into outputs of their own; the shared buffers and the zones behind them hold their
+    uploaded bytes at the end"""
+    res = _run(15)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_16_multiplicity_errors_stay_where_they_happen():
+    """thread A alternates good calls with a missing value, two missing values of which the smaller sits in a later column,
+    k = 17 and an output that overlaps the table: status, index, last_bad_index and last_error are its own call's after every
+    call, every refused call leaves its output and zone 0xFF, the good call behind a refusal is correct; thread B, good calls
+    only, never sees a status or a message, and in its last 10 rounds creates and destroys its context per round"""
+    res = _run(16)
+    assert res["threads"] == 2 and res["rounds"][1] >= 20
     _overlapped(res)

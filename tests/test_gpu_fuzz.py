@@ -3,7 +3,7 @@ input shapes (cancellation, doubling, identities), every tuning option incl. the
 with simulated ranks, divisor-witness forests and scalar-witness batches, fixed-base MSM under random table geometries and
 prefixes, the right-hand side (rhs, fraction_sums), RegularFunction::ev and L(f) on random forests (regfn) and
 compute_lhs_witness in full (lhs_witness), and chains of the resident polynomial entries (poly, domain, gate, column, perm,
-lookup: tests/fuzz_resident.py) -- every case against a reference that is not the library."""
+lookup, open, logup: tests/fuzz_resident.py) -- every case against a reference that is not the library."""
 import collections
 
 import pytest
@@ -19,8 +19,8 @@ def test_fuzz_slice(seed):
 
 
 # The family of case k depends on (seed, k) alone (fuzz_gpu.case_kinds, no GPU involved): seed 71 reaches the five newer
-# families within its first 24 cases -- fixed 3, rhs 2, lhs_witness 2, regfn 1, fraction_sums 1 beside msm 5, lhs 5,
-# witness 1, scalar_witness 1, poly 1, domain 1, gate 1.  The count-bound mode makes that hold whatever the machine's speed.
+# families within its first 24 cases -- fixed 3, rhs 2, lhs_witness 2, regfn 1, fraction_sums 1 beside lhs 5, msm 2, logup 2,
+# witness 1, scalar_witness 1, poly 1, domain 1, gate 1, open 1.  The count-bound mode makes that hold whatever the machine's speed.
 COUNT_SEED, COUNT_CASES = 71, 24
 
 
@@ -34,10 +34,10 @@ def test_fuzz_count_bound_reaches_every_family():
     assert sum(seen.values()) == COUNT_CASES
 
 
-# Seed 287 reaches the six resident families within its first 14 cases -- poly 2, domain 1, gate 1, column 1, perm 1, lookup 1 --
-# with msm 2, witness 2, lhs 1, regfn 1, fraction_sums 1 between them: their chains run on a context whose arenas and twiddle
-# table the older families have used in between.
-RESIDENT_SEED, RESIDENT_CASES = 287, 14
+# Seed 287 reaches the eight resident families within its first 18 cases -- poly 2, domain 2, gate 1, column 1, perm 1, lookup 1,
+# logup 1, open 1 (the last case) -- with msm 3, witness 2, lhs 1, regfn 1, fraction_sums 1 between them: their chains run on a
+# context whose arenas and twiddle table the older families have used in between.
+RESIDENT_SEED, RESIDENT_CASES = 287, 18
 
 
 def test_fuzz_count_bound_reaches_every_resident_family():

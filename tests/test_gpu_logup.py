@@ -11,14 +11,20 @@ Single-block stages and capped grids of the path, the size above which each take
 The join itself (k_lu_first, k_lu_flags, k_lu_count, k_lu_zero, k_lu_find_pos) has a thread per row on an uncapped grid and no
 scan: no threshold.  The thresholds are the library's own, so a change of either constant moves these tests with it."""
 import ctypes
+import functools
 import random
 
 import numpy as np
 import pytest
 
 from halo2_liam_eagen_msm_amd import _lib, api
+from oracle.divisor import best_fft
 
+import domain_ref
+import fuzz_resident as fr
 import logup_ref as ref
+import lookup_ref
+import open_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -345,6 +351,142 @@ def test_with_guards(canary):
     table = [2, 4, 6]
     _missing(canary, [[2, 4], [6, 5, 2]], table, 3)
     _missing(canary, [[8]], [], 0)
+
+
+# ---- behind other families on one context -----------------------------------------------------------------------------------------
+def _figures(c):
+    return {"sort": c.sort_last(), "poly": c.poly_last()[1:], "bad": int(c.lib.lemsm_last_bad_index(c.h))}
+
+
+@functools.lru_cache(maxsize=None)
+def _cross_family_steps():
+    """the ten calls of the test below, built once: (name, the figures the call records, fn(ctx) that makes the call and compares
+    it with its reference).  A refusal records sort_last, poly_last and last_bad_index; a good multiplicity, permute or sort
+    call sort_last and poly_last; a transform or an opening poly_last alone (the header defines last_bad_index after an error
+    status only, and no entry resets it)"""
+    rng = random.Random(9700)
+    nrng = np.random.default_rng(9700)
+    logn = 16
+    data = fr._rand(nrng, 1 << logn)
+    w = domain_ref.omega(logn)
+    spectrum = fr._ints(data)
+    best_fft(spectrum, w, logn, P)
+    want_fft = _arr(spectrum).tobytes()
+
+    def fft(c):
+        buf = c.to_device(data)
+        c.fft_device(buf.ptr, 1, logn, fr._fe(w), None)
+        assert buf.download(np.uint8).tobytes() == want_fft
+        buf.free()
+
+    def table_and_inputs(t, lens, distinct):
+        table = _table(rng, t, distinct)
+        return table, [[rng.choice(table) for _ in range(n)] for n in lens]
+
+    t1, in1 = table_and_inputs(300, [400, 0, 300], 120)
+    t4, in4 = table_and_inputs(300, [1, 699], 300)
+    t5, in5 = table_and_inputs(TILE + 3, [200, 500], 64)
+    gone = next(v for v in (rng.randrange(P) for _ in range(9)) if v not in set(t5))
+    in5[1][311] = gone
+    t8 = _table(rng, 257, 100)
+    in9 = [[rng.randrange(5, P) for _ in range(77)], [rng.randrange(5, P) for _ in range(23)]]
+    in9[0][0] = 3                                                           # the smallest value of all stands at position 0
+    t10, in10 = table_and_inputs(4000, [123, 377], 2000)
+
+    n_pair = 500
+    alphabet = [rng.randrange(P) for _ in range(60)]
+    S = [rng.choice(alphabet) for _ in range(n_pair)]
+    A_good = [rng.choice(S) for _ in range(n_pair)]
+    A_bad = A_good[:]
+    A_bad[77], A_bad[402] = (1 << 200) + 1, 7                              # the smaller missing value in the higher row
+    assert not {A_bad[77], A_bad[402]} & set(S)
+    want_pair = lookup_ref.permute_expression_pair(A_good, S)
+    with pytest.raises(lookup_ref.NotInTable) as e:
+        lookup_ref.permute_expression_pair(A_bad, S)
+    bad_row = e.value.index
+    assert bad_row == 402
+
+    def permute(A, good):
+        def fn(c):
+            d_a, d_s = c.to_device(_mont(A)), c.to_device(_mont(S))
+            out_a, out_s = _filled(c, n_pair), _filled(c, n_pair)
+            if good:
+                c.lookup_permute_device(d_a.ptr, d_s.ptr, n_pair, out_a, out_s)
+                for out, want in zip((out_a, out_s), want_pair):
+                    got = out.download(np.uint8)
+                    assert got[:n_pair * 32].tobytes() == _mont(want).tobytes() and (got[n_pair * 32:] == 0xFF).all()
+            else:
+                with pytest.raises(api.NotInTable) as err:
+                    c.lookup_permute_device(d_a.ptr, d_s.ptr, n_pair, out_a, out_s)
+                assert err.value.index == bad_row
+                _untouched(out_a); _untouched(out_s)
+            for d in (d_a, d_s, out_a, out_s):
+                d.free()
+        return fn
+
+    lens_q, roots, cs = [20000, 0, 257], [rng.randrange(P), 0], [rng.randrange(P), 1, rng.randrange(P)]
+    polys = [fr._rand(nrng, n) for n in lens_q]
+    low = fr._rand(nrng, 2)
+    want_q, want_rem = open_ref.open_quotient([fr._ints(p) for p in polys], cs, fr._ints(low), roots, P)
+
+    def quotient(c):
+        bufs = [c.to_device(p) if p.shape[0] else None for p in polys]
+        out = _filled(c, len(want_q))
+        _, qn, rem = c.open_quotient(bufs, lens_q, _mont(cs), low, _mont(roots), False, out)
+        got = out.download(np.uint8)
+        assert qn == len(want_q) == 20000 - 2 and got[:qn * 32].tobytes() == _arr(want_q).tobytes() and (got[qn * 32:] == 0xFF).all()
+        assert fr._ints(rem) == want_rem
+        plan = api.open_plan(lens_q, 2, 2)
+        assert c.poly_last()[1:] == (plan["bytes"], plan["field_mults"])
+        for d in bufs + [out]:
+            if d:
+                d.free()
+
+    good, refused = ("sort", "poly"), ("sort", "poly", "bad")
+    return [("fft_device logn 16", ("poly",), fft),
+            ("multiplicities N = 700, t = 300", good, lambda c: _run(c, in1, t1, MONT)),
+            ("lookup_permute_device, a missing value", refused, permute(A_bad, False)),
+            ("multiplicities, good", good, lambda c: _run(c, in4, t4, CANON)),
+            ("multiplicities, a missing value", refused, lambda c: _missing(c, in5, t5, 200 + 311, host=False)),
+            ("lookup_permute_device, good", good, permute(A_good, True)),
+            ("open_quotient_device, 20000 coefficients, 2 roots", ("poly",), quotient),
+            ("multiplicities, N = 0", good, lambda c: _run(c, [[], []], t8, MONT)),
+            ("multiplicities, t = 0 < N", refused, lambda c: _missing(c, in9, [], 0, host=False)),
+            ("multiplicities, N = 500, t = 4000", good, lambda c: _run(c, in10, t10, MONT))]
+
+
+@pytest.mark.parametrize("guards", [0, 1])
+def test_calls_behind_other_families_on_one_context(ctx, guards):
+    """a fixed order of ten calls on one context -- a transform that leaves the workspace full of field elements, multiplicity
+    calls, lookup_permute (which records into the same sort_last and error words' arena), an opening (which carves the same
+    workspace), refusals between good calls, N = 0, t = 0, a table eight times the inputs -- each compared with its reference.
+    After each call the figures the call records (sort_last, poly_last; after a refusal last_bad_index too) are those of the
+    same call on a context created for it alone, and the figures it does not record are as they were before it"""
+    steps = _cross_family_steps()
+    reported = {2: 402, 4: 511, 8: 0}                                       # step -> the row / position its refusal reports
+    assert [k for k, (_, records, _) in enumerate(steps) if "bad" in records] == sorted(reported)
+    ctx.set_option("ws_canary", guards)
+    try:
+        for k, (name, records, fn) in enumerate(steps):
+            before = _figures(ctx)
+            fn(ctx)
+            got = _figures(ctx)
+            alone = api.Context(0)
+            try:
+                alone.set_option("ws_canary", guards)
+                fn(alone)
+                want = _figures(alone)
+            finally:
+                alone.close()
+            for key in ("sort", "poly", "bad"):
+                if key in records:
+                    assert got[key] == want[key], (name, key, got, want)
+                else:
+                    assert got[key] == before[key], (name, key, got, before)
+            if "bad" in records:
+                assert got["bad"] == reported[k], (name, got)
+    finally:
+        ctx.set_option("ws_canary", 0)
 
 
 # ---- the chain: m is what makes the two running sums meet ---------------------------------------------------------------------------

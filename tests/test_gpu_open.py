@@ -327,6 +327,84 @@ def test_divide_a_long_row(ctx):
     d_in.free(); d_out.free()
 
 
+SEGMENT_CHANGE = 1 << 21              # poly_kd_segment: 64 coefficients a segment below it, 128 from it on
+
+
+@functools.lru_cache(maxsize=None)
+def _long_rows():
+    """2^21 + 1 and 1 000 003 random coefficients, made once for every case of the test below"""
+    return _rand(5600, SEGMENT_CHANGE + 1), _rand(5601, 1000003)
+
+
+def _tail_and_top(ctx, buf, n_elems):
+    """(the zone behind the n_elems elements of buf, its last element)"""
+    tail, top = np.zeros(ZONE, np.uint8), np.zeros((1, 4), np.uint64)
+    ctx._check(ctx.lib.lemsm_device_download(ctx.h, tail.ctypes.data, buf.ptr + 32 * n_elems, ZONE))
+    ctx._check(ctx.lib.lemsm_device_download(ctx.h, top.ctypes.data, buf.ptr + 32 * (n_elems - 1), 32))
+    return tail, _ints(top)[0]
+
+
+def _remainder_form(rems, roots, x):
+    """sum_i r_i prod_{j < i} (x - z_j)"""
+    total, run = 0, 1
+    for r, z in zip(rems, roots):
+        total, run = (total + r * run) % P, run * (x - z) % P
+    return total
+
+
+@pytest.mark.parametrize("canary", [0, 1])
+@pytest.mark.parametrize("k", [3, 8])
+def test_divide_stages_on_both_sides_of_the_segment_change(ctx, k, canary):
+    """2^21 + 1 coefficients by k >= 3 roots: the stages have 2^21 + 1, 2^21, 2^21 - 1, .. coefficients, so the first two run on
+    segments of 128 (16385 and 16384 of them) and every later one on segments of 64 (32768): the segment buffer is sized by a
+    later stage than the first, and z^S changes between the stages of one call.  poly_divide_roots_device, and open_quotient_device
+    over two polynomials, the longer of that length, against something that is not the division kernels (regfn_eval_device's
+    Horner and big integers): a(x) = q(x) prod (x - z_i) + sum_i r_i prod_{j < i} (x - z_j) at two random x, r_0 = a(z_0), the
+    leading coefficient, the 0xFF zone, poly_last; with and without the workspace guards"""
+    n = SEGMENT_CHANGE + 1
+    plan = api.open_plan([n], 0, k)
+    assert n - 1 >= SEGMENT_CHANGE > n - 2 and k >= 3                          # stages 0 and 1 at or above the change, stage 2 below
+    rng = random.Random(5610 + k)
+    a, b = _long_rows()
+    roots = _roots(rng, k, "both" if k == 8 else "distinct")
+    xs = [rng.randrange(P), rng.randrange(P)]
+    prod = [functools.reduce(lambda acc, z: acc * (x - z) % P, roots, 1) for x in xs]
+    d_a, d_b, d_out = ctx.to_device(a), ctx.to_device(b), _filled(ctx, n - k)
+    ctx.set_option("ws_canary", canary)
+    try:
+        _, rem = ctx.divide_by_roots(d_a, n, _mont(roots), False, d_out)
+        assert ctx.poly_last()[1:] == (plan["bytes"] - 64 * n, plan["field_mults"] - n) == (sum(96 * (n - i) for i in range(k)), sum(2 * (n - i) for i in range(k)))
+        rems = _ints(rem)
+        ax = _eval(ctx, d_a.ptr, n, n, xs + [roots[0]])
+        qx = _eval(ctx, d_out.ptr, n - k, n - k, xs)
+        assert ax[2] == rems[0]                                                # a(z_0) is the first remainder
+        for x, pr, av, qv in zip(xs, prod, ax, qx):
+            assert av == (qv * pr + _remainder_form(rems, roots, x)) % P
+        tail, top = _tail_and_top(ctx, d_out, n - k)
+        assert (tail == 0xFF).all() and top == _ints(a[n - 1:])[0]             # the leading coefficient comes down unchanged
+        # the quotient of c_0 a + c_1 b - low
+        cs, low = [rng.randrange(1, P), rng.randrange(P)], _rand(5620 + k, 2)
+        d_out.upload(np.full((n - k) * 32 + ZONE, 0xFF, np.uint8))
+        lens = [n, b.shape[0]]
+        _, qn, rem = ctx.open_quotient([d_a, d_b], lens, _mont(cs), low, _mont(roots), False, d_out)
+        full = api.open_plan(lens, 2, k)
+        assert qn == n - k == full["len_out"] and ctx.poly_last()[1:] == (full["bytes"], full["field_mults"])
+        rems = _ints(rem)
+        bx = _eval(ctx, d_b.ptr, lens[1], lens[1], xs + [roots[0]])
+        comb = [(cs[0] * av + cs[1] * bv - open_ref.ev(_ints(low), x, P)) % P for av, bv, x in zip(ax, bx, xs + [roots[0]])]
+        qx = _eval(ctx, d_out.ptr, n - k, n - k, xs)
+        assert comb[2] == rems[0]
+        for x, pr, cv, qv in zip(xs, prod, comb, qx):
+            assert cv == (qv * pr + _remainder_form(rems, roots, x)) % P
+        tail, top = _tail_and_top(ctx, d_out, n - k)
+        assert (tail == 0xFF).all() and top == cs[0] * _ints(a[n - 1:])[0] % P
+        assert d_a.download(np.uint64, 64).tobytes() == a[:2].tobytes()
+    finally:
+        ctx.set_option("ws_canary", 0)
+        for buf in (d_a, d_b, d_out):
+            buf.free()
+
+
 def test_divide_errors_leave_the_outputs_untouched(ctx):
     n = 300
     a_host = _rand(5500, n)
