@@ -1,6 +1,7 @@
 """MI355X (gfx950) MSM witness path for Liam Eagen's MSM argument.
 
-`api` mirrors the reference's Rust entry points over the C ABI in include/lemsm.h;
+`api` mirrors the reference's Rust entry points over the C ABI in include/lemsm.h (and halo2's g_to_lagrange over
+include/lemsm_srs.h, the setup side);
 `dist` shards one MSM by Pippenger window / negabase digit position over the GPUs of a node.
 """
 from . import _lib  # noqa: F401
@@ -20,4 +21,5 @@ from .api import (  # noqa: F401
     sort_field_geometry, lookup_permute_plan, permute_expression_pair, NotInTable, debug_sort_thresholds,
     lookup_multiplicities_plan, lookup_multiplicities,
     poly_lincomb, divide_by_roots, open_quotient, lagrange_interpolate, open_plan,
+    ecfft_plan, ecfft, g_to_lagrange,
 )

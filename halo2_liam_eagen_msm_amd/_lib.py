@@ -1,4 +1,4 @@
-"""ctypes loader for the C-ABI library (include/lemsm.h).
+"""ctypes loader for the C-ABI library (include/lemsm.h, and include/lemsm_srs.h for the setup side).
 
 The product path has NO CPU fallback: if liblemsm.so is missing or no gfx950
 device is usable, loading / context creation raises.
@@ -86,6 +86,10 @@ SYMBOLS = [
     "lemsm_open_quotient_device", "lemsm_open_quotient", "lemsm_open_plan", "lemsm_lagrange_interpolate",
 ]
 
+# Every symbol include/lemsm_srs.h declares: the setup side (tests/test_ecfft_plan.py checks this list against that header)
+SRS_SYMBOLS = ["lemsm_ecfft_plan", "lemsm_ecfft_device", "lemsm_ecfft", "lemsm_srs_to_lagrange_device", "lemsm_ecfft_last"]
+LEMSM_ECFFT_MAX_LOGN = 24
+
 
 class GateQuery(ctypes.Structure):
     """lemsm_gate_query"""
@@ -108,7 +112,7 @@ GATE_OPS = ("PUSH_CELL", "PUSH_CONST", "PUSH_X", "ADD", "SUB", "MUL", "NEG", "AD
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "lemsm.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("lemsm.h", "lemsm_srs.h")]
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs if os.path.isfile(s)
     )
@@ -291,6 +295,16 @@ def load() -> ctypes.CDLL:
         "lemsm_open_plan": (i, [vp, sz, sz, sz, szp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), szp]),
         "lemsm_lagrange_interpolate": (i, [u64p, u64p, sz, u64p, szp]),
     }
+    u64o = ctypes.POINTER(ctypes.c_uint64)
+    srs_sig = {
+        "lemsm_ecfft_plan": (i, [ctypes.c_uint32, i, u64o, u64o, u64o, u64o]),
+        "lemsm_ecfft_device": (i, [vp, i, vp, ctypes.c_uint32, u64p, u64p, vp, szp]),
+        "lemsm_ecfft": (i, [vp, i, u64p, ctypes.c_uint32, u64p, u64p, u64p, szp]),
+        "lemsm_srs_to_lagrange_device": (i, [vp, i, vp, sz, ctypes.c_uint32, vp]),
+        "lemsm_ecfft_last": (i, [vp, ctypes.POINTER(ctypes.c_double), u64o, u64o, u64o]),
+    }
+    assert sorted(srs_sig) == sorted(SRS_SYMBOLS)
+    sig.update(srs_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res

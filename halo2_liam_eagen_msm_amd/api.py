@@ -111,6 +111,9 @@ ENTRY_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8"), ("mask", "<u4"), ("kind", 
 ENTRY_KINDS = ("Scalar", "Bucket", "Limb")
 
 
+_NO_INDEX = (1 << 64) - 1          # what a bad_index output holds when the entry named no input
+
+
 def _curve_id(curve) -> int:
     if isinstance(curve, str):
         return CURVE_IDS[curve]
@@ -846,6 +849,51 @@ class Context:
         ms = ctypes.c_double(); by = ctypes.c_uint64(); fm = ctypes.c_uint64()
         self._check(self.lib.lemsm_poly_last(self.h, ctypes.byref(ms), ctypes.byref(by), ctypes.byref(fm)))
         return ms.value, by.value, fm.value
+
+    # ---- the setup side: best_fft over G1, g_to_lagrange (include/lemsm_srs.h) ----
+    def ecfft_device(self, d_in: int, logn: int, omega, scale, d_out: int, curve="bn254_g1"):
+        """halo2's best_fft on the 2^logn G1 points (64 B affine, raw Montgomery, identity all zeros) at device pointer d_in
+        into d_out (d_out == d_in allowed), natural order in and out: out[k] = scale sum_j omega^(j k) in[j].  omega: a
+        primitive 2^logn-th root of unity of Fr (4 limbs); scale: None (unscaled) or 4 limbs.  A point off the curve under
+        option validate_points: LemsmError with the point's index in .index."""
+        w = np.ascontiguousarray(omega, np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.uint64).reshape(4)
+        bad = ctypes.c_size_t(_NO_INDEX)
+        rc = self.lib.lemsm_ecfft_device(self.h, _curve_id(curve), self._dev(d_in), logn, _ptr(w), _ptr(sc) if sc is not None else None,
+                                         self._dev(d_out), ctypes.byref(bad))
+        self._check_indexed(rc, bad)
+
+    def ecfft(self, points, logn: int, omega, scale=None, curve="bn254_g1") -> np.ndarray:
+        """the same for host points ((2^logn, 8) uint64): returns the transform"""
+        p = _limbs(points, 8)
+        if p.shape[0] != 1 << logn:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the points are not 2^logn affine points")
+        w = np.ascontiguousarray(omega, np.uint64).reshape(4)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.uint64).reshape(4)
+        out = np.zeros_like(p)
+        bad = ctypes.c_size_t(_NO_INDEX)
+        rc = self.lib.lemsm_ecfft(self.h, _curve_id(curve), _ptr(p), logn, _ptr(w), _ptr(sc) if sc is not None else None, _ptr(out), ctypes.byref(bad))
+        self._check_indexed(rc, bad)
+        return out
+
+    def srs_to_lagrange_device(self, d_g: int, n_g: int, logn: int, d_out: int, curve="bn254_g1"):
+        """halo2's g_to_lagrange / the transform inside ParamsKZG::downsize: the first 2^logn of the n_g monomial bases at device
+        pointer d_g into the Lagrange basis at d_out, ready to be the points of msm_device"""
+        self._check(self.lib.lemsm_srs_to_lagrange_device(self.h, _curve_id(curve), self._dev(d_g), n_g, logn, self._dev(d_out)))
+
+    def ecfft_last(self) -> Tuple[float, int, int, int]:
+        """(device ms, point_muls, point_adds, group_ops) of the last ecfft* / srs_to_lagrange_device call"""
+        ms = ctypes.c_double(); pm = ctypes.c_uint64(); pa = ctypes.c_uint64(); go = ctypes.c_uint64()
+        self._check(self.lib.lemsm_ecfft_last(self.h, ctypes.byref(ms), ctypes.byref(pm), ctypes.byref(pa), ctypes.byref(go)))
+        return ms.value, pm.value, pa.value, go.value
+
+    def _check_indexed(self, rc: int, bad):
+        """_check for the entries whose LEMSM_ERR_BAD_ARG may name an input: the error then carries .index"""
+        try:
+            self._check(rc)
+        except LemsmError as e:
+            e.index = None if bad.value == _NO_INDEX else int(bad.value)
+            raise
 
     # ---- multipoint openings on resident polynomials: combine, divide by roots (DESIGN 7h) ----
     @staticmethod
@@ -2003,6 +2051,39 @@ def best_fft(a, omega, log_n: int, ctx: Optional[Context] = None) -> np.ndarray:
     """halo2 arithmetic::best_fft(a, omega, log_n) (called at src/regular_functions_utils.rs:119-124), unscaled; returns the
     transform of a ((2^log_n, 4) raw Montgomery limbs) instead of working in place"""
     return (ctx or default_context()).fft(a, log_n, omega)
+
+
+def ecfft_plan(logn: int, scaled: bool = False) -> dict:
+    """the price of one transform of 2^logn G1 points (pure host: lemsm_ecfft_plan): {"point_muls", "point_adds",
+    "group_ops", "workspace_bytes"}; raises LemsmError (LEMSM_ERR_BAD_ARG) past logn 24"""
+    lib = _lib.load()
+    pm = ctypes.c_uint64(); pa = ctypes.c_uint64(); go = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_ecfft_plan(logn, 1 if scaled else 0, ctypes.byref(pm), ctypes.byref(pa), ctypes.byref(go), ctypes.byref(wb))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"point_muls": pm.value, "point_adds": pa.value, "group_ops": go.value, "workspace_bytes": wb.value}
+
+
+def ecfft(points, omega, log_n: int, scale=None, ctx: Optional[Context] = None) -> np.ndarray:
+    """halo2 arithmetic::best_fft(a, omega, log_n) on G1 points (FftGroup): (2^log_n, 8) raw affine limbs in, the transform out;
+    scale: None (as best_fft leaves it) or 4 limbs of Fr"""
+    return (ctx or default_context()).ecfft(points, log_n, omega, scale)
+
+
+def g_to_lagrange(g, k: int, ctx: Optional[Context] = None) -> np.ndarray:
+    """halo2 poly::kzg::commitment::g_to_lagrange(g, k): the first 2^k of the monomial bases g ((n, 8) raw affine limbs,
+    n >= 2^k) in the Lagrange basis, (2^k, 8); what ParamsKZG::setup, from_parts and downsize(k) compute"""
+    g = _limbs(g, 8)
+    ctx = ctx or default_context()
+    n = 1 << k
+    if g.shape[0] < n:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "g_to_lagrange: fewer than 2^k bases")
+    buf = ctx.to_device(g[:n])
+    try:
+        ctx.srs_to_lagrange_device(buf.ptr, n, k, buf.ptr)
+        return buf.download(np.uint64, n * 64).reshape(n, 8)
+    finally:
+        buf.free()
 
 
 def kate_division(a, b, ctx: Optional[Context] = None) -> np.ndarray:

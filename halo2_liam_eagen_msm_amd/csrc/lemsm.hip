@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/lemsm.h"
+#include "../../include/lemsm_srs.h"
 #include "arena.hpp"
 #include "timed_run.hpp"
 #include "ntt_schedule.hpp"
@@ -36,6 +37,7 @@
 #include "lookup.cuh"
 #include "logup.cuh"
 #include "open.cuh"
+#include "ecfft.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -143,6 +145,8 @@ struct PolyTable {
 
 // what a family's *_last entry reports: device time of the last call's kernels, the bytes and field products it was priced at
 struct LastStats { double ms = 0; u64 bytes = 0, mults = 0; };
+// ... and lemsm_ecfft_last: the point multiplications, the additions of the butterflies, the group operations in all
+struct EcfftLast { double ms = 0; u64 muls = 0, adds = 0, ops = 0; };
 
 // host-pointer entries: where one call's inputs live on the host and where their slabs are staged in HBM
 struct HostStage { const uint8_t* h_scalars; const void* h_points; char* d_scalars; char* d_points; };
@@ -178,6 +182,8 @@ struct lemsm_ctx {
   DevBuf poly_ws, poly_stage;        // fft / kate_division / poly_mul: call workspace, staged arrays (host entries)
   PolyTable poly_tab;                // ... and their twiddle table
   LastStats poly_last;               // lemsm_poly_last
+  DevBuf ec_ws, ec_stage;            // ecfft / srs_to_lagrange: call workspace, staged points (host entry)
+  EcfftLast ec_last;                 // lemsm_ecfft_last
   u32 sort_passes_run = 0, sort_passes_skipped = 0;   // lemsm_sort_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
@@ -1881,7 +1887,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab.buf}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab.buf, &ctx->ec_ws, &ctx->ec_stage}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);
@@ -2794,3 +2800,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "lookup_abi.inc"
 #include "logup_abi.inc"
 #include "open_abi.inc"
+#include "ecfft_abi.inc"
