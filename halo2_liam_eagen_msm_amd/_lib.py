@@ -1,4 +1,5 @@
-"""ctypes loader for the C-ABI library (include/lemsm.h, and include/lemsm_srs.h for the setup side).
+"""ctypes loader for the C-ABI library (include/lemsm.h, include/lemsm_srs.h for the setup side, include/lemsm_ipa.h for the
+inner-product argument).
 
 The product path has NO CPU fallback: if liblemsm.so is missing or no gfx950
 device is usable, loading / context creation raises.
@@ -90,6 +91,11 @@ SYMBOLS = [
 SRS_SYMBOLS = ["lemsm_ecfft_plan", "lemsm_ecfft_device", "lemsm_ecfft", "lemsm_srs_to_lagrange_device", "lemsm_ecfft_last"]
 LEMSM_ECFFT_MAX_LOGN = 24
 
+# Every symbol include/lemsm_ipa.h declares: the inner-product argument (tests/test_ipa_plan.py checks this list against that header)
+IPA_SYMBOLS = ["lemsm_ipa_plan", "lemsm_ipa_powers_device", "lemsm_ipa_round_device", "lemsm_ipa_fold_device", "lemsm_ipa_s_device",
+               "lemsm_ipa_last"]
+LEMSM_IPA_MAX_K = 24
+
 
 class GateQuery(ctypes.Structure):
     """lemsm_gate_query"""
@@ -112,7 +118,7 @@ GATE_OPS = ("PUSH_CELL", "PUSH_CONST", "PUSH_X", "ADD", "SUB", "MUL", "NEG", "AD
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("lemsm.h", "lemsm_srs.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("lemsm.h", "lemsm_srs.h", "lemsm_ipa.h")]
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs if os.path.isfile(s)
     )
@@ -305,6 +311,16 @@ def load() -> ctypes.CDLL:
     }
     assert sorted(srs_sig) == sorted(SRS_SYMBOLS)
     sig.update(srs_sig)
+    ipa_sig = {
+        "lemsm_ipa_plan": (i, [ctypes.c_uint32, u64o, u64o, u64o, u64o]),
+        "lemsm_ipa_powers_device": (i, [vp, u64p, sz, vp]),
+        "lemsm_ipa_round_device": (i, [vp, i, vp, vp, vp, sz, u64p, u64p, u64p, u64p]),
+        "lemsm_ipa_fold_device": (i, [vp, i, vp, vp, vp, sz, u64p, u64p]),
+        "lemsm_ipa_s_device": (i, [vp, u64p, ctypes.c_uint32, u64p, i, vp]),
+        "lemsm_ipa_last": (i, [vp, ctypes.POINTER(ctypes.c_double), u64o, u64o, u64o]),
+    }
+    assert sorted(ipa_sig) == sorted(IPA_SYMBOLS)
+    sig.update(ipa_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res

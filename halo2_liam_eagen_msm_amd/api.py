@@ -887,6 +887,55 @@ class Context:
         self._check(self.lib.lemsm_ecfft_last(self.h, ctypes.byref(ms), ctypes.byref(pm), ctypes.byref(pa), ctypes.byref(go)))
         return ms.value, pm.value, pa.value, go.value
 
+    # ---- the inner-product argument's rounds on resident data (include/lemsm_ipa.h) ----
+    def ipa_powers_device(self, x, n: int, d_out):
+        """out[i] = x^i, i < n (32 B raw Montgomery each) at device pointer d_out: the vector b of an opening at x (4 limbs)"""
+        xx = np.ascontiguousarray(x, np.uint64).reshape(4)
+        self._check(self.lib.lemsm_ipa_powers_device(self.h, _ptr(xx), n, self._dev(d_out)))
+
+    def ipa_round_device(self, d_p, d_b, d_g, half: int, curve="bn254_g1"):
+        """One round on the 2 half coefficients at d_p, the 2 half generators at d_g and (or None) the 2 half elements at d_b:
+        (L, R, value_l, value_r) with L = <p_hi, g_lo>, R = <p_lo, g_hi> as 12-limb Jacobian points and value_l = <p_hi, b_lo>,
+        value_r = <p_lo, b_hi> as 4 raw Montgomery limbs (None, None without d_b).  Reads only."""
+        l, r = np.zeros(12, np.uint64), np.zeros(12, np.uint64)
+        vl, vr = (np.zeros(4, np.uint64), np.zeros(4, np.uint64)) if d_b is not None else (None, None)
+        rc = self.lib.lemsm_ipa_round_device(self.h, _curve_id(curve), self._dev(d_p), self._dev(d_b), self._dev(d_g), half, _ptr(l), _ptr(r),
+                                             _ptr(vl) if vl is not None else None, _ptr(vr) if vr is not None else None)
+        self._check_generators(rc)
+        return l, r, vl, vr
+
+    def ipa_fold_device(self, d_p, d_b, d_g, half: int, u, u_inv, curve="bn254_g1"):
+        """One round's folds in place: p_lo += u_inv p_hi, b_lo += u b_hi, g_lo[i] = affine(g_lo[i] + u g_hi[i]); each of d_p,
+        d_b, d_g may be None (not all three); u, u_inv: 4 raw Montgomery limbs with u u_inv = 1"""
+        uu = np.ascontiguousarray(u, np.uint64).reshape(4)
+        ui = np.ascontiguousarray(u_inv, np.uint64).reshape(4)
+        rc = self.lib.lemsm_ipa_fold_device(self.h, _curve_id(curve), self._dev(d_p), self._dev(d_b), self._dev(d_g), half, _ptr(uu), _ptr(ui))
+        self._check_generators(rc)
+
+    def ipa_s_device(self, u, k: int, init, d_out, form: int = _lib.LEMSM_FORM_MONTGOMERY):
+        """halo2's compute_s into the 2^k elements at d_out: s_i = init prod_j u_j^(bit_(k-1-j)(i)); u: (k, 4) raw Montgomery limbs;
+        form FORM_CANONICAL gives the scalars msm_device takes"""
+        uu = np.ascontiguousarray(u, np.uint64).reshape(-1, 4) if k else np.zeros((1, 4), np.uint64)
+        if k and uu.shape[0] != k:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the challenges are not k field elements")
+        ini = np.ascontiguousarray(init, np.uint64).reshape(4)
+        self._check(self.lib.lemsm_ipa_s_device(self.h, _ptr(uu), k, _ptr(ini), form, self._dev(d_out)))
+
+    def _check_generators(self, rc: int):
+        """_check for the entries that name an off-curve generator through lemsm_last_bad_index alone (option validate_points):
+        the error then carries .index"""
+        try:
+            self._check(rc)
+        except LemsmError as e:
+            e.index = int(self.lib.lemsm_last_bad_index(self.h)) if "validate_points" in str(e) else None
+            raise
+
+    def ipa_last(self) -> Tuple[float, int, int, int]:
+        """(device ms, point_muls, msm_pairs, field_mults) of the last ipa_*_device call"""
+        ms = ctypes.c_double(); pm = ctypes.c_uint64(); mp = ctypes.c_uint64(); fm = ctypes.c_uint64()
+        self._check(self.lib.lemsm_ipa_last(self.h, ctypes.byref(ms), ctypes.byref(pm), ctypes.byref(mp), ctypes.byref(fm)))
+        return ms.value, pm.value, mp.value, fm.value
+
     def _check_indexed(self, rc: int, bad):
         """_check for the entries whose LEMSM_ERR_BAD_ARG may name an input: the error then carries .index"""
         try:
@@ -2084,6 +2133,63 @@ def g_to_lagrange(g, k: int, ctx: Optional[Context] = None) -> np.ndarray:
         return buf.download(np.uint64, n * 64).reshape(n, 8)
     finally:
         buf.free()
+
+
+def ipa_plan(k: int) -> dict:
+    """the price of a whole IPA opening of 2^k coefficients (pure host: lemsm_ipa_plan): {"point_muls", "msm_pairs",
+    "field_mults", "workspace_bytes"}; raises LemsmError (LEMSM_ERR_BAD_ARG) past k 24"""
+    lib = _lib.load()
+    pm = ctypes.c_uint64(); mp = ctypes.c_uint64(); fm = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_ipa_plan(k, ctypes.byref(pm), ctypes.byref(mp), ctypes.byref(fm), ctypes.byref(wb))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"point_muls": pm.value, "msm_pairs": mp.value, "field_mults": fm.value, "workspace_bytes": wb.value}
+
+
+def ipa_open(p, g, x, challenge, b=None, ctx: Optional[Context] = None) -> dict:
+    """The rounds of halo2's IPA opening (poly::ipa::commitment::prover::create_proof) of the 2^k coefficients p ((2^k, 4) raw
+    Montgomery limbs) over the generators g ((2^k, 8) raw affine limbs) at the point x (4 limbs), or against the vector b
+    ((2^k, 4)) where one is given.  Everything is uploaded once; round j computes L_j, R_j, value_l_j, value_r_j, calls
+    challenge(j, L, R, value_l, value_r), which returns (u, u_inv) as 4 limbs each (the transcript, the blinding and the U / W
+    terms are the caller's), and folds.  Returns {"L", "R": (k, 12) Jacobian; "value_l", "value_r", "u", "u_inv": (k, 4);
+    "c", "b": the final p'[0], b'[0]; "g": the final g'[0] (8 limbs); "last": the (ms, point_muls, msm_pairs, field_mults) of
+    every round and fold call, in order}."""
+    p = _limbs(p, 4)
+    g = _limbs(g, 8)
+    n = p.shape[0]
+    k = n.bit_length() - 1
+    if n == 0 or n != 1 << k or g.shape[0] != n or (b is not None and _limbs(b, 4).shape[0] != n):
+        raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "ipa_open: p, g (and b) must hold the same power of two of elements")
+    ctx = ctx or default_context()
+    bufs = [ctx.to_device(p), ctx.to_device(g)]
+    try:
+        d_p, d_g = bufs
+        if b is None:
+            d_b = ctx.alloc(n * 32)
+            bufs.append(d_b)
+            ctx.ipa_powers_device(x, n, d_b)
+        else:
+            d_b = ctx.to_device(_limbs(b, 4))
+            bufs.append(d_b)
+        out = {name: np.zeros((k, w), np.uint64) for name, w in (("L", 12), ("R", 12), ("value_l", 4), ("value_r", 4), ("u", 4), ("u_inv", 4))}
+        out["last"] = []
+        half = n
+        for j in range(k):
+            half >>= 1
+            l, r, vl, vr = ctx.ipa_round_device(d_p, d_b, d_g, half)
+            out["last"].append(ctx.ipa_last())
+            u, u_inv = challenge(j, l, r, vl, vr)
+            ctx.ipa_fold_device(d_p, d_b, d_g, half, u, u_inv)
+            out["last"].append(ctx.ipa_last())
+            out["L"][j], out["R"][j], out["value_l"][j], out["value_r"][j] = l, r, vl, vr
+            out["u"][j], out["u_inv"][j] = np.ascontiguousarray(u, np.uint64).reshape(4), np.ascontiguousarray(u_inv, np.uint64).reshape(4)
+        out["c"] = d_p.download(np.uint64, 32).copy()
+        out["b"] = d_b.download(np.uint64, 32).copy()
+        out["g"] = d_g.download(np.uint64, 64).copy()
+        return out
+    finally:
+        for d in bufs:
+            d.free()
 
 
 def kate_division(a, b, ctx: Optional[Context] = None) -> np.ndarray:

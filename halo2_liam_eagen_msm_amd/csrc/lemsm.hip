@@ -15,6 +15,7 @@
 
 #include "../../include/lemsm.h"
 #include "../../include/lemsm_srs.h"
+#include "../../include/lemsm_ipa.h"
 #include "arena.hpp"
 #include "timed_run.hpp"
 #include "ntt_schedule.hpp"
@@ -38,6 +39,7 @@
 #include "logup.cuh"
 #include "open.cuh"
 #include "ecfft.cuh"
+#include "ipa.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -147,6 +149,8 @@ struct PolyTable {
 struct LastStats { double ms = 0; u64 bytes = 0, mults = 0; };
 // ... and lemsm_ecfft_last: the point multiplications, the additions of the butterflies, the group operations in all
 struct EcfftLast { double ms = 0; u64 muls = 0, adds = 0, ops = 0; };
+// ... and lemsm_ipa_last: the generator multiplications, the pairs of the multiexps, the field products
+struct IpaLast { double ms = 0; u64 muls = 0, pairs = 0, mults = 0; };
 
 // host-pointer entries: where one call's inputs live on the host and where their slabs are staged in HBM
 struct HostStage { const uint8_t* h_scalars; const void* h_points; char* d_scalars; char* d_points; };
@@ -184,6 +188,8 @@ struct lemsm_ctx {
   LastStats poly_last;               // lemsm_poly_last
   DevBuf ec_ws, ec_stage;            // ecfft / srs_to_lagrange: call workspace, staged points (host entry)
   EcfftLast ec_last;                 // lemsm_ecfft_last
+  DevBuf ipa_ws;                     // ipa round / fold / powers / s: call workspace
+  IpaLast ipa_last;                  // lemsm_ipa_last
   u32 sort_passes_run = 0, sort_passes_skipped = 0;   // lemsm_sort_last
   double dw_phase_ms[4] = {0, 0, 0, 0};   // lhs witness: MSM core, point lists, merge forest, coefficient download
   ncclComm_t comm = nullptr; int comm_size = 1, comm_rank = 0;   // lemsm_comm_init
@@ -1887,7 +1893,7 @@ void lemsm_destroy(lemsm_ctx* ctx) {
   ctx->pool.reset();
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab.buf, &ctx->ec_ws, &ctx->ec_stage}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&ctx->ws, &ctx->in_s, &ctx->in_p, &ctx->in_aux, &ctx->gather, &ctx->fail_buf, &ctx->dw_tab, &ctx->dw_arena, &ctx->dw_tmp, &ctx->rf_coef, &ctx->rf_ws, &ctx->rhs_ws, &ctx->rhs_tab, &ctx->rhs_pw, &ctx->col_ws, &ctx->col_stage, &ctx->poly_ws, &ctx->poly_stage, &ctx->poly_tab.buf, &ctx->ec_ws, &ctx->ec_stage, &ctx->ipa_ws}) if (b->p) (void)hipFree(b->p);
   for (auto& kv : ctx->pyr_cache) if (kv.second.buf.p) (void)hipFree(kv.second.buf.p);
   for (int i = 0; i < 5; i++) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (int i = 0; i < 2; i++) if (ctx->dw_ev[i]) (void)hipEventDestroy(ctx->dw_ev[i]);
@@ -2801,3 +2807,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "logup_abi.inc"
 #include "open_abi.inc"
 #include "ecfft_abi.inc"
+#include "ipa_abi.inc"
