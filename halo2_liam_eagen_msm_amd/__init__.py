@@ -1,7 +1,7 @@
 """MI355X (gfx950) MSM witness path for Liam Eagen's MSM argument.
 
 `api` mirrors the reference's Rust entry points over the C ABI in include/lemsm.h (and halo2's g_to_lagrange over
-include/lemsm_srs.h, the setup side, and the rounds of halo2's IPA opening over include/lemsm_ipa.h);
+include/lemsm_srs.h, the setup side, and the rounds of halo2's IPA opening over include/lemsm_ipa.h and lemsm_ipa_tail.h);
 `dist` shards one MSM by Pippenger window / negabase digit position over the GPUs of a node.
 """
 from . import _lib  # noqa: F401
@@ -23,4 +23,5 @@ from .api import (  # noqa: F401
     poly_lincomb, divide_by_roots, open_quotient, lagrange_interpolate, open_plan,
     ecfft_plan, ecfft, g_to_lagrange,
     ipa_plan, ipa_open,
+    ipa_tail_plan, ipa_default_fold_rounds, ipa_open_unfolded,
 )

@@ -1,5 +1,5 @@
 """ctypes loader for the C-ABI library (include/lemsm.h, include/lemsm_srs.h for the setup side, include/lemsm_ipa.h for the
-inner-product argument).
+inner-product argument, include/lemsm_ipa_tail.h for its late rounds over unfolded generators).
 
 The product path has NO CPU fallback: if liblemsm.so is missing or no gfx950
 device is usable, loading / context creation raises.
@@ -96,6 +96,10 @@ IPA_SYMBOLS = ["lemsm_ipa_plan", "lemsm_ipa_powers_device", "lemsm_ipa_round_dev
                "lemsm_ipa_last"]
 LEMSM_IPA_MAX_K = 24
 
+# Every symbol include/lemsm_ipa_tail.h declares: the late rounds over unfolded generators (tests/test_ipa_tail_plan.py checks this
+# list against that header)
+IPA_TAIL_SYMBOLS = ["lemsm_ipa_tail_plan", "lemsm_ipa_round_unfolded_device", "lemsm_ipa_final_generator_device"]
+
 
 class GateQuery(ctypes.Structure):
     """lemsm_gate_query"""
@@ -118,7 +122,7 @@ GATE_OPS = ("PUSH_CELL", "PUSH_CONST", "PUSH_X", "ADD", "SUB", "MUL", "NEG", "AD
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("lemsm.h", "lemsm_srs.h", "lemsm_ipa.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("lemsm.h", "lemsm_srs.h", "lemsm_ipa.h", "lemsm_ipa_tail.h")]
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs if os.path.isfile(s)
     )
@@ -321,6 +325,13 @@ def load() -> ctypes.CDLL:
     }
     assert sorted(ipa_sig) == sorted(IPA_SYMBOLS)
     sig.update(ipa_sig)
+    ipa_tail_sig = {
+        "lemsm_ipa_tail_plan": (i, [ctypes.c_uint32, ctypes.c_uint32, u64o, u64o, u64o, u64o]),
+        "lemsm_ipa_round_unfolded_device": (i, [vp, i, vp, vp, vp, sz, u64p, ctypes.c_uint32, u64p, u64p, u64p, u64p]),
+        "lemsm_ipa_final_generator_device": (i, [vp, i, vp, u64p, ctypes.c_uint32, u64p]),
+    }
+    assert sorted(ipa_tail_sig) == sorted(IPA_TAIL_SYMBOLS)
+    sig.update(ipa_tail_sig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -921,6 +921,32 @@ class Context:
         ini = np.ascontiguousarray(init, np.uint64).reshape(4)
         self._check(self.lib.lemsm_ipa_s_device(self.h, _ptr(uu), k, _ptr(ini), form, self._dev(d_out)))
 
+    # ---- the late rounds over generators that are no longer folded (include/lemsm_ipa_tail.h) ----
+    @staticmethod
+    def _challenges(u_prev, q: int) -> np.ndarray:
+        uu = np.ascontiguousarray(u_prev, np.uint64).reshape(-1, 4) if q else np.zeros((1, 4), np.uint64)
+        if q and uu.shape[0] != q:
+            raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "the challenges are not q field elements")
+        return uu
+
+    def ipa_round_unfolded_device(self, d_p, d_b, d_G, half: int, u_prev, q: int, curve="bn254_g1"):
+        """ipa_round_device on generators last folded q rounds ago: d_G holds 2 half 2^q rows, u_prev ((q, 4) raw Montgomery limbs,
+        oldest first) the challenges since; (L, R, value_l, value_r) as ipa_round_device returns them.  Reads only."""
+        uu = self._challenges(u_prev, q)
+        l, r = np.zeros(12, np.uint64), np.zeros(12, np.uint64)
+        vl, vr = (np.zeros(4, np.uint64), np.zeros(4, np.uint64)) if d_b is not None else (None, None)
+        rc = self.lib.lemsm_ipa_round_unfolded_device(self.h, _curve_id(curve), self._dev(d_p), self._dev(d_b), self._dev(d_G), half, _ptr(uu), q,
+                                                      _ptr(l), _ptr(r), _ptr(vl) if vl is not None else None, _ptr(vr) if vr is not None else None)
+        self._check_generators(rc)
+        return l, r, vl, vr
+
+    def ipa_final_generator_device(self, d_G, u_prev, q: int, curve="bn254_g1") -> np.ndarray:
+        """g'[0] = <compute_s(u_prev, 1), G> over the 2^q rows at d_G: 8 raw affine limbs, the bytes q generator folds leave"""
+        uu = self._challenges(u_prev, q)
+        out = np.zeros(8, np.uint64)
+        self._check_generators(self.lib.lemsm_ipa_final_generator_device(self.h, _curve_id(curve), self._dev(d_G), _ptr(uu), q, _ptr(out)))
+        return out
+
     def _check_generators(self, rc: int):
         """_check for the entries that name an off-curve generator through lemsm_last_bad_index alone (option validate_points):
         the error then carries .index"""
@@ -2186,6 +2212,75 @@ def ipa_open(p, g, x, challenge, b=None, ctx: Optional[Context] = None) -> dict:
         out["c"] = d_p.download(np.uint64, 32).copy()
         out["b"] = d_b.download(np.uint64, 32).copy()
         out["g"] = d_g.download(np.uint64, 64).copy()
+        return out
+    finally:
+        for d in bufs:
+            d.free()
+
+
+def ipa_tail_plan(k: int, t: int) -> dict:
+    """the price of an IPA opening of 2^k coefficients whose first t rounds fold the generators and whose other k - t rounds run
+    on the 2^(k - t) generators kept (pure host: lemsm_ipa_tail_plan): the keys of ipa_plan; raises LemsmError
+    (LEMSM_ERR_BAD_ARG) past k 24 or t > k"""
+    lib = _lib.load()
+    pm = ctypes.c_uint64(); mp = ctypes.c_uint64(); fm = ctypes.c_uint64(); wb = ctypes.c_uint64()
+    rc = lib.lemsm_ipa_tail_plan(k, t, ctypes.byref(pm), ctypes.byref(mp), ctypes.byref(fm), ctypes.byref(wb))
+    if rc != _lib.LEMSM_OK:
+        raise LemsmError(rc, lib.lemsm_strerror(rc).decode())
+    return {"point_muls": pm.value, "msm_pairs": mp.value, "field_mults": fm.value, "workspace_bytes": wb.value}
+
+
+def ipa_default_fold_rounds(k: int) -> int:
+    """how many of an opening's k rounds ipa_open_unfolded folds the generators in where the caller does not say: max(0, k - 18),
+    which keeps 2^18 generators.  Measured (tools/ipa_tail_timing.py): the fastest fold_rounds of those tried is 2 at
+    k = 20 and 0 at k = 16; no fewer than k - 18 were tried, and for other k the rule is what these two share, not a measurement"""
+    return max(0, k - 18)
+
+
+def ipa_open_unfolded(p, g, x, challenge, fold_rounds: Optional[int], b=None, ctx: Optional[Context] = None) -> dict:
+    """ipa_open whose generators are folded in the first fold_rounds rounds only (None: ipa_default_fold_rounds(k)).  The later
+    rounds compute L_j and R_j on the 2^(k - fold_rounds) generators kept (ipa_round_unfolded_device) and fold p and b alone;
+    g'[0] comes from ipa_final_generator_device.  Same arguments otherwise, same keys and, as group elements and bytes, the
+    same opening; "last" has one more record, the final generator's."""
+    p = _limbs(p, 4)
+    g = _limbs(g, 8)
+    n = p.shape[0]
+    k = n.bit_length() - 1
+    if n == 0 or n != 1 << k or g.shape[0] != n or (b is not None and _limbs(b, 4).shape[0] != n):
+        raise LengthMismatch(_lib.LEMSM_ERR_LEN_MISMATCH, "ipa_open_unfolded: p, g (and b) must hold the same power of two of elements")
+    t = ipa_default_fold_rounds(k) if fold_rounds is None else fold_rounds
+    if not 0 <= t <= k:
+        raise LemsmError(_lib.LEMSM_ERR_BAD_ARG, "ipa_open_unfolded: fold_rounds must be 0 .. k")
+    ctx = ctx or default_context()
+    bufs = [ctx.to_device(p), ctx.to_device(g)]
+    try:
+        d_p, d_g = bufs
+        if b is None:
+            d_b = ctx.alloc(n * 32)
+            bufs.append(d_b)
+            ctx.ipa_powers_device(x, n, d_b)
+        else:
+            d_b = ctx.to_device(_limbs(b, 4))
+            bufs.append(d_b)
+        out = {name: np.zeros((k, w), np.uint64) for name, w in (("L", 12), ("R", 12), ("value_l", 4), ("value_r", 4), ("u", 4), ("u_inv", 4))}
+        out["last"] = []
+        half = n
+        for j in range(k):
+            half >>= 1
+            if j < t:
+                l, r, vl, vr = ctx.ipa_round_device(d_p, d_b, d_g, half)
+            else:
+                l, r, vl, vr = ctx.ipa_round_unfolded_device(d_p, d_b, d_g, half, out["u"][t:j], j - t)
+            out["last"].append(ctx.ipa_last())
+            u, u_inv = challenge(j, l, r, vl, vr)
+            ctx.ipa_fold_device(d_p, d_b, d_g if j < t else None, half, u, u_inv)
+            out["last"].append(ctx.ipa_last())
+            out["L"][j], out["R"][j], out["value_l"][j], out["value_r"][j] = l, r, vl, vr
+            out["u"][j], out["u_inv"][j] = np.ascontiguousarray(u, np.uint64).reshape(4), np.ascontiguousarray(u_inv, np.uint64).reshape(4)
+        out["g"] = ctx.ipa_final_generator_device(d_g, out["u"][t:], k - t)
+        out["last"].append(ctx.ipa_last())
+        out["c"] = d_p.download(np.uint64, 32).copy()
+        out["b"] = d_b.download(np.uint64, 32).copy()
         return out
     finally:
         for d in bufs:

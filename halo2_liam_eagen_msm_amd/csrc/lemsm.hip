@@ -16,6 +16,7 @@
 #include "../../include/lemsm.h"
 #include "../../include/lemsm_srs.h"
 #include "../../include/lemsm_ipa.h"
+#include "../../include/lemsm_ipa_tail.h"
 #include "arena.hpp"
 #include "timed_run.hpp"
 #include "ntt_schedule.hpp"
@@ -40,6 +41,7 @@
 #include "open.cuh"
 #include "ecfft.cuh"
 #include "ipa.cuh"
+#include "ipa_tail.cuh"
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <functional>
@@ -2808,3 +2810,4 @@ int lemsm_debug_xyzz29_raw(lemsm_ctx* ctx, int curve, int op, const int32_t* acc
 #include "open_abi.inc"
 #include "ecfft_abi.inc"
 #include "ipa_abi.inc"
+#include "ipa_tail_abi.inc"
