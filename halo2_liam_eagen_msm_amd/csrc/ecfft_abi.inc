@@ -71,10 +71,10 @@ int lemsm_ecfft_device(lemsm_ctx* ctx, int curve, const void* d_in_affine, uint3
   if (d_in_affine != d_out_affine && poly_overlap(d_in_affine, n * 64, d_out_affine, n * 64))
     return fail(ctx, LEMSM_ERR_BAD_ARG, "ecfft: d_out overlaps d_in (only d_out == d_in is allowed)");
   const EcFigures f = ecfft_figures(logn, scale != nullptr);
-  ctx->ec_last = EcfftLast{0, f.muls, f.adds, f.ops};
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = validate_points(ctx, curve, d_in_affine, n);
   if (rc) { if (rc == LEMSM_ERR_BAD_ARG && bad_index) *bad_index = ctx->bad_index; return rc; }
+  ctx->ec_last = EcfftLast{0, f.muls, f.adds, f.ops};   // behind every refusal: a refused call leaves the last record alone
   hipStream_t st = ctx->stream;
   host::fe p2[32];                                    // omega^(2^b)
   for (u32 b = 0; b < 32; b++) p2[b] = b ? HFr::sqr(p2[b - 1]) : poly_fe(omega);

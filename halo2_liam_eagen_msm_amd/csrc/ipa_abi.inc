@@ -102,9 +102,9 @@ int lemsm_ipa_round_device(lemsm_ctx* ctx, int curve, const void* d_p, const voi
   if (!d_p || !d_g || !out_l || !out_r) return LEMSM_ERR_BAD_ARG;
   if (d_b ? (!out_value_l || !out_value_r) : (out_value_l || out_value_r))
     return fail(ctx, LEMSM_ERR_BAD_ARG, "ipa_round: the value outputs go with d_b (both with it, none without)");
-  ctx->ipa_last = IpaLast{0, 0, 2 * (u64)half, d_b ? 2 * (u64)half : 0};
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = validate_points(ctx, curve, d_g, 2 * half); if (rc) return rc;
+  ctx->ipa_last = IpaLast{0, 0, 2 * (u64)half, d_b ? 2 * (u64)half : 0};   // behind every refusal: a refused call leaves the record alone
   hipStream_t st = ctx->stream;
   const u32 h = (u32)half, nblk = (h + 255) / 256;
   u64 values[8] = {0, 0, 0, 0, 0, 0, 0, 0}, l[12], r[12];
@@ -149,9 +149,9 @@ int lemsm_ipa_fold_device(lemsm_ctx* ctx, int curve, void* d_p, void* d_b, void*
   const host::fe uu[2] = {poly_fe(u), poly_fe(u_inv)};
   if (!HFr::eq(HFr::mul(uu[0], uu[1]), HFr::one())) return fail(ctx, LEMSM_ERR_BAD_ARG, "ipa_fold: u u_inv is not 1");
   const u64 field = (d_p ? (u64)half : 0) + (d_b ? (u64)half : 0);
-  ctx->ipa_last = IpaLast{0, d_g ? (u64)half : 0, 0, field};
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (d_g) { rc = validate_points(ctx, curve, d_g, 2 * half); if (rc) return rc; }
+  ctx->ipa_last = IpaLast{0, d_g ? (u64)half : 0, 0, field};
   hipStream_t st = ctx->stream;
   const u32 h = (u32)half;
   IpaFoldCarve c;

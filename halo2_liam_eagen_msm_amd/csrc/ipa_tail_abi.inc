@@ -74,9 +74,9 @@ int lemsm_ipa_round_unfolded_device(lemsm_ctx* ctx, int curve, const void* d_p, 
   if (m > ((u64)1 << IPA_MAX_K)) return fail(ctx, LEMSM_ERR_BAD_ARG, "ipa_round_unfolded: 2 half 2^q at most 2^24");
   if (d_b ? (!out_value_l || !out_value_r) : (out_value_l || out_value_r))
     return fail(ctx, LEMSM_ERR_BAD_ARG, "ipa_round_unfolded: the value outputs go with d_b (both with it, none without)");
-  ctx->ipa_last = IpaLast{0, 0, m, m + (d_b ? 2 * (u64)half : 0)};
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = validate_points(ctx, curve, d_G, (size_t)m); if (rc) return rc;
+  ctx->ipa_last = IpaLast{0, 0, m, m + (d_b ? 2 * (u64)half : 0)};
   hipStream_t st = ctx->stream;
   const u32 h = (u32)half, nblk = (h + 255) / 256, ns = 1u << q;
   u64 values[8] = {0, 0, 0, 0, 0, 0, 0, 0}, l[12], r[12];
@@ -128,9 +128,9 @@ int lemsm_ipa_final_generator_device(lemsm_ctx* ctx, int curve, const void* d_G,
   host::fe tab[IPA_MAX_K + 1];
   rc = ipa_tail_challenges(ctx, "ipa_final_generator", u_prev, q, tab); if (rc) return rc;
   const u32 ns = 1u << q;
-  ctx->ipa_last = IpaLast{0, 0, ns, 0};
   HIPCHK(ctx, hipSetDevice(ctx->device));
   rc = validate_points(ctx, curve, d_G, ns); if (rc) return rc;
+  ctx->ipa_last = IpaLast{0, 0, ns, 0};
   hipStream_t st = ctx->stream;
   u64 jac[12], aff[8];
   IpaTailCarve c;

@@ -75,7 +75,9 @@ int lemsm_ipa_s_device(lemsm_ctx* ctx, const uint64_t* u, uint32_t k, const uint
 /* Device time (ms: HIP events around the launches on the context's stream, plus the MSM core's own time for a round) of the
    last lemsm_ipa_*_device call and its figures: a round has msm_pairs = 2 half and field_mults = 2 half (0 without d_b); a
    fold has point_muls = half (0 without d_g) and field_mults = half for each of d_p, d_b; powers and s report the time alone.
-   Summed over the k rounds of an opening with all three vectors these are the plan's totals. */
+   Summed over the k rounds of an opening with all three vectors these are the plan's totals.  A refused call
+   (LEMSM_ERR_BAD_ARG, a generator off the curve under validate_points included) leaves the record as it was; a
+   lemsm_ipa_powers_device with n = 0 sets ms to 0.0. */
 int lemsm_ipa_last(const lemsm_ctx* ctx, double* ms, uint64_t* point_muls, uint64_t* msm_pairs, uint64_t* field_mults);
 
 #ifdef __cplusplus

@@ -57,7 +57,8 @@ int lemsm_ecfft(lemsm_ctx* ctx, int curve, const uint64_t* in_affine, uint32_t l
    lemsm_bases_* or lemsm_fixed_*.  (g_to_lagrange, poly/kzg/commitment.rs; ParamsKZG::setup, from_parts, downsize) */
 int lemsm_srs_to_lagrange_device(lemsm_ctx* ctx, int curve, const void* d_g_affine, size_t n_g, uint32_t logn, void* d_out_affine);
 /* Device time (ms, HIP events around the launches on the context's stream) of the last lemsm_ecfft* /
-   lemsm_srs_to_lagrange_device call and the plan's figures for it.  (best_fft on FftGroup; g_to_lagrange) */
+   lemsm_srs_to_lagrange_device call and the plan's figures for it.  A refused call (LEMSM_ERR_BAD_ARG, a point off the curve
+   under validate_points included) leaves the record as it was.  (best_fft on FftGroup; g_to_lagrange) */
 int lemsm_ecfft_last(const lemsm_ctx* ctx, double* ms, uint64_t* point_muls, uint64_t* point_adds, uint64_t* group_ops);
 
 #ifdef __cplusplus

@@ -1,5 +1,6 @@
-"""The inputs and expected values of scenarios 8 to 16 of tests/concurrency_child.py (the threading contract on the resident
-polynomial entries; 14 to 16: on the multiplicity entry), built without a context: every builder is a pure function of its
+"""The inputs and expected values of scenarios 8 to 20 of tests/concurrency_child.py (the threading contract on the resident
+polynomial entries; 14 to 16: on the multiplicity entry; 17 to 20: on the transform over G1 and the inner-product argument's
+entries, against tests/ecfft_ref.py, ipa_ref.py and ipa_tail_ref.py), built without a context: every builder is a pure function of its
 arguments, every expected value comes from the big-integer references the entries' own tests use (oracle.divisor's best_fft and
 PolyRing, tests/domain_ref.py, gate_ref.py, perm_ref.py, lookup_ref.py, logup_ref.py, open_ref.py, rhs_ref.py).
 tests/test_concurrency_cases.py holds the builders without a GPU; concurrency_child.py turns a Spec into a library call on a
@@ -18,11 +19,15 @@ import hashlib
 import numpy as np
 
 from halo2_liam_eagen_msm_amd import _lib, api
+from oracle import cref
 from oracle.divisor import best_fft
 
 import domain_ref
+import ecfft_ref
 import fuzz_resident as fr
 import gate_ref
+import ipa_ref
+import ipa_tail_ref
 import logup_ref
 import lookup_ref
 import open_ref
@@ -429,3 +434,157 @@ def scenario16():
          multiplicities(1604, lens, t, MONT)]
     b = [multiplicities(1650, [1000, 300], 600, MONT), multiplicities(1651, [0, 1500], 333, CANON, below=1 << 16), multiplicities(1652, [2049], 1025, MONT)]
     return {"A": a, "B": b}
+
+
+# ---- scenarios 17 to 20: the transform over G1 and the inner-product argument ---------------------------------------------------
+# Points are rows of fuzz_resident's pool (4096 sums P_a + Q_b: unknown discrete logarithms, with repeats); every expected value
+# is ecfft_ref's, ipa_ref's or ipa_tail_ref's.  L and R are Jacobian points whose limbs vary from run to run: a Spec expects their
+# canonical bytes (cref.jac_to_canonical), which concurrency_child.py takes of what the entry returns.
+def _canonical(jac):
+    return np.frombuffer(cref.jac_to_canonical(ecfft_ref.CID, np.ascontiguousarray(jac, np.uint64)), np.uint8).copy()
+
+
+def ecfft(seed, logn, inverse=False, scale=True, plant=None, lagrange_rows=None):
+    """ecfft_device out of place (lagrange_rows: srs_to_lagrange_device on that many bases); plant: "omega" (a root of twice the
+    order) or "overlap" (the output 64 bytes into the input): refused, the output untouched"""
+    rng = _rng(seed, 17)
+    n = 1 << logn
+    rows = lagrange_rows or n
+    pts = fr._pool_rows(rng, rows)
+    pts[int(rng.integers(0, n))] = 0                                   # an identity among them
+    inverse = inverse or lagrange_rows is not None
+    w = domain_ref.omega(logn)
+    if inverse:
+        w = pow(w, -1, P)
+    sc = pow(n, -1, P) if lagrange_rows else (2 + fr._fe_int(rng) % (P - 2) if scale else None)
+    note = "logn=%d rows=%d inverse=%s scale=%s" % (logn, rows, inverse, sc is not None)
+    kw = dict(logn=logn, rows=rows, omega=_fe(w), scale=None if sc is None else _fe(sc), lagrange=lagrange_rows is not None, overlap=plant == "overlap")
+    if plant:
+        if plant == "omega":
+            kw["omega"] = _fe(domain_ref.omega(logn + 1))
+        return Spec("ecfft", note + " plant=" + plant, {"in": pts}, [("out", 2 * n, b"", None)], status=BAD_ARG, **kw)
+    want = ecfft_ref.ecfft(pts[:n], w, logn, sc)
+    return Spec("ecfft", note, {"in": pts}, [("out", 2 * n, want.tobytes(), None)], **kw)
+
+
+def _ipa_vectors(rng, half, rows=None):
+    p, b = _ints(_rand(rng, 2 * half)), _ints(_rand(rng, 2 * half))
+    g = fr._pool_rows(rng, rows or 2 * half)
+    g[int(rng.integers(0, g.shape[0]))] = 0
+    return p, b, g
+
+
+def ipa_round(seed, half, off_curve=False, shared=None):
+    """ipa_round_device with b; off_curve: one generator's x spoilt (refused under validate_points, with its index); shared:
+    (p, b, g) in place of drawn vectors"""
+    rng = _rng(seed, 18)
+    p, b, g = shared or _ipa_vectors(rng, half)
+    note = "half=%d" % half
+    ins = {"p": _mont(p), "b": _mont(b), "g": g}
+    if off_curve:
+        ins["g"], index = fr._off_curve(g, rng)
+        return Spec("round", note + " generator %d off the curve" % index, ins, [], small=[], status=BAD_ARG, index=index, half=half)
+    L, Rr, vl, vr = ipa_ref.round_(p, b, g, half)
+    return Spec("round", note, ins, [], small=[_canonical(L), _canonical(Rr), _fe(vl), _fe(vr)], half=half)
+
+
+def ipa_fold(seed, half, bad_inverse=False):
+    """ipa_fold_device of p, b and g in place; bad_inverse: u u_inv != 1, refused with the three vectors untouched"""
+    rng = _rng(seed, 19)
+    p, b, g = _ipa_vectors(rng, half)
+    u = 1 + fr._fe_int(rng) % (P - 1)
+    u_inv = pow(u, -1, P)
+    raw_p, raw_b = _mont(p), _mont(b)
+    note = "half=%d" % half
+    if bad_inverse:
+        outs = [("p", 2 * half, raw_p.tobytes(), raw_p), ("b", 2 * half, raw_b.tobytes(), raw_b), ("g", 4 * half, g.tobytes(), g)]
+        return Spec("fold", note + " u u_inv != 1", {}, outs, status=BAD_ARG, half=half, u=_fe(u), u_inv=_fe((u_inv + 1) % P))
+    fp, fb = ipa_ref.fold_field(p, b, half, u)
+    fg = np.concatenate([ipa_ref.fold_generators(g, half, u), g[half:]])
+    outs = [("p", 2 * half, _mont(fp + p[half:]).tobytes(), raw_p), ("b", 2 * half, _mont(fb + b[half:]).tobytes(), raw_b), ("g", 4 * half, fg.tobytes(), g)]
+    return Spec("fold", note, {}, outs, half=half, u=_fe(u), u_inv=_fe(u_inv))
+
+
+def ipa_round_unfolded(seed, half, q, zero_challenge=False, shared=None):
+    """ipa_round_unfolded_device on 2 half 2^q generators; zero_challenge: one of u_prev is 0, refused; shared: (p, b, G)"""
+    rng = _rng(seed, 20)
+    m = (2 * half) << q
+    p, b, G = shared or _ipa_vectors(rng, half, m)
+    u = [1 + fr._fe_int(rng) % (P - 1) for _ in range(q)]
+    ins = {"p": _mont(p[:2 * half]), "b": _mont(b[:2 * half]), "G": G[:m]}
+    note = "half=%d q=%d" % (half, q)
+    if zero_challenge:
+        u[int(rng.integers(0, q))] = 0
+        return Spec("uround", note + " a zero challenge", ins, [], small=[], status=BAD_ARG, half=half, q=q, u=_mont(u))
+    L, Rr, vl, vr = ipa_tail_ref.round_unfolded(p[:2 * half], b[:2 * half], G[:m], half, u)
+    return Spec("uround", note, ins, [], small=[_canonical(L), _canonical(Rr), _fe(vl), _fe(vr)], half=half, q=q, u=_mont(u))
+
+
+def ipa_final_generator(seed, q, shared=None):
+    rng = _rng(seed, 21)
+    G = shared if shared is not None else fr._pool_rows(rng, 1 << q)
+    u = [1 + fr._fe_int(rng) % (P - 1) for _ in range(q)]
+    return Spec("final", "q=%d" % q, {"G": G[:1 << q]}, [], small=[ipa_tail_ref.final_generator(G[:1 << q], u)], q=q, u=_mont(u))
+
+
+OPEN_K = 10
+
+
+def opening_challenge(canonical_l, canonical_r):
+    """the challenge both threads of scenario 17 and the reference derive from a round's L and R (their canonical bytes)"""
+    return int.from_bytes(hashlib.sha256(bytes(canonical_l) + bytes(canonical_r)).digest(), "little") % P or 1
+
+
+def scenario17():
+    """the inputs of one opening of 2^10 coefficients and what ipa_ref.open_ makes of it, and thread A's transform at logn 8"""
+    rng = _rng(1700, 22)
+    n = 1 << OPEN_K
+    p, g = _ints(_rand(rng, n)), fr._pool_rows(rng, n)
+    x = fr._fe_int(rng)
+    b = ipa_ref.powers(x, n)
+    Ls, Rs, vls, vrs, us, c, b_fin, g_fin = ipa_ref.open_(p, b, g, lambda j, L, Rr, vl, vr: opening_challenge(_canonical(L), _canonical(Rr)))
+    return {"p": _mont(p), "g": g, "x": _fe(x), "k": OPEN_K, "fold_rounds": 4,
+            "want": {"u": _mont(us), "c": _fe(c), "b": _fe(b_fin), "value_l": _mont(vls), "value_r": _mont(vrs), "g": np.array(g_fin, np.uint64),
+                     "L": np.stack([_canonical(v) for v in Ls]), "R": np.stack([_canonical(v) for v in Rs])},
+            "ecfft": ecfft(1701, 8, inverse=True), "options": {"A": {}, "B": {"field": 1, "window_bits": 13}}}
+
+
+SHARED_ROWS = 1 << 12
+
+
+def scenario18():
+    """one G of 2^12 rows and one p (and b): the five read-only calls both contexts make on the same pointers"""
+    rng = _rng(1800, 23)
+    half = SHARED_ROWS // 2
+    p, b, G = _ipa_vectors(rng, half)
+    shared = (p, b, G)
+    # the transforms read the first rows of the shared G: ecfft_device at logn 8 and srs_to_lagrange_device at logn 9
+    w8, w9, s8 = domain_ref.omega(8), pow(domain_ref.omega(9), -1, P), 2 + fr._fe_int(rng) % (P - 2)
+    ec = Spec("ecfft", "logn=8 shared", {"G": G}, [("out", 512, ecfft_ref.ecfft(G[:256], w8, 8, s8).tobytes(), None)],
+              logn=8, rows=256, omega=_fe(w8), scale=_fe(s8), lagrange=False, overlap=False)
+    lag = Spec("ecfft", "logn=9 rows=%d shared" % SHARED_ROWS, {"G": G}, [("out", 1024, ecfft_ref.ecfft(G[:512], w9, 9, pow(512, -1, P)).tobytes(), None)],
+               logn=9, rows=SHARED_ROWS, omega=_fe(w9), scale=_fe(pow(512, -1, P)), lagrange=True, overlap=False)
+    return [ipa_round(1801, half, shared=shared), ipa_round_unfolded(1802, 256, 3, shared=shared), ipa_final_generator(1803, 9, shared=G), ec, lag]
+
+
+def scenario19():
+    """A: good calls and refusals in turn (validate_points = 1 on its context); B: good calls only"""
+    a = [ipa_round(1900, 129),
+         ipa_round(1901, 129, off_curve=True),
+         ipa_round(1901, 129),
+         ipa_fold(1902, 65, bad_inverse=True),
+         ipa_fold(1902, 65),
+         ipa_round_unfolded(1903, 9, 2, zero_challenge=True),
+         ipa_round_unfolded(1903, 9, 2),
+         ecfft(1904, 6, plant="omega"),
+         ecfft(1904, 6),
+         ecfft(1905, 5, plant="overlap"),
+         ecfft(1905, 5)]
+    b = [ipa_round(1950, 257), ipa_fold(1951, 33), ecfft(1952, 7, inverse=True), ipa_round_unfolded(1953, 16, 2), ipa_final_generator(1954, 5)]
+    return {"A": a, "B": b, "options": {"A": {"validate_points": 1}, "B": {}}}
+
+
+def scenario20(k):
+    """context k's list, before its cyclic shift (the msm_device call is made by the child: its oracle is the C one)"""
+    s = 2000 + 20 * k
+    return [ecfft(s, 7), ipa_round(s + 1, 257), ipa_fold(s + 2, 65), ipa_round_unfolded(s + 3, 64, 2), fft(s + 4, 10)]

@@ -2,7 +2,7 @@
 "Threading") on device 0.  Usage: python concurrency_child.py ROOT SCENARIO.  Not a test module.
 
 Every expected value comes from the oracle (oracle/cref.py, tests/rhs_ref.py, tests/column_ref.py, oracle/divisor.py; for
-scenarios 8-16, the resident polynomial entries, from the big-integer references tests/concurrency_cases.py builds on) and is
+scenarios 8-20, the resident entries, from the big-integer and oracle references tests/concurrency_cases.py builds on) and is
 computed single-threaded before any thread starts.  The threads are threading.Thread; ctypes releases the GIL for the
 duration of a CDLL call, so the library calls of different threads do overlap; all threads leave one threading.Barrier
 before their first call and every call's (start, end) on time.perf_counter() is kept.  Every context has ws_canary = 1.
@@ -97,6 +97,10 @@ def normalise(f):
 def canon_points(cid, rows):
     rows = np.ascontiguousarray(rows, np.uint64).reshape(-1, 12)
     return b"".join(cref.jac_to_canonical(cid, r) for r in rows)
+
+
+def canon_bytes(jac):
+    return np.frombuffer(cref.jac_to_canonical(0, np.ascontiguousarray(jac, np.uint64)), np.uint8).copy()
 
 
 class Call:
@@ -583,7 +587,7 @@ def filled(ctx, n_elems, payload, keep):
 
 def upload_inputs(ctx, sp, keep):
     """name -> (buffer, the bytes it holds) of a Spec's resident inputs"""
-    return {k: filled(ctx, a.shape[0], a, keep) for k, a in sp.ins.items()}
+    return {k: filled(ctx, a.nbytes // 32, a, keep) for k, a in sp.ins.items()}      # (elements of 32 bytes: a point takes two)
 
 
 def _open_args(sp, ins):
@@ -642,6 +646,24 @@ def launcher(ctx, sp, ins, o):
             ctx.lookup_multiplicities_device(cols, a["lens"], p["T"], a["t"], a["form"], out)
             return [np.array(ctx.sort_last(), np.uint32)]
         return run_mult
+    if sp.op == "ecfft":
+        src = p["in"] if "in" in p else p["G"]
+        dst = src + 64 if a["overlap"] else o[0].ptr
+        if a["lagrange"]:
+            return lambda: ctx.srs_to_lagrange_device(src, a["rows"], a["logn"], dst) or []
+        return lambda: ctx.ecfft_device(src, a["logn"], a["omega"], a["scale"], dst) or []
+    if sp.op in ("round", "uround"):
+        def run_round():
+            if sp.op == "round":
+                L, Rr, vl, vr = ctx.ipa_round_device(p["p"], p["b"], p["g"], a["half"])
+            else:
+                L, Rr, vl, vr = ctx.ipa_round_unfolded_device(p["p"], p["b"], p["G"], a["half"], a["u"], a["q"])
+            return [canon_bytes(L), canon_bytes(Rr), vl, vr]         # (a Jacobian triple is not unique: its canonical bytes are)
+        return run_round
+    if sp.op == "fold":
+        return lambda: ctx.ipa_fold_device(o[0].ptr, o[1].ptr, o[2].ptr, a["half"], a["u"], a["u_inv"]) or []
+    if sp.op == "final":
+        return lambda: [ctx.ipa_final_generator_device(p["G"], a["u"], a["q"])]
     cap = sp.outs[0][1]                                              # the C entries themselves: the capacity is the Spec's, exactly
     if sp.op == "lincomb":
         ptrs, ln, J, cf, lwp, k_low = _open_args(sp, ins)
@@ -966,14 +988,167 @@ def scenario16():
     a.close(); long_lived.close()
 
 
+# ---- scenarios 17-20: the transform over G1 and the inner-product argument ------------------------------------------------------------
+def ipa_figures(ctx):
+    """what a call leaves in its context beside its results, times apart: ipa_last, ecfft_last, the accumulate count"""
+    return ctx.ipa_last()[1:] + ctx.ecfft_last()[1:] + (ctx.last_timing()[2],)
+
+
+def scenario17():
+    case = cases.scenario17()
+    want, k, t = case["want"], case["k"], case["fold_rounds"]
+
+    def challenge(j, L, Rr, vl, vr):
+        u = cases.opening_challenge(canon_bytes(L), canon_bytes(Rr))
+        return fe(u), fe(pow(u, -1, P))
+
+    def opening_call(ctx, unfolded, who):
+        def fn():
+            if unfolded:
+                out = api.ipa_open_unfolded(case["p"], case["g"], case["x"], challenge, t, ctx=ctx)
+            else:
+                out = api.ipa_open(case["p"], case["g"], case["x"], challenge, ctx=ctx)
+            figures = np.array([rec[1:] for rec in out["last"]], np.uint64)
+            return [out[name] for name in ("u", "c", "b", "value_l", "value_r", "g")] + [np.stack([canon_bytes(v) for v in out[name]]) for name in ("L", "R")] + [figures]
+
+        def verify(raw):
+            for name, got in zip(("u", "c", "b", "value_l", "value_r", "g", "L", "R"), raw):
+                need(np.ascontiguousarray(got).tobytes() == want[name].tobytes(), who, "the opening's %s differs from the reference" % name)
+            plan = api.ipa_tail_plan(k, t) if unfolded else api.ipa_plan(k)
+            need(tuple(int(v) for v in raw[8].sum(axis=0)) == (plan["point_muls"], plan["msm_pairs"], plan["field_mults"]), who, "ipa_last summed is not the plan")
+        return Call("ipa_open%s k=%d" % ("_unfolded" if unfolded else "", k), "ipa_open", fn, verify)
+
+    lanes, alone, lists = [], {}, {}
+    for name, unfolded in (("A", False), ("B", True)):
+        c = new_ctx()
+        for opt, v in case["options"][name].items():
+            c.set_option(opt, v)
+        calls = [opening_call(c, unfolded, "context %s:" % name)] + (resident_calls(c, [case["ecfft"]], who="context A: ") if name == "A" else [])
+        for rnd in range(2):                                           # what each call leaves when made alone
+            alone[name] = []
+            for call in calls:
+                call.fn()
+                alone[name].append(ipa_figures(c))
+        for i, call in enumerate(calls):
+            def after(raw, r, c=c, i=i, name=name, call=call):
+                got = ipa_figures(c)
+                need(got == alone[name][i], "context %s, %s: ipa_last / ecfft_last / accumulate count %s are not this context's own %s" % (name, call.name, got, alone[name][i]))
+            call.after = after
+        lists[name] = calls
+        lanes.append(Lane("context %s %s" % (name, case["options"][name]), calls, ROUNDS[17][len(lanes)]))
+    need(alone["A"][0] != alone["B"][0], "the two contexts leave the same figures: the check could not tell them apart", alone)
+    serial_then_concurrent(17, lanes)
+    for x, y in zip(lists["A"][0].ref[:8], lists["B"][0].ref[:8]):     # the folded and the unfolded opening: the same bytes
+        need(np.array_equal(x, y), "ipa_open and ipa_open_unfolded differ")
+
+
+def scenario18():
+    specs = cases.scenario18()
+    a, b = new_ctx(), new_ctx()
+    rnd = specs[0]
+    shared = upload_inputs(a, rnd, KEEP)                               # p, b and G uploaded once through A; both contexts read the same pointers
+    for sp in specs[1:]:
+        for name, arr in sp.ins.items():
+            whole = rnd.ins[{"G": "g"}.get(name, name)]
+            need(np.array_equal(arr, whole[:arr.shape[0]]), "%s does not read the shared %s" % (sp.op, name))
+    ins_of = lambda sp: {name: shared[{"G": "g"}.get(name, name)] for name in sp.ins}      # noqa: E731
+    lanes = []
+    for k, c in enumerate((a, b)):
+        calls = [resident_call(c, sp, ins=ins_of(sp), who="context %d: " % k) for sp in specs]
+        lanes.append(Lane("context %d" % k, calls[2 * k:] + calls[:2 * k], ROUNDS[18][k]))
+    serial_then_concurrent(18, lanes)
+    for name, (buf, image) in shared.items():
+        need(np.array_equal(buf.download(np.uint8), image), "the shared input %s, or the zone behind it, was written" % name)
+    b.close(); a.close()
+
+
+def scenario19():
+    case = cases.scenario19()
+    a = new_ctx()
+    for opt, v in case["options"]["A"].items():
+        a.set_option(opt, v)
+    ins_a = [upload_inputs(a, sp, KEEP) for sp in case["A"]]
+    steps = [resident_call(a, sp, ins=ins, who="A: ") for sp, ins in zip(case["A"], ins_a)]
+    alone = []
+    for rnd in range(2):                                               # what each step leaves in A's context when A is alone
+        alone = []
+        for call in steps:
+            call.verify(call.fn())
+            alone.append(state_of(a))
+    bad = [k for k, sp in enumerate(case["A"]) if sp.error]
+    need(len(bad) == 5 and len({alone[k][0] for k in bad}) == 5 and all(alone[k][0] for k in bad), "alone: the failing calls do not leave five messages", alone)
+    for k in bad:
+        if case["A"][k].index is not None:
+            need(alone[k][1] == case["A"][k].index, "alone: last_bad_index %d after '%s'" % (alone[k][1], steps[k].name))
+
+    def a_fn(k):
+        def fn():
+            raw = steps[k].fn()
+            steps[k].verify(raw)                                       # status, index, the outputs (untouched when refused) against the reference
+            got = state_of(a)
+            need(got == alone[k], "A: after '%s' the context holds %s, alone it held %s" % (steps[k].name, got, alone[k]))
+            return []
+        return fn
+    calls_a = [Call("A step %d: %s" % (k, steps[k].name), "errors", a_fn(k), None) for k in range(len(steps))]
+    rounds_b = ROUNDS[19][1]
+    long_lived = new_ctx()
+    box = {"round": -1, "ctx": long_lived, "own": False}
+    box["calls"] = [resident_call(long_lived, sp, who="B: ") for sp in case["B"]]
+
+    def enter():
+        box["round"] += 1
+        if box["round"] >= rounds_b - SHORT_LIVED:
+            box["ctx"], box["bufs"], box["own"] = new_ctx(), [], True
+            box["calls"] = [resident_call(box["ctx"], sp, keep=box["bufs"], who="B, short-lived context: ") for sp in case["B"]]
+        return []
+
+    def b_step(k):
+        def fn():
+            c = box["calls"][k]
+            raw = c.fn()
+            c.verify(raw)                                              # every one of B's results against the reference
+            got = state_of(box["ctx"])
+            need(int(raw[-1][0]) == 0 and got == ("", 0, 0), "B: a context that only made good calls returned status %d and holds" % int(raw[-1][0]), got)
+            return []
+        return fn
+
+    def leave():
+        if box["own"]:
+            for buf in box.pop("bufs"):
+                buf.free()
+            box.pop("calls"); box.pop("ctx").close()
+        return []
+    named = [("enter", enter)] + [("%s %s" % (sp.op, sp.note), b_step(k)) for k, sp in enumerate(case["B"])] + [("leave", leave)]
+    calls_b = [Call(nm, "lifetime", f, None) for nm, f in named]
+    for c in calls_a + calls_b:
+        c.ref = False                                                  # (nothing to compare: the step checks itself)
+    lanes = [Lane("A: good and refused calls", calls_a, ROUNDS[19][0]), Lane("B: good calls, then a context per round", calls_b, rounds_b)]
+    wall = run_concurrent(lanes)
+    need(box["round"] == rounds_b - 1 and box["own"] and "ctx" not in box, "B did not end on a short-lived context")
+    finish(19, lanes, wall)
+    for sp, ins in zip(case["A"], ins_a):
+        for name, (buf, image) in ins.items():
+            need(np.array_equal(buf.download(np.uint8), image), "A: %s (%s): the input %s, or the zone behind it, was written" % (sp.op, sp.note, name))
+    a.close(); long_lived.close()
+
+
+def scenario20():
+    lanes = []
+    for k in range(4):
+        c = new_ctx()
+        fam = resident_calls(c, cases.scenario20(k), who="context %d: " % k) + [msm_call(c, 0, 1000, msm_inputs(0, 1000, 20100 + 10 * k))]
+        lanes.append(Lane("context %d" % k, fam[k:] + fam[:k], ROUNDS[20][k]))
+    serial_then_concurrent(20, lanes)
+
+
 SHORT_LIVED = 10
 # rounds of each thread's list (chosen so that the threads of a scenario run about equally long: profiles/concurrency/NOTES.md)
 ROUNDS = {1: (40, 3), 2: (25, 25), 3: (10, 10, 10, 10), 4: (25, 25), 5: (12, 60), 6: (10, 30),
           8: (90, 30), 9: (40, 35), 10: (15, 15, 15, 15), 11: (40, 40), 12: (26, 50), 13: (10, 43),
-          14: (40, 40), 15: (30, 30), 16: (16, 30)}
+          14: (40, 40), 15: (30, 30), 16: (16, 30), 17: (10, 20), 18: (8, 8), 19: (18, 24), 20: (6, 6, 6, 6)}
 SCENARIOS = {1: scenario1, 2: scenario2, 3: scenario3, 4: scenario4, 5: scenario5, 6: scenario6, 7: scenario7,
              8: scenario8, 9: scenario9, 10: scenario10, 11: scenario11, 12: scenario12, 13: scenario13,
-             14: scenario14, 15: scenario15, 16: scenario16}
+             14: scenario14, 15: scenario15, 16: scenario16, 17: scenario17, 18: scenario18, 19: scenario19, 20: scenario20}
 
 if __name__ == "__main__":
     which = int(sys.argv[2])

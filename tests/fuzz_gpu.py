@@ -24,6 +24,10 @@ the C ABI and compares with a reference that is not the library.  The families (
                       with the references of the entries' own test modules, behind 0xFF-filled outputs.  These entries keep
                       state between calls (the shared twiddle table, the re-carved arenas, the words a call resets), which
                       the chains and the mix with every other family on one context exercise
+    srs, ipa, ipa_tail
+                      the transform over G1 / g_to_lagrange, the inner-product argument's rounds and its late rounds over
+                      unfolded generators (tests/fuzz_resident.py too): chains whose rounds run the MSM core under this soak's
+                      drawn pipeline options, which are set before every case -- the main point of these three families
 Input shapes aim at the rare branches: P next to -P with equal scalars (cancellation), repeated points
 (doubling), identity points, all-equal and tiny scalars, scalars = order-1.  The families that decompose scalars in a
 negabase (lhs, scalar_witness, rhs, lhs_witness) take their usual short list of bases in three cases out of four; in the
@@ -67,7 +71,8 @@ NAMES = list(OPTION_DRAWS)
 FAMILY_P = [("witness", 0.12), ("scalar_witness", 0.06), ("fixed", 0.08), ("rhs", 0.04), ("fraction_sums", 0.03), ("regfn", 0.04),
             ("lhs_witness", 0.03),
             ("poly", 0.04), ("domain", 0.04), ("gate", 0.03), ("column", 0.03), ("perm", 0.04), ("lookup", 0.04),
-            ("open", 0.03), ("logup", 0.03)]
+            ("open", 0.03), ("logup", 0.03),
+            ("srs", 0.02), ("ipa", 0.02), ("ipa_tail", 0.02)]
 NEW_FAMILIES = ("fixed", "rhs", "fraction_sums", "regfn", "lhs_witness")
 RESIDENT_FAMILIES = fuzz_resident.FAMILIES      # appended to FAMILY_P: the intervals of the families before them stay where they were
 LAST_KINDS = {}        # kinds_seen of the last main() call

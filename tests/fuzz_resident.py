@@ -10,6 +10,18 @@
               on both sides of the one-segment-per-thread limit of k_kd_scan
     logup     lookup_multiplicities against tests/logup_ref.py: ragged and NULL columns, tables laden with duplicates, a planted
               missing value with a good call behind it in the same chain
+    srs       ecfft_device (or the host twin) and srs_to_lagrange_device against tests/ecfft_ref.py: forward and inverse, scaled
+              (0, 1, r - 1 among the scales) or not, in place or not, identities, opposite and constant inputs; byte for byte up to
+              2^8 points, the linear-combination identity up to 2^12; planted refusals (an omega of the wrong order, a non-canonical
+              scale, partial overlap, a point off the curve) with a good call behind each
+    ipa       ipa_round_device, ipa_fold_device (every subset of p, b, g), ipa_s_device, ipa_powers_device against tests/ipa_ref.py;
+              successive halves regrow and shrink ipa_ws; three cases in ten walk one opening, each round on the buffers the fold
+              before it left on the device; identities among the generators, g_lo = u g_hi and g_lo = -u g_hi, p all zero;
+              planted refusals (u u_inv != 1, u = 0, a non-canonical u, value outputs without b, a generator off the curve)
+    ipa_tail  ipa_round_unfolded_device and ipa_final_generator_device against tests/ipa_tail_ref.py on (half, q) with at most
+              2^13 generators; planted refusals (a zero challenge, more than 2^24 generators)
+The last three run the MSM core under whatever options the soak has drawn; after every step ipa_last or ecfft_last is what
+the headers' relations give, and after a round lemsm_last_timing's accumulate count is that of its two multiexps run alone.
 These entries keep state between calls -- the twiddle table five of them share, the arenas poly_ws and poly_stage every call
 carves anew, the words a call must reset, the figures poly_last and sort_last that several families record into -- so a case is
 not one call but a chain of 3 to 8 steps in a drawn order, on the soak's one long-lived context and under its drawn options.
@@ -23,6 +35,7 @@ soak(family, seconds, seed) is the time-bound loop of one family alone on a cont
 tests/fuzz_logup.py are its command lines): case k is drawn from case_rng(seed, k), and a failure prints the
 `seed=... case=...` line that draws it again."""
 import ctypes
+import functools
 import hashlib
 import random
 import time
@@ -30,21 +43,24 @@ import time
 import numpy as np
 
 from halo2_liam_eagen_msm_amd import _lib, api
-from oracle import pyref
+from oracle import cref, pyref
 from oracle.divisor import PolyRing, best_fft
 
 import column_ref
 import domain_ref
+import ecfft_ref
 import gate_ref
+import ipa_ref
+import ipa_tail_ref
 import logup_ref
 import lookup_ref
 import open_ref
 import perm_ref
 import poly_ref
 
-FAMILIES = ("poly", "domain", "gate", "column", "perm", "lookup", "open", "logup")
+FAMILIES = ("poly", "domain", "gate", "column", "perm", "lookup", "open", "logup", "srs", "ipa", "ipa_tail")
 P = pyref.R_BN254
-assert P == perm_ref.P == lookup_ref.P == logup_ref.P == pyref.GRUMPKIN.fp
+assert P == perm_ref.P == lookup_ref.P == logup_ref.P == pyref.GRUMPKIN.fp == ecfft_ref.R_ORDER
 R = 1 << 256
 RI = pow(R, -1, P)
 TOP = 0x30644E72E131A029            # top limb of r: a smaller top limb makes any four limbs canonical
@@ -62,7 +78,9 @@ LIMITS = {"fft_logn": 26, "mul_len": 1 << 26, "kate_len": 1 << 26, "ext_logn": 2
           "gate_code": gate_ref.MAX_CODE, "gate_table": gate_ref.MAX_TABLE, "gate_cols": gate_ref.MAX_COLS, "gate_depth": gate_ref.MAX_DEPTH,
           "perm_logn": perm_ref.MAX_LOGN, "perm_cols": perm_ref.MAX_COLS, "factors": perm_ref.MAX_FACTORS, "lookup_n": lookup_ref.MAX_N,
           "column_rows": 1 << 28, "open_polys": _lib.LEMSM_OPEN_MAX_POLYS, "open_roots": _lib.LEMSM_OPEN_MAX_ROOTS, "open_len": 1 << 28,
-          "logup_cols": logup_ref.MAX_COLS, "logup_rows": 1 << 28}
+          "logup_cols": logup_ref.MAX_COLS, "logup_rows": 1 << 28,
+          "ec_logn": _lib.LEMSM_ECFFT_MAX_LOGN, "ipa_half": 1 << (_lib.LEMSM_IPA_MAX_K - 1), "ipa_k": _lib.LEMSM_IPA_MAX_K,
+          "ipa_n": 1 << _lib.LEMSM_IPA_MAX_K, "tail_m": 1 << _lib.LEMSM_IPA_MAX_K}
 assert open_ref.MAX_ROOTS == _lib.LEMSM_OPEN_MAX_ROOTS and logup_ref.MAX_COLS == 16 and logup_ref.MAX_N == 1 << 28
 
 
@@ -959,6 +977,599 @@ def _run_mult(ctx, cs, k, st):
         cs.mismatch("step %d %s (%s): sort_last %s, poly_last %s; the reference gives %s, %s" % (k, st.op, st.note, ctx.sort_last(), ctx.poly_last()[1:], st.passes, st.figures))
 
 
+# ---- srs, ipa, ipa_tail: shared pieces -------------------------------------------------------------------------------------------
+BAD_ARG = _lib.LEMSM_ERR_BAD_ARG
+BN254 = _lib.BN254_G1
+POOL_SIDE = 64
+EC_EXACT_LOGN, EC_MAX_LOGN = 8, 12                                 # byte for byte up to 2^8 points; the linear-combination identity above
+IPA_EXACT_HALF, IPA_MAX_HALF = 256, 1 << 12                        # a generator fold byte for byte up to 256 pairs
+IPA_HALVES = (1, 2, 3, 7, 8, 9, 63, 64, 65, 255, 256, 257, 1000)   # tests/test_gpu_ipa.py's HALVES
+TAIL_MAX_LOG_M = 13
+P_REFUSAL = 0.15                                                   # per case: one step of it (never the last) is a planted refusal
+NON_CANONICAL = np.full(4, 0xFFFFFFFFFFFFFFFF, np.uint64)
+
+
+@functools.lru_cache(maxsize=None)
+def _point_pool():
+    """4096 points of unknown discrete logarithm, a constant of the module (ecfft_ref.random_grid: 128 scalar multiplications
+    and 4096 additions on the oracle, once): the cases draw rows of it, with repeats"""
+    g = ecfft_ref.random_grid(0x706F6F6C, POOL_SIDE)
+    g.setflags(write=False)
+    return g
+
+
+def _pool_rows(rng, n):
+    return np.array(_point_pool()[rng.integers(0, POOL_SIDE * POOL_SIDE, n)], np.uint64).reshape(n, 8)
+
+
+def _canon(vals):
+    """integers mod r as the (n, 32) canonical scalars msm_device takes"""
+    return _arr([v % P for v in vals]).view(np.uint8).reshape(-1, 32)
+
+
+def _tag(*arrays):
+    """six hex digits of the inputs, for the case line: two cases of equal shapes are told apart"""
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()[:6]
+
+
+def _challenge(rng):
+    return int(_pick(rng, [1, P - 1, 0, 0, 0, 0])) or 1 + _fe_int(rng) % (P - 1)
+
+
+def _log_uniform(rng, top):
+    return max(1, min(top, int(2 ** rng.uniform(0, np.log2(top)))))
+
+
+def _off_curve(g, rng):
+    """a copy of g with the x of one non-identity row spoilt, and that row's index"""
+    off = np.array(g, np.uint64)
+    live = [i for i in range(off.shape[0]) if off[i].any()]
+    i = live[int(rng.integers(0, len(live)))]
+    off[i, 0] ^= np.uint64(1)
+    assert not cref.is_on_curve(ecfft_ref.CID, off[i])
+    return off, i
+
+
+def _status(cs, k, st, rc):
+    """the status against what the step expects; True when the call ran"""
+    if st.error and rc != BAD_ARG:
+        cs.mismatch("step %d %s (%s): status %d, the planted %s must be refused" % (k, st.op, st.note, rc, st.plant))
+    if not st.error and rc != _lib.LEMSM_OK:
+        cs.mismatch("step %d %s (%s): status %d" % (k, st.op, st.note, rc))
+    return not st.error
+
+
+def _bad_index(ctx, cs, k, st):
+    if st.plant == "off_curve" and ctx.lib.lemsm_last_bad_index(ctx.h) != st.index:
+        cs.mismatch("step %d %s (%s): last_bad_index %d, the spoilt row is %d" % (k, st.op, st.note, ctx.lib.lemsm_last_bad_index(ctx.h), st.index))
+
+
+def _record(cs, k, st, what, got, want):
+    if tuple(got[1:]) != tuple(want) or not got[0] > 0:
+        cs.mismatch("step %d %s (%s): %s %s, the header's relations give %s and a time above 0" % (k, st.op, st.note, what, got, want))
+
+
+def _untouched(cs, k, st, what, got, before):
+    if got != before:
+        cs.mismatch("step %d %s (%s): the refused call changed %s from %s to %s" % (k, st.op, st.note, what, before, got))
+
+
+def _same_point(cs, k, st, name, got, want):
+    if not cref.jac_eq(ecfft_ref.CID, np.ascontiguousarray(got, np.uint64), np.ascontiguousarray(want, np.uint64)):
+        cs.mismatch("step %d %s (%s): %s is not the reference's point" % (k, st.op, st.note, name))
+
+
+def _accumulations(ctx, cs, k, st, pairs, points_buf, want_count, outs):
+    """the same multiexps through msm_device, one by one, under the same options: their accumulate counts add up to what the
+    round reported, and they give the round's points"""
+    total = 0
+    for name, (scalars, first, n), got in zip("LR", pairs, outs):
+        d = ctx.to_device(scalars)
+        try:
+            alone = ctx.msm_device(BN254, d.ptr, points_buf.ptr + first * 64, n)
+        finally:
+            d.free()
+        total += ctx.last_timing()[2]
+        _same_point(cs, k, st, name + " (msm_device)", alone, got)
+    if total != want_count:
+        cs.mismatch("step %d %s (%s): last_timing counted %d accumulations, the two multiexps alone %d" % (k, st.op, st.note, want_count, total))
+
+
+# ---- srs -----------------------------------------------------------------------------------------------------------------------
+EC_CONTENT = ("random", "identity", "all_identities", "opposite", "constant")
+EC_PLANTS = ("omega", "scale", "overlap", "off_curve")
+
+
+def _ec_points(rng, rows, n, kind):
+    pts = _pool_rows(rng, rows)
+    if kind == "identity":
+        pts[int(rng.integers(0, n))] = 0
+    elif kind == "all_identities":
+        pts[:n] = 0
+    elif kind == "opposite" and n >= 2:                            # in[j] = -in[j + n/2]: opposite operands in the first stage
+        pts[n // 2:n] = [ecfft_ref.neg(q) for q in pts[:n // 2]]
+    elif kind == "constant":
+        pts[:n] = pts[0]
+    return pts
+
+
+def _gen_ecfft(rng, plant=None):
+    lagrange = plant is None and rng.random() < 0.35
+    if plant:
+        logn = int(rng.integers(2, 6))
+    else:
+        logn = int(_pick(rng, [0, 1, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 8])) if rng.random() < 0.88 else int(rng.integers(EC_EXACT_LOGN + 1, EC_MAX_LOGN + 1))
+    n = 1 << logn
+    inverse = True if lagrange else bool(rng.integers(0, 2))
+    w = domain_ref.omega(logn)
+    if inverse:
+        w = pow(w, -1, P)
+    ssel = "half_pow" if lagrange else str(_pick(rng, ["none", "none", "zero", "one", "minus_one", "random", "random"]))
+    scale = {"none": None, "zero": 0, "one": 1, "minus_one": P - 1, "half_pow": pow(n, -1, P)}.get(ssel, 2 + _fe_int(rng) % (P - 2))
+    content = "random" if plant == "off_curve" else str(_pick(rng, EC_CONTENT))
+    rows = int(rng.integers(n, 2 * n + 1)) if lagrange else n
+    pts = _ec_points(rng, rows, n, content)
+    in_place = bool(rng.integers(0, 2)) and rows == n and plant != "overlap"
+    kw = dict(logn=logn, rows=rows, points=pts, omega=_fe(w), scale=None if scale is None else _fe(scale), in_place=in_place, content=content,
+              scale_sel=ssel, plant=plant, index=-1, exact=logn <= EC_EXACT_LOGN, scaled=scale is not None)
+    note = "logn=%d rows=%d inverse=%s scale=%s content=%s in_place=%s tag=%s" % (logn, rows, inverse, ssel, content, in_place, _tag(pts))
+    op = "lagrange" if lagrange else "ecfft"
+    if plant:
+        if plant == "omega":                                       # a primitive root of twice the order
+            kw["omega"] = _fe(domain_ref.omega(logn + 1))
+        elif plant == "scale":
+            kw["scale"], kw["scaled"] = NON_CANONICAL.copy(), True
+        elif plant == "off_curve":
+            kw["points"], kw["index"] = _off_curve(pts, rng)
+        return Step(op, note + " plant=" + plant, [("ec_logn", logn)], error=True, want=b"", **kw)
+    if kw["exact"]:
+        return Step(op, note, [("ec_logn", logn)], want=ecfft_ref.ecfft(pts[:n], w, logn, scale).tobytes(), **kw)
+    e = _ints(_rand(rng, n))                                       # sum_k e_k out[k] = sum_j c_j in[j]: ecfft_ref.lincomb_sides
+    c = [(1 if scale is None else scale) * v % P for v in ecfft_ref.ntt(e, w, logn)]
+    return Step(op, note, [("ec_logn", logn)], want=b"", e=_canon(e), c=_canon(c), **kw)
+
+
+def _draw_srs(rng, nsteps):
+    planted = int(rng.integers(0, nsteps - 1)) if rng.random() < P_REFUSAL else -1
+    plant = str(_pick(rng, EC_PLANTS))
+    return [_gen_ecfft(rng, plant if k == planted else None) for k in range(nsteps)]
+
+
+def _run_ecfft(ctx, cs, k, st):
+    n, lib = 1 << st.logn, ctx.lib
+    sc = st.scale.ctypes.data if st.scale is not None else None
+    before = ctx.ecfft_last()
+    if cs.host_entry and st.op == "ecfft" and not st.error:        # the host twin
+        got = ctx.ecfft(st.points, st.logn, st.omega, st.scale)
+        if st.exact:
+            _same(cs, k, st, got.tobytes(), st.want)
+        else:
+            _ec_identity(cs, k, st, got, n)
+        return _record(cs, k, st, "ecfft_last", ctx.ecfft_last(), _ec_figures(st))
+    d_in = _filled(ctx, 2 * st.rows, st.points)
+    d_out = d_in if st.in_place else _filled(ctx, 2 * n)
+    dst = d_in.ptr + 64 if st.plant == "overlap" else d_out.ptr
+    bad = ctypes.c_size_t(0)
+    if st.plant == "off_curve":
+        ctx.set_option("validate_points", 1)
+    try:
+        if st.op == "lagrange":
+            rc = lib.lemsm_srs_to_lagrange_device(ctx.h, BN254, d_in.ptr, st.rows, st.logn, dst)
+        else:
+            rc = lib.lemsm_ecfft_device(ctx.h, BN254, d_in.ptr, st.logn, st.omega.ctypes.data, sc, dst, ctypes.byref(bad))
+    finally:
+        if st.plant == "off_curve":
+            ctx.set_option("validate_points", cs.opts.get("validate_points", 0))    # back to what the case runs under
+    given = st.points.tobytes()
+    if not _status(cs, k, st, rc):
+        _bad_index(ctx, cs, k, st)
+        if st.plant == "off_curve" and bad.value != st.index:
+            cs.mismatch("step %d %s (%s): *bad_index %d, the spoilt row is %d" % (k, st.op, st.note, bad.value, st.index))
+        _untouched(cs, k, st, "ecfft_last", ctx.ecfft_last(), before)
+        if not st.in_place:
+            _payload(cs, k, st, d_out, b"")                        # the whole output and its zone are still 0xFF
+        return _payload(cs, k, st, d_in, given)
+    _record(cs, k, st, "ecfft_last", ctx.ecfft_last(), _ec_figures(st))
+    if st.exact:
+        if st.in_place:
+            return _payload(cs, k, st, d_in, st.want + given[n * 64:])
+        _payload(cs, k, st, d_out, st.want)
+        return _payload(cs, k, st, d_in, given)
+    got = d_out.download(np.uint8)
+    _ec_identity(cs, k, st, got[:n * 64].view(np.uint64).reshape(n, 8), n)
+    _payload(cs, k, st, d_out, got[:n * 64].tobytes() if not st.in_place else got[:n * 64].tobytes() + given[n * 64:])
+    if not st.in_place:
+        _payload(cs, k, st, d_in, given)
+
+
+def _ec_figures(st):
+    plan = api.ecfft_plan(st.logn, st.scaled)                      # (pure host)
+    return plan["point_muls"], plan["point_adds"], plan["group_ops"]
+
+
+def _ec_identity(cs, k, st, out, n):
+    out = np.ascontiguousarray(out, np.uint64).reshape(n, 8)
+    lhs = cref.best_multiexp(ecfft_ref.CID, st.e, out, 8)
+    rhs = cref.best_multiexp(ecfft_ref.CID, st.c, np.ascontiguousarray(st.points[:n]), 8)
+    if not cref.jac_eq(ecfft_ref.CID, lhs, rhs):
+        cs.mismatch("step %d %s (%s): the linear-combination identity fails" % (k, st.op, st.note))
+    for i in range(0, n, n // 16):
+        if out[i].any() and not cref.is_on_curve(ecfft_ref.CID, out[i]):
+            cs.mismatch("step %d %s (%s): output %d is not on the curve" % (k, st.op, st.note, i))
+
+
+# ---- ipa -----------------------------------------------------------------------------------------------------------------------
+IPA_CONTENT = ("random", "identity_lo", "identity_hi", "equal", "opposite", "p_zero")
+IPA_PLANTS = ("u_uinv", "u_zero", "u_non_canonical", "values_without_b", "off_curve")
+
+
+def _ipa_half(rng, top=IPA_MAX_HALF):
+    half = int(_pick(rng, IPA_HALVES)) if rng.random() < 0.5 else _log_uniform(rng, top)
+    return min(half, top)
+
+
+def _ipa_generators(rng, half, kind, u):
+    """2 half rows; `equal` / `opposite`: g_lo = u g_hi / g_lo = -u g_hi on known logarithms"""
+    if kind in ("equal", "opposite"):
+        t = [1 + _fe_int(rng) % (P - 1) for _ in range(half)]
+        sign = 1 if kind == "equal" else P - 1
+        return np.concatenate([ecfft_ref.multiples([sign * u * v % P for v in t]), ecfft_ref.multiples(t)])
+    g = _pool_rows(rng, 2 * half)
+    if kind == "identity_lo":
+        g[int(rng.integers(0, half))] = 0
+    elif kind == "identity_hi":
+        g[half + int(rng.integers(0, half))] = 0
+    return g
+
+
+def _gen_ipa_round(rng, plant=None, carried=None):
+    """carried: (p, b, g, whole buffers) that the fold before left on the device"""
+    if carried:
+        p, b, g, bufs = carried
+        half, content, with_b = len(p) // 2, "carried", True
+    else:
+        half = int(rng.integers(4, 40)) if plant else _ipa_half(rng)
+        content = "random" if plant else str(_pick(rng, ("random", "random", "identity_lo", "identity_hi", "p_zero")))
+        with_b = bool(rng.random() < 0.7) and plant != "values_without_b"
+        p = [0] * (2 * half) if content == "p_zero" else _ints(_rand(rng, 2 * half))
+        b = _ints(_rand(rng, 2 * half)) if with_b else None
+        g = _ipa_generators(rng, half, content, 1)
+        bufs = None
+    kw = dict(half=half, p=_mont(p), b=_mont(b) if with_b else None, g=g, content=content, plant=plant, index=-1, carried=carried is not None,
+              bufs=bufs, canon=_canon(p))
+    note = "half=%d b=%s content=%s tag=%s" % (half, with_b, content, _tag(kw["p"], g))
+    if plant:
+        if plant == "off_curve":
+            kw["g"], kw["index"] = _off_curve(g, rng)
+        return Step("round", note + " plant=" + plant, [("ipa_half", half)], error=True, want=b"", **kw)
+    L, Rr, vl, vr = ipa_ref.round_(p, b, g, half)
+    values = _mont([vl, vr]).tobytes() if with_b else b""
+    return Step("round", note, [("ipa_half", half)], want=values, L=L, R=Rr, **kw)
+
+
+def _gen_ipa_fold(rng, plant=None, walk=None):
+    """walk: (p, b, g) of a walked opening: all three are folded and stay on the device for the round behind"""
+    u = _challenge(rng)
+    if walk:
+        p, b, g = walk
+        half, content, given = len(p) // 2, "walk", (True, True, True)
+    else:
+        given = (True, False, True) if plant == "off_curve" else tuple(bool(v) for v in _pick(rng, [(1, 1, 1), (1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1)]))
+        content = "random" if plant or not given[2] else str(_pick(rng, ("random", "random", "identity_lo", "identity_hi", "equal", "opposite")))
+        half = int(rng.integers(1, 33)) if content in ("equal", "opposite") or plant else _ipa_half(rng, IPA_MAX_HALF if not given[2] or rng.random() < 0.25 else IPA_EXACT_HALF)
+        p, b = _ints(_rand(rng, 2 * half)), _ints(_rand(rng, 2 * half))
+        g = _ipa_generators(rng, half, content, u)
+    u_inv = pow(u, -1, P)
+    kw = dict(half=half, given=given, p=_mont(p), b=_mont(b), g=g, u=_fe(u), u_inv=_fe(u_inv), content=content, plant=plant, index=-1, feeds=walk is not None,
+              exact=half <= IPA_EXACT_HALF)
+    note = "half=%d given=%s content=%s u=%s tag=%s" % (half, "".join(n for n, v in zip("pbg", given) if v), content, u if u in (1, P - 1) else "random",
+                                                        _tag(kw["p"], kw["u"]))
+    if plant:
+        if plant == "u_uinv":
+            kw["u_inv"] = _fe((u_inv + 1) % P)
+        elif plant == "u_zero":
+            kw["u"], kw["u_inv"] = _fe(0), _fe(0)
+        elif plant == "u_non_canonical":
+            kw["u"] = NON_CANONICAL.copy()
+        else:
+            kw["g"], kw["index"] = _off_curve(g, rng)
+        return Step("fold", note + " plant=" + plant, [("ipa_half", half)], error=True, want=b"", folded=None, **kw)
+    fp, fb = ipa_ref.fold_field(p, b, half, u)
+    want = _mont(fp + p[half:]).tobytes() + _mont(fb + b[half:]).tobytes()
+    folded = [fp, fb, None]
+    if given[2] and kw["exact"]:
+        folded[2] = ipa_ref.fold_generators(g, half, u)
+        kw["want_g"] = folded[2].tobytes() + g[half:].tobytes()
+    elif given[2]:                                                  # sum e_i g'_i = sum e_i g_lo_i + sum (u e_i) g_hi_i
+        e = _ints(_rand(rng, half))
+        kw["e"], kw["ue"] = _canon(e), _canon(e + [u * v % P for v in e])
+    return Step("fold", note, [("ipa_half", half)], want=want, folded=folded, **kw)
+
+
+def _gen_ipa_s(rng):
+    k, form = int(rng.integers(0, 11)), int(_pick(rng, [MONT, CANON]))
+    u = [_challenge(rng) for _ in range(k)]
+    init = int(_pick(rng, [1, 1, 1 + _fe_int(rng) % (P - 1)]))
+    s = ipa_ref.compute_s(u, init)
+    return Step("s", "k=%d form=%d tag=%s" % (k, form, _tag(_arr(u + [init]))), [("ipa_k", k)], k=k, form=form, u=_mont(u) if k else np.zeros((1, 4), np.uint64), init=_fe(init),
+                want=(_mont(s) if form == MONT else _arr(s)).tobytes(), plant=None)
+
+
+def _gen_ipa_powers(rng):
+    n = int(_pick(rng, [0, 1, 2, 255, 256, 257, _log_uniform(rng, 1 << 12), _log_uniform(rng, 1 << 12)]))
+    x = int(_pick(rng, [0, 1, 2 + _fe_int(rng) % (P - 2), 2 + _fe_int(rng) % (P - 2)]))
+    return Step("powers", "n=%d x=%s" % (n, x if x < 2 else "random " + _tag(_arr([x]))), [("ipa_n", n)], n=n, x=_fe(x), want=_mont(ipa_ref.powers(x, n)).tobytes(), plant=None)
+
+
+def _draw_ipa(rng, nsteps):
+    """independent steps with at most one planted refusal (never the last step), or a walk: round, fold, round, ... of one opening
+    of 2^k coefficients, each round on the buffers the fold before it left on the device, the references folding alongside"""
+    if rng.random() < 0.3:
+        k = int(rng.integers(3, 8))
+        x = _fe_int(rng)
+        p, b, g = _ints(_rand(rng, 1 << k)), ipa_ref.powers(x, 1 << k), _pool_rows(rng, 1 << k)
+        steps = [_gen_ipa_round(rng, carried=(p, b, g, None))]
+        steps[0].carried = False                                   # the first round uploads its own
+        while len(steps) < nsteps and len(p) >= 2:
+            fold = _gen_ipa_fold(rng, walk=(p, b, g))
+            steps.append(fold)
+            p, b = fold.folded[0], fold.folded[1]
+            bufs = (fold.want[:len(fold.want) // 2], fold.want[len(fold.want) // 2:], fold.want_g)
+            g = fold.folded[2]
+            if len(p) < 2 or len(steps) >= nsteps:
+                fold.feeds = False
+                break
+            steps.append(_gen_ipa_round(rng, carried=(p, b, g, bufs)))
+        while len(steps) < nsteps:
+            steps.append(_gen_ipa_s(rng) if rng.random() < 0.5 else _gen_ipa_powers(rng))
+        return steps
+    planted = int(rng.integers(0, nsteps - 1)) if rng.random() < P_REFUSAL * 1.2 else -1
+    plant = str(_pick(rng, IPA_PLANTS))
+    steps = []
+    for k in range(nsteps):
+        if k == planted:
+            steps.append(_gen_ipa_round(rng, plant) if plant == "values_without_b" or (plant == "off_curve" and rng.random() < 0.5) else _gen_ipa_fold(rng, plant))
+        else:
+            steps.append(_pick(rng, [_gen_ipa_round, _gen_ipa_fold, _gen_ipa_s, _gen_ipa_powers])(rng))
+    return steps
+
+
+def _drop_carry(cs):
+    for d in getattr(cs, "carry", None) or ():
+        d.free()
+    cs.carry = None
+
+
+def _run_ipa_round(ctx, cs, k, st):
+    half, lib = st.half, ctx.lib
+    carry = getattr(cs, "carry", None) if st.carried else None
+    if st.carried and not carry:
+        cs.mismatch("step %d %s (%s): the fold before it left no buffers" % (k, st.op, st.note))
+    if carry:
+        d_p, d_b, d_g = carry
+        cs.carry = None
+        images = st.bufs
+    else:
+        _drop_carry(cs)
+        d_p, d_g = _filled(ctx, 2 * half, st.p), _filled(ctx, 4 * half, st.g)
+        d_b = _filled(ctx, 2 * half, st.b) if st.b is not None else None
+        images = (st.p.tobytes(), st.b.tobytes() if st.b is not None else None, st.g.tobytes())
+    outs = [np.full(w, 0xFFFFFFFFFFFFFFFF, np.uint64) for w in (12, 12, 4, 4)]
+    values = st.b is not None or st.plant == "values_without_b"
+    before, timing = ctx.ipa_last(), None
+    if st.plant == "off_curve":
+        ctx.set_option("validate_points", 1)
+    try:
+        rc = lib.lemsm_ipa_round_device(ctx.h, BN254, d_p.ptr, d_b.ptr if d_b else None, d_g.ptr, half, outs[0].ctypes.data, outs[1].ctypes.data,
+                                        outs[2].ctypes.data if values else None, outs[3].ctypes.data if values else None)
+    finally:
+        if st.plant == "off_curve":
+            ctx.set_option("validate_points", cs.opts.get("validate_points", 0))    # back to what the case runs under
+    try:
+        if not _status(cs, k, st, rc):
+            _bad_index(ctx, cs, k, st)
+            _untouched(cs, k, st, "ipa_last", ctx.ipa_last(), before)
+            if not all((a == 0xFFFFFFFFFFFFFFFF).all() for a in outs):
+                cs.mismatch("step %d %s (%s): the refused call wrote an output" % (k, st.op, st.note))
+        else:
+            timing = ctx.last_timing()
+            _record(cs, k, st, "ipa_last", ctx.ipa_last(), (0, 2 * half, 2 * half if st.b is not None else 0))
+            _same_point(cs, k, st, "L", outs[0], st.L)
+            _same_point(cs, k, st, "R", outs[1], st.R)
+            if st.b is not None and outs[2].tobytes() + outs[3].tobytes() != st.want:
+                cs.mismatch("step %d %s (%s): value_l, value_r differ from the reference" % (k, st.op, st.note))
+            if st.b is None and not all((a == 0xFFFFFFFFFFFFFFFF).all() for a in outs[2:]):
+                cs.mismatch("step %d %s (%s): a value output written without b" % (k, st.op, st.note))
+            # L = <p_hi, g_lo>, R = <p_lo, g_hi>
+            _accumulations(ctx, cs, k, st, ((st.canon[half:], 0, half), (st.canon[:half], half, half)), d_g, timing[2], outs[:2])
+    finally:
+        for d, image in zip((d_p, d_b, d_g), images):              # reads only: the inputs and their zones are as they were
+            if d is not None:
+                _payload(cs, k, st, d, image)
+
+
+def _run_ipa_fold(ctx, cs, k, st):
+    _drop_carry(cs)
+    half, lib = st.half, ctx.lib
+    d_p = _filled(ctx, 2 * half, st.p) if st.given[0] else None
+    d_b = _filled(ctx, 2 * half, st.b) if st.given[1] else None
+    d_g = _filled(ctx, 4 * half, st.g) if st.given[2] else None
+    before = ctx.ipa_last()
+    if st.plant == "off_curve":
+        ctx.set_option("validate_points", 1)
+    try:
+        rc = lib.lemsm_ipa_fold_device(ctx.h, BN254, d_p.ptr if d_p else None, d_b.ptr if d_b else None, d_g.ptr if d_g else None, half,
+                                       st.u.ctypes.data, st.u_inv.ctypes.data)
+    finally:
+        if st.plant == "off_curve":
+            ctx.set_option("validate_points", cs.opts.get("validate_points", 0))    # back to what the case runs under
+    keep = st.feeds and not st.error
+    if not _status(cs, k, st, rc):
+        _bad_index(ctx, cs, k, st)
+        _untouched(cs, k, st, "ipa_last", ctx.ipa_last(), before)
+        images = (st.p.tobytes(), st.b.tobytes(), st.g.tobytes())   # nothing is folded
+    else:
+        _record(cs, k, st, "ipa_last", ctx.ipa_last(), (half if st.given[2] else 0, 0, half * (st.given[0] + st.given[1])))
+        cut = len(st.want) // 2
+        images = [st.want[:cut], st.want[cut:], None]
+        if st.given[2] and st.exact:
+            images[2] = st.want_g
+        elif st.given[2]:
+            got = d_g.download(np.uint8)[:2 * half * 64]
+            rows = got.view(np.uint64).reshape(2 * half, 8)
+            lhs = cref.best_multiexp(ecfft_ref.CID, st.e, np.ascontiguousarray(rows[:half]), 8)
+            rhs = cref.best_multiexp(ecfft_ref.CID, st.ue, np.ascontiguousarray(st.g), 8)
+            if not cref.jac_eq(ecfft_ref.CID, lhs, rhs):
+                cs.mismatch("step %d %s (%s): the folded generators fail the linear-combination identity" % (k, st.op, st.note))
+            for i in range(0, half, max(1, half // 16)):
+                if rows[i].any() and not cref.is_on_curve(ecfft_ref.CID, rows[i]):
+                    cs.mismatch("step %d %s (%s): g'[%d] is not on the curve" % (k, st.op, st.note, i))
+            images[2] = got[:half * 64].tobytes() + st.g[half:].tobytes()     # the hi half and the zone as they were
+    for d, image in zip((d_p, d_b, d_g), images):
+        if d is not None:
+            _payload(cs, k, st, d, image, free=not keep)
+    if keep:
+        cs.carry = (d_p, d_b, d_g)
+
+
+def _run_ipa_s(ctx, cs, k, st):
+    _drop_carry(cs)
+    out = _filled(ctx, 1 << st.k)
+    ctx.ipa_s_device(st.u, st.k, st.init, out, st.form)
+    _record(cs, k, st, "ipa_last", ctx.ipa_last(), (0, 0, 0))
+    _payload(cs, k, st, out, st.want)
+
+
+def _run_ipa_powers(ctx, cs, k, st):
+    _drop_carry(cs)
+    out = _filled(ctx, st.n)
+    ctx.ipa_powers_device(st.x, st.n, out)
+    last = ctx.ipa_last()
+    if tuple(last[1:]) != (0, 0, 0) or (last[0] > 0) != (st.n > 0):
+        cs.mismatch("step %d %s (%s): ipa_last %s" % (k, st.op, st.note, last))
+    _payload(cs, k, st, out, st.want)
+
+
+# ---- ipa_tail ------------------------------------------------------------------------------------------------------------------
+TAIL_PLANTS = ("zero_challenge", "m_over")
+
+
+def _tail_shape(rng):
+    """(half, q) with m = 2 half 2^q <= 2^13, halves that are no powers of two and q = 0 among them; four steps in five stay
+    below 2^10 generators: the reference folds G literally, a scalar multiplication a row"""
+    log_m = int(rng.integers(1, (TAIL_MAX_LOG_M if rng.random() < 0.2 else 9) + 1))
+    q = int(rng.integers(0, log_m))
+    half = 1 << (log_m - 1 - q)
+    if half > 2 and rng.random() < 0.5:
+        half = int(rng.integers(half // 2 + 1, half))
+    return half, q
+
+
+def _gen_uround(rng, plant=None):
+    half, q = _tail_shape(rng)
+    if plant == "zero_challenge":
+        half, q = int(rng.integers(1, 9)), int(rng.integers(1, 5))
+    elif plant == "m_over":                                        # 2 half 2^q = 2^26: refused before anything is read
+        half, q = 1 << 20, 5
+    m = (2 * half) << q
+    with_b = bool(rng.random() < 0.7)
+    u = [_challenge(rng) for _ in range(q)]
+    rows = 2 if plant == "m_over" else m
+    pn = 2 if plant == "m_over" else 2 * half
+    p, b = _ints(_rand(rng, pn)), _ints(_rand(rng, pn)) if with_b else None
+    G = _pool_rows(rng, rows)
+    content = str(_pick(rng, ("random", "random", "identity")))
+    if content == "identity" and not plant:
+        G[int(rng.integers(0, rows))] = 0
+    kw = dict(half=half, q=q, m=m, p=_mont(p), b=_mont(b) if with_b else None, G=G, u=_mont(u) if q else np.zeros((1, 4), np.uint64), content=content,
+              plant=plant, index=-1)
+    note = "half=%d q=%d m=%d b=%s content=%s tag=%s" % (half, q, m, with_b, content, _tag(kw["p"], kw["u"]))
+    if plant:
+        if plant == "zero_challenge":
+            kw["u"][int(rng.integers(0, q))] = 0
+        return Step("uround", note + " plant=" + plant, [("ipa_half", half), ("ipa_k", q)], error=True, want=b"", **kw)
+    L, Rr, vl, vr = ipa_tail_ref.round_unfolded(p, b, G, half, u)
+    s = ipa_ref.compute_s(u, 1)                                    # the scalars of the two multiexps over G itself (lemsm_ipa_tail.h)
+    wl, wr = [0] * m, [0] * m
+    for h in range(1 << q):
+        for i in range(half):
+            wl[h * 2 * half + i] = s[h] * p[half + i] % P
+            wr[h * 2 * half + half + i] = s[h] * p[i] % P
+    return Step("uround", note, [("ipa_half", half), ("ipa_k", q), ("tail_m", m)], want=_mont([vl, vr]).tobytes() if with_b else b"", L=L, R=Rr,
+                wl=_canon(wl), wr=_canon(wr), **kw)
+
+
+def _gen_final(rng, plant=None):
+    q = int(rng.integers(1, 6)) if plant else int(_pick(rng, [0, 0, 1, 2, 3, 5, int(rng.integers(0, 10)), int(rng.integers(0, 10))]))
+    u = [_challenge(rng) for _ in range(q)]
+    G = _pool_rows(rng, 1 << q)
+    if rng.random() < 0.2 and not plant:
+        G[int(rng.integers(0, 1 << q))] = 0
+    kw = dict(q=q, G=G, u=_mont(u) if q else np.zeros((1, 4), np.uint64), plant=plant, index=-1)
+    if plant:
+        kw["u"][int(rng.integers(0, q))] = 0
+        return Step("final", "q=%d plant=%s tag=%s" % (q, plant, _tag(G)), [("ipa_k", q)], error=True, want=b"", **kw)
+    return Step("final", "q=%d tag=%s" % (q, _tag(G, kw["u"])), [("ipa_k", q), ("tail_m", 1 << q)], want=ipa_tail_ref.final_generator(G, u).tobytes(), **kw)
+
+
+def _draw_ipa_tail(rng, nsteps):
+    planted = int(rng.integers(0, nsteps - 1)) if rng.random() < P_REFUSAL else -1
+    plant = str(_pick(rng, TAIL_PLANTS))
+    steps = []
+    for k in range(nsteps):
+        if k == planted:
+            steps.append(_gen_final(rng, plant) if plant == "zero_challenge" and rng.random() < 0.4 else _gen_uround(rng, plant))
+        else:
+            steps.append(_gen_uround(rng) if rng.random() < 0.6 else _gen_final(rng))
+    return steps
+
+
+def _run_uround(ctx, cs, k, st):
+    _drop_carry(cs)
+    lib, half = ctx.lib, st.half
+    d_p, d_G = _filled(ctx, st.p.shape[0], st.p), _filled(ctx, 2 * st.G.shape[0], st.G)
+    d_b = _filled(ctx, st.b.shape[0], st.b) if st.b is not None else None
+    outs = [np.full(w, 0xFFFFFFFFFFFFFFFF, np.uint64) for w in (12, 12, 4, 4)]
+    before = ctx.ipa_last()
+    rc = lib.lemsm_ipa_round_unfolded_device(ctx.h, BN254, d_p.ptr, d_b.ptr if d_b else None, d_G.ptr, half, st.u.ctypes.data, st.q, outs[0].ctypes.data,
+                                             outs[1].ctypes.data, outs[2].ctypes.data if d_b else None, outs[3].ctypes.data if d_b else None)
+    try:
+        if not _status(cs, k, st, rc):
+            _untouched(cs, k, st, "ipa_last", ctx.ipa_last(), before)
+            if not all((a == 0xFFFFFFFFFFFFFFFF).all() for a in outs):
+                cs.mismatch("step %d %s (%s): the refused call wrote an output" % (k, st.op, st.note))
+        else:
+            timing = ctx.last_timing()
+            _record(cs, k, st, "ipa_last", ctx.ipa_last(), (0, st.m, st.m + (2 * half if d_b else 0)))
+            _same_point(cs, k, st, "L", outs[0], st.L)
+            _same_point(cs, k, st, "R", outs[1], st.R)
+            if d_b and outs[2].tobytes() + outs[3].tobytes() != st.want:
+                cs.mismatch("step %d %s (%s): value_l, value_r differ from the reference" % (k, st.op, st.note))
+            _accumulations(ctx, cs, k, st, ((st.wl, 0, st.m), (st.wr, 0, st.m)), d_G, timing[2], outs[:2])
+    finally:
+        for d, a in ((d_p, st.p), (d_b, st.b), (d_G, st.G)):
+            if d is not None:
+                _payload(cs, k, st, d, a.tobytes())
+
+
+def _run_final(ctx, cs, k, st):
+    _drop_carry(cs)
+    d_G = _filled(ctx, 2 * st.G.shape[0], st.G)
+    out = np.full(8, 0xFFFFFFFFFFFFFFFF, np.uint64)
+    before = ctx.ipa_last()
+    rc = ctx.lib.lemsm_ipa_final_generator_device(ctx.h, BN254, d_G.ptr, st.u.ctypes.data, st.q, out.ctypes.data)
+    try:
+        if not _status(cs, k, st, rc):
+            _untouched(cs, k, st, "ipa_last", ctx.ipa_last(), before)
+            if not (out == 0xFFFFFFFFFFFFFFFF).all():
+                cs.mismatch("step %d %s (%s): the refused call wrote its output" % (k, st.op, st.note))
+        else:
+            _record(cs, k, st, "ipa_last", ctx.ipa_last(), (0, 1 << st.q, 0))
+            _same(cs, k, st, out.tobytes(), st.want)
+    finally:
+        _payload(cs, k, st, d_G, st.G.tobytes())
+
+
 # ---- the comparisons -----------------------------------------------------------------------------------------------------------
 def _filled(ctx, n_elems, payload=None):
     """a device buffer of n_elems elements + a zone, all 0xFF, with `payload` (an (n, 4) array) at its start"""
@@ -999,10 +1610,12 @@ def _no_error(cs, k, st):
 
 
 DRAW = {"poly": _draw_poly, "domain": _draw_domain, "gate": _draw_gate, "column": _draw_column, "perm": _draw_perm, "lookup": _draw_lookup,
-        "open": _draw_open, "logup": _draw_logup}
+        "open": _draw_open, "logup": _draw_logup, "srs": _draw_srs, "ipa": _draw_ipa, "ipa_tail": _draw_ipa_tail}
 RUN = {"fft": _run_fft, "kate": _run_kate, "mul": _run_mul, "coset": _run_coset, "c2e": _run_c2e, "e2c": _run_e2c, "gate": _run_gate,
        "column": _run_column, "rlc": _run_rlc, "fp": _run_fp, "pp": _run_pp, "sort": _run_sort, "pair": _run_pair,
-       "lincomb": _run_open, "divide": _run_open, "quotient": _run_open, "mult": _run_mult}
+       "lincomb": _run_open, "divide": _run_open, "quotient": _run_open, "mult": _run_mult,
+       "ecfft": _run_ecfft, "lagrange": _run_ecfft, "round": _run_ipa_round, "fold": _run_ipa_fold, "s": _run_ipa_s, "powers": _run_ipa_powers,
+       "uround": _run_uround, "final": _run_final}
 
 
 def case_rng(seed, index):
@@ -1017,11 +1630,20 @@ def draw(family, rng):
 
 def run(ctx, cs, steps):
     """every step on ctx, compared at once; cs (fuzz_gpu.Case) names the case on a mismatch"""
-    for k, st in enumerate(steps):
-        RUN[st.op](ctx, cs, k, st)
+    try:
+        for k, st in enumerate(steps):
+            RUN[st.op](ctx, cs, k, st)
+    finally:
+        _drop_carry(cs)                                            # (buffers a fold of the ipa family kept for the round behind it)
 
 
 # ---- one family alone --------------------------------------------------------------------------------------------------------------
+MSM_FAMILIES = ("srs", "ipa", "ipa_tail")
+# the options of the MSM core an IPA round runs under, with fuzz_gpu.OPTION_DRAWS' values (tests/test_fuzz_cases.py compares them)
+MSM_OPTION_DRAWS = {"window_bits": [0, 0, 2, 3, 5, 8, 11, 13, 16, 17], "field": [0, 0, 1], "abi_points": [0, 1, 2], "slab_bits": [0, 0, 12, 14],
+                    "groups": [0, 0, 2, 3], "accum_waves": [0, 0, 2, 4], "xcd_windows": [0, 1]}
+
+
 class Mismatch(AssertionError):
     pass
 
@@ -1044,7 +1666,10 @@ def soak_case(family, seed, index):
     """(steps, options, host_entry) of case `index` of soak(family, .., seed): a function of (family, seed, index) alone"""
     rng = case_rng(seed, index)
     steps = draw(family, rng)
-    return steps, {"ws_canary": int(rng.random() < 0.3)}, bool(rng.random() < 0.3)
+    opts, host_entry = {"ws_canary": int(rng.random() < 0.3)}, bool(rng.random() < 0.3)
+    if family in MSM_FAMILIES:                                     # their rounds run the MSM core: under drawn pipeline options
+        opts.update({name: int(_pick(rng, values)) for name, values in MSM_OPTION_DRAWS.items()})
+    return steps, opts, host_entry
 
 
 def soak(family, seconds, seed, ctx=None):
@@ -1067,7 +1692,8 @@ def soak(family, seconds, seed, ctx=None):
                 raise
             done += 1
     finally:
-        ctx.set_option("ws_canary", 0)
+        for name in ["ws_canary"] + (list(MSM_OPTION_DRAWS) if family in MSM_FAMILIES else []):
+            ctx.set_option(name, 0)
         if own:
             ctx.close()
     return done

@@ -113,3 +113,64 @@ def opening_sides(p, g, Ls, Rs, us, c: int, g_final, threads: int = 1):
 def opening_values(p, b, vls, vrs, us) -> int:
     """<p, b> + sum_j (u_j^-1 value_l_j + u_j value_r_j) mod r: what c b'[0] must equal"""
     return (inner(p, b) + sum(pow(u, -1, R) * vl + u * vr for vl, vr, u in zip(vls, vrs, us))) % R
+
+
+# ---- the non-adjacent form: the oracle for k_ec_digits' recoding and the scalars that exercise its edges ------------------
+BOUNDARIES = (31, 63, 95, 127, 159, 191, 223)     # the digits a 32-bit word takes from the word above
+TOP_DIGIT = 254                                   # the highest digit of a scalar below r < 2^254
+
+
+def naf(x: int) -> list:
+    """the signed digits d_i in {-1, 0, 1} of x >= 0, lowest first, no two adjacent non-zero: the textbook recurrence (an odd
+    x takes d = 2 - (x mod 4), which leaves x - d divisible by 4)"""
+    out = []
+    while x:
+        d = 2 - (x & 3) if x & 1 else 0
+        out.append(d)
+        x = (x - d) >> 1
+    return out
+
+
+def naf_digit(x: int, i: int) -> int:
+    d = naf(x)
+    return d[i] if i < len(d) else 0
+
+
+def _first_with_top_digit() -> int:
+    """the smallest x with a digit at TOP_DIGIT (the digit count of the form never falls as x grows: bisection)"""
+    lo, hi = 1, R - 1
+    assert len(naf(lo)) <= TOP_DIGIT < len(naf(hi))
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if len(naf(mid)) > TOP_DIGIT:
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def boundary_scalars() -> list:
+    """(name, x, {digit index: sign}) for scalars whose non-adjacent form has what the name says at the places k_ec_digits
+    and mul_digits treat on their own: the digits a word takes from the word above, and the top of the top word.  The third
+    entry is what the case claims; a test asserts it against naf(x) before it runs the scalar."""
+    out = []
+    for i in BOUNDARIES:
+        out.append(("plus_at_%d" % i, 1 << i, {i: 1}))
+        out.append(("minus_at_%d" % i, 3 << i, {i: -1, i + 2: 1}))                      # 3 2^i = 2^(i+2) - 2^i
+    for i in BOUNDARIES:                                  # both signs in the word below the boundary and in the word above
+        x = -(1 << (i - 2)) + (1 << i) - (1 << (i + 2)) + (1 << (i + 4))
+        out.append(("both_signs_across_%d" % i, x, {i - 2: -1, i - 1: 0, i: 1, i + 1: 0, i + 2: -1, i + 4: 1}))
+    third = (1 << 255) // 3                               # 0x2AAA...A: a digit at every odd index up to 253
+    out.append(("third_below", third - 1, {TOP_DIGIT: 0, 253: 1, 251: 1, 0: 1}))
+    out.append(("third", third, {TOP_DIGIT: 0, 253: 1, 251: 1, 1: 1}))
+    out.append(("third_above", third + 1, {TOP_DIGIT: 1, 252: -1, 250: -1, 0: -1}))      # 3 x >= 2^255: the top digit appears
+    quiet = {j: 0 for j in range(1, 253)}                 # 252 doublings between the two additions
+    out.append(("2^253-1", (1 << 253) - 1, {253: 1, 0: -1, **quiet}))
+    out.append(("2^253+1", (1 << 253) + 1, {253: 1, 0: 1, **quiet}))
+    out.append(("(r-1)/2", (R - 1) // 2, {}))
+    out.append(("(r+1)/2", (R + 1) // 2, {}))
+    out.append(("r-2", R - 2, {TOP_DIGIT: 1}))
+    first = _first_with_top_digit()
+    out.append(("first_top_digit", first, {TOP_DIGIT: 1}))
+    out.append(("last_top_digit", R - 1, {TOP_DIGIT: 1}))
+    return out

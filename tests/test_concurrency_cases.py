@@ -215,3 +215,79 @@ def test_planted_failures_of_scenario_16(built):
         cols, table = _mult_columns(good)
         assert not good.error and logup_ref.missing_position(cols, table) is None and len(good.outs[0][2]) == 32 * good.args["t"]
         assert good.args["lens"] == a[0].args["lens"] and a[k].outs[0][2] == b""
+
+
+# ---- scenarios 17 to 20: the transform over G1 and the inner-product argument ---------------------------------------------------
+IPA_BUILDERS = {"18": lambda: {"shared": cc.scenario18()}, "19": cc.scenario19, "20": lambda: {str(k): cc.scenario20(k) for k in range(4)}}
+
+
+@pytest.fixture(scope="module")
+def built_ipa():
+    return {name: fn() for name, fn in IPA_BUILDERS.items()}
+
+
+def test_ipa_builders_are_deterministic_and_fit_their_buffers(built_ipa):
+    for name, fn in IPA_BUILDERS.items():
+        assert [sp.fingerprint() for sp in _specs(fn())] == [sp.fingerprint() for sp in _specs(built_ipa[name])], name   # reproducible from the seed
+        for sp in _specs(built_ipa[name]):
+            for out, cap, want, init in sp.outs:
+                assert len(want) % 32 == 0 and len(want) <= cap * 32, (name, sp, out)
+                assert not sp.error or want == (b"" if init is None else init.tobytes()), (name, sp, out)   # a refused call leaves its output as it was
+            assert not (sp.error and sp.small)
+    prints = [sp.fingerprint() for name in IPA_BUILDERS for sp in _specs(built_ipa[name])]
+    assert len(set(prints)) == len(prints)
+    assert len({sp.fingerprint() for k in range(4) for sp in built_ipa["20"][str(k)]}) == 4 * 5          # every context of scenario 20 has inputs of its own
+    assert [sp.op for sp in built_ipa["20"]["0"]] == ["ecfft", "round", "fold", "uround", "fft"]
+    assert [(sp.args.get("logn"), sp.args.get("half"), sp.args.get("q")) for sp in built_ipa["20"]["0"]] == [(7, None, None), (None, 257, None), (None, 65, None), (None, 64, 2), (10, None, None)]
+
+
+def test_opening_of_scenario_17_is_the_references():
+    one, two = cc.scenario17(), cc.scenario17()
+    assert all(one["want"][k].tobytes() == two["want"][k].tobytes() for k in one["want"]) and one["ecfft"].fingerprint() == two["ecfft"].fingerprint()
+    assert one["k"] == 10 and one["p"].shape == (1024, 4) and one["g"].shape == (1024, 8) and 0 < one["fold_rounds"] < 10
+    assert one["options"] == {"A": {}, "B": {"field": 1, "window_bits": 13}} and one["ecfft"].args["logn"] == 8
+    want = one["want"]
+    us = [v * RI % P for v in cc._ints(want["u"])]
+    assert len(set(us)) == 10 and all(0 < u < P for u in us)
+    # the reference's own closing identities on this opening: c b'[0] = <p, b> + sum (u^-1 value_l + u value_r), b'[0] = <s, b>
+    p = [v * RI % P for v in cc._ints(one["p"])]
+    b = cc.ipa_ref.powers(cc._ints(one["x"])[0] * RI % P, 1024)
+    c, b_fin = (cc._ints(want[k])[0] * RI % P for k in ("c", "b"))
+    vls, vrs = ([v * RI % P for v in cc._ints(want[k])] for k in ("value_l", "value_r"))
+    assert c * b_fin % P == cc.ipa_ref.opening_values(p, b, vls, vrs, us)
+    assert b_fin == cc.ipa_ref.inner(cc.ipa_ref.compute_s(us, 1), b)
+    # every challenge is the hash of its round's L and R
+    assert all(cc.opening_challenge(want["L"][j], want["R"][j]) == us[j] for j in range(10))
+
+
+def test_shared_buffers_of_scenario_18_are_read_only(built_ipa):
+    specs = built_ipa["18"]["shared"]
+    assert [sp.op for sp in specs] == ["round", "uround", "final", "ecfft", "ecfft"] and not any(sp.error for sp in specs)
+    whole = {"p": specs[0].ins["p"], "b": specs[0].ins["b"], "G": specs[0].ins["g"]}
+    assert whole["G"].shape == (cc.SHARED_ROWS, 8) and whole["p"].shape == (cc.SHARED_ROWS, 4)
+    for sp in specs:
+        assert sp.ins and all(name in ("p", "b", "g", "G") for name in sp.ins)
+        for name, arr in sp.ins.items():                                    # a prefix of the shared vector, never an output
+            assert arr.tobytes() == whole["G" if name == "g" else name][:arr.shape[0]].tobytes(), (sp, name)
+        assert all(out == "out" and init is None for out, _, _, init in sp.outs)     # outputs of the call's own, none in place
+    assert specs[3].args["lagrange"] is False and specs[4].args["lagrange"] is True and specs[4].args["rows"] == cc.SHARED_ROWS
+
+
+def test_planted_refusals_of_scenario_19(built_ipa):
+    a, b = built_ipa["19"]["A"], built_ipa["19"]["B"]
+    assert built_ipa["19"]["options"] == {"A": {"validate_points": 1}, "B": {}}
+    assert not any(sp.error for sp in b) and sorted(sp.op for sp in b) == ["ecfft", "final", "fold", "round", "uround"]
+    assert [sp.error for sp in a] == [False, True, False, True, False, True, False, True, False, True, False]
+    for k in range(1, len(a), 2):                                           # every refusal is followed by the good call of the same entry
+        assert a[k].op == a[k + 1].op and not a[k + 1].error and a[k].status == cc.BAD_ARG
+    off, inverse, zero, omega, overlap = (a[k] for k in range(1, len(a), 2))
+    g = off.ins["g"]                                                        # one generator off the curve, its index reported
+    bad_rows = [i for i in range(g.shape[0]) if g[i].any() and not cc.cref.is_on_curve(0, g[i])]
+    assert bad_rows == [off.index] and all(sp.index is None for sp in (inverse, zero, omega, overlap))
+    u, ui = (cc._ints(inverse.args[k].reshape(1, 4))[0] * RI % P for k in ("u", "u_inv"))
+    assert u * ui % P != 1 and 0 < u < P
+    assert 0 in [v for v in cc._ints(zero.args["u"])] and zero.args["q"] == 2
+    w = cc._ints(omega.args["omega"].reshape(1, 4))[0] * RI % P
+    n = 1 << omega.args["logn"]
+    assert pow(w, n, P) == P - 1                                            # a root of order 2n: no 2^logn-th root
+    assert overlap.args["overlap"] and not any(sp.args.get("overlap") for sp in a if sp is not overlap and sp.op == "ecfft")

@@ -1,8 +1,9 @@
 """The case generators of the soak's resident families (tests/fuzz_resident.py) without a GPU: 200 cases of each family from a
 fixed seed are the same cases when drawn again, every drawn size lies inside the entry's documented limits, and the error-path
-cases (a planted zero denominator, a planted missing value) are at most one in four of their family, so that the soak does not
-spend itself on refusals.  The 200 cases of `open` and `logup` also cover what those families exist for
-(test_open_and_logup_cover_what_they_exist_for)."""
+cases (a planted zero denominator, a planted missing value, a planted refusal) are at most one in four of their family, so that
+the soak does not spend itself on refusals.  The 200 cases of `open` and `logup` also cover what those families exist for
+(test_open_and_logup_cover_what_they_exist_for), and so do those of `srs`, `ipa` and `ipa_tail`
+(test_srs_and_ipa_cover_what_they_exist_for)."""
 import collections
 import os
 import re
@@ -63,10 +64,11 @@ def test_generators(drawn, family):
                 assert 0 <= value <= fr.LIMITS[name], (family, s.op, s.note, name)
             assert isinstance(s.want, (bytes, list))
     expected = {"poly": {"fft", "kate", "mul"}, "domain": {"coset", "c2e", "e2c"}, "gate": {"gate"}, "column": {"column", "rlc"},
-                "perm": {"fp", "pp"}, "lookup": {"sort", "pair"}, "open": {"lincomb", "divide", "quotient"}, "logup": {"mult"}}[family]
+                "perm": {"fp", "pp"}, "lookup": {"sort", "pair"}, "open": {"lincomb", "divide", "quotient"}, "logup": {"mult"},
+                "srs": {"ecfft", "lagrange"}, "ipa": {"round", "fold", "s", "powers"}, "ipa_tail": {"uround", "final"}}[family]
     assert set(ops) == expected and min(ops.values()) >= CASES // 2, ops  # every entry of the family is drawn often
     errors = sum(1 for steps in cases if any(s.error for s in steps))
-    if family in ("perm", "lookup", "logup"):
+    if family in ("perm", "lookup", "logup", "srs", "ipa", "ipa_tail"):
         assert 0 < errors <= CASES // 4, errors
         assert all(sum(s.error for s in steps) <= 1 for steps in cases)
     elif family == "poly":                                                  # (two empty operands of the product: rare)
@@ -134,3 +136,76 @@ def test_open_and_logup_cover_what_they_exist_for(drawn):
     for s in steps:
         assert s.error or len(s.want) == 32 * s.t
         assert s.passes[0] + s.passes[1] == logup_ref.sorts(sum(s.lens), s.t) * logup_ref.MAX_PASSES
+
+
+def test_srs_and_ipa_cover_what_they_exist_for(drawn):
+    """conditions on the 200 cases of each of the three families, met by the references alone: every step kind, every
+    point-content kind and every refusal kind occurs, and every planted refusal has a good step behind it in its chain"""
+    want = {"srs": (fr.EC_CONTENT, fr.EC_PLANTS), "ipa": (fr.IPA_CONTENT + ("carried", "walk"), fr.IPA_PLANTS),
+            "ipa_tail": (("random", "identity"), fr.TAIL_PLANTS)}
+    for family, (contents, plants) in want.items():
+        cases = drawn(family)
+        steps = [s for c in cases for s in c]
+        assert {s.content for s in steps if hasattr(s, "content")} == set(contents), family
+        assert {s.plant for s in steps if s.error} == set(plants), family
+        assert all(s.error == (s.plant is not None) for s in steps)
+        for c in cases:
+            for at, s in enumerate(c):
+                if s.error:                                                 # the good call behind the refused one
+                    assert s.want == b"" and at + 1 < len(c) and not c[at + 1].error, (family, fr.describe(c))
+                if s.plant == "off_curve":
+                    rows = s.points if family == "srs" else s.g
+                    assert 0 <= s.index < rows.shape[0] and rows[s.index].any()
+
+    steps = [s for c in drawn("srs") for s in c]
+    assert {s.logn for s in steps if not s.error} == set(range(fr.EC_MAX_LOGN + 1))
+    assert {s.exact for s in steps} == {True, False} and all(s.exact == (s.logn <= fr.EC_EXACT_LOGN) for s in steps)
+    assert {s.scale_sel for s in steps} == {"none", "zero", "one", "minus_one", "random", "half_pow"}
+    assert {s.in_place for s in steps} == {True, False}
+    for s in steps:
+        if s.op == "lagrange":
+            assert (1 << s.logn) <= s.rows <= (2 << s.logn) and s.scale_sel == "half_pow"
+        if not s.error:
+            assert len(s.want) == (64 << s.logn if s.exact else 0) and (s.exact or (s.e.shape == s.c.shape == (1 << s.logn, 32)))
+    assert {s.rows - (1 << s.logn) for s in steps if s.op == "lagrange"} >= {0}
+    assert any(s.rows == 2 << s.logn for s in steps if s.op == "lagrange") and any((1 << s.logn) < s.rows < (2 << s.logn) for s in steps)
+
+    cases = drawn("ipa")
+    steps = [s for c in cases for s in c]
+    folds = [s for s in steps if s.op == "fold" and not s.error]
+    assert {s.given for s in folds} == {g for g in [(a, b, c) for a in (False, True) for b in (False, True) for c in (False, True)] if any(g)}
+    assert {s.exact for s in folds if s.given[2]} == {True, False}
+    rounds = [s for s in steps if s.op == "round" and not s.error]
+    assert {s.b is None for s in rounds} == {True, False}
+    assert {s.form for s in steps if s.op == "s"} == {fr.MONT, fr.CANON} and {0, 10} <= {s.k for s in steps if s.op == "s"}
+    assert {0, 257} <= {s.n for s in steps if s.op == "powers"}
+    halves = {s.half for s in rounds + folds}
+    assert set(fr.IPA_HALVES) <= halves and max(halves) > 1000 and max(halves) <= fr.IPA_MAX_HALF
+    walks = [c for c in cases if any(getattr(s, "carried", False) for s in c)]
+    assert len(walks) >= 20
+    for c in walks:                                                         # a carried round stands right behind the fold that feeds it
+        for at, s in enumerate(c):
+            if getattr(s, "carried", False):
+                assert c[at - 1].op == "fold" and c[at - 1].feeds and c[at - 1].given == (True, True, True) and 2 * s.half == c[at - 1].half
+            if s.op == "fold" and s.feeds:
+                assert c[at + 1].op == "round" and c[at + 1].carried
+    grows = sum(1 for c in cases for a, b in zip(c, c[1:]) if hasattr(a, "half") and hasattr(b, "half") and b.half > a.half)
+    shrinks = sum(1 for c in cases for a, b in zip(c, c[1:]) if hasattr(a, "half") and hasattr(b, "half") and b.half < a.half)
+    assert grows >= 50 and shrinks >= 50                                    # successive steps regrow and shrink ipa_ws
+
+    steps = [s for c in drawn("ipa_tail") for s in c]
+    good = [s for s in steps if s.op == "uround" and not s.error]
+    assert all(s.m == (2 * s.half) << s.q <= 1 << fr.TAIL_MAX_LOG_M for s in good) and max(s.m for s in good) == 1 << fr.TAIL_MAX_LOG_M
+    assert any(s.q == 0 for s in good) and any(s.half & (s.half - 1) for s in good) and {s.b is None for s in good} == {True, False}
+    assert any(s.op == "uround" and s.plant == "m_over" and s.m > 1 << 24 for s in steps)
+    assert {s.op for s in steps if s.plant == "zero_challenge"} == {"uround", "final"}
+    assert {0, 1} <= {s.q for s in steps if s.op == "final"}
+
+
+def test_solo_soak_draws_the_msm_options_of_the_whole_soak():
+    for name, values in fr.MSM_OPTION_DRAWS.items():
+        assert fuzz_gpu.OPTION_DRAWS[name] == values, name
+    for family in fr.MSM_FAMILIES:
+        _, opts, _ = fr.soak_case(family, 3, 0)
+        assert set(opts) == {"ws_canary"} | set(fr.MSM_OPTION_DRAWS)
+    assert set(fr.soak_case("open", 3, 0)[1]) == {"ws_canary"}

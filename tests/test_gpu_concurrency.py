@@ -4,7 +4,9 @@ than the process has hardware queues -- and device pointers may be read by sever
 the MSM, witness and column entries, scenarios 8 to 13 the resident polynomial entries (fft to open_quotient) with the state
 they keep per context: the cached twiddle table, the regrown workspaces, the device error words, poly_last and sort_last.
 Scenarios 14 to 16 run the multiplicity entry (lookup_multiplicities), which carves the same workspace and records into the
-same sort_last, poly_last and bad_index as the sorts, the lookup and every polynomial entry.
+same sort_last, poly_last and bad_index as the sorts, the lookup and every polynomial entry.  Scenarios 17 to 20 run the
+transform over G1 and the inner-product argument's entries (include/lemsm_srs.h, lemsm_ipa.h, lemsm_ipa_tail.h), whose rounds
+run the MSM core under their context's options and add into its timing figures, and which carve ipa_ws anew at every size.
 
 Each scenario runs in a fresh child interpreter (tests/concurrency_child.py, which documents how a scenario is run and what
 it compares): contexts on device 0, every expected value from the oracle before a thread starts, threading.Thread workers
@@ -193,4 +195,41 @@ def test_16_multiplicity_errors_stay_where_they_happen():
     only, never sees a status or a message, and in its last 10 rounds creates and destroys its context per round"""
     res = _run(16)
     assert res["threads"] == 2 and res["rounds"][1] >= 20
+    _overlapped(res)
+
+
+def test_17_openings_side_by_side_in_different_states():
+    """thread A: api.ipa_open at k = 10 and an ecfft_device at logn 8; thread B: api.ipa_open_unfolded on the same inputs and
+    challenges on a context with field = 1 and window_bits = 13; u, c, b, value_l, value_r and g byte-equal between the two and
+    equal to ipa_ref's opening, L and R as group elements (canonical bytes); after every call ipa_last, ecfft_last and the
+    accumulate count of last_timing of each context are those of the same call made alone"""
+    res = _run(17)
+    assert res["threads"] == 2 and res["serial_s"] is not None
+    _overlapped(res)
+
+
+def test_18_shared_read_only_generators():
+    """one resident G of 2^12 rows, one p and one b; two contexts run ipa_round_device, ipa_round_unfolded_device,
+    ipa_final_generator_device, an out-of-place ecfft_device and srs_to_lagrange_device on the same pointers into outputs of their
+    own; the shared buffers and the zones behind them hold their uploaded bytes at the end"""
+    res = _run(18)
+    assert res["threads"] == 2
+    _overlapped(res)
+
+
+def test_19_ipa_and_ecfft_errors_stay_where_they_happen():
+    """thread A (validate_points = 1) alternates good calls with a generator off the curve, u u_inv != 1, a zero u_prev challenge,
+    an omega of the wrong order and a partial overlap: status, index, last_bad_index and last_error are its own call's after every
+    call, every refused call leaves its outputs and zones as they were, the good call behind a refusal is correct; thread B, good
+    calls only, never sees a status or a message, and in its last 10 rounds creates and destroys its context per round"""
+    res = _run(19)
+    assert res["threads"] == 2 and res["rounds"][1] >= 20
+    _overlapped(res)
+
+
+def test_20_ipa_and_ecfft_on_more_contexts_than_hardware_queues():
+    """four contexts on four threads, each a different cyclic shift of ecfft at logn 7, an IPA round at half 257, a fold at
+    half 65, an unfolded round at (64, 2), an fft_device and one msm_device (n = 1000) on its own inputs"""
+    res = _run(20)
+    assert res["threads"] == 4
     _overlapped(res)

@@ -352,3 +352,64 @@ def test_repeat_and_guards(ctx):
         assert all(cref.jac_eq(CID, a, w) for a, w in zip(other_round[:2], first_round[:2]))   # (a Jacobian triple is not unique)
         assert all(np.array_equal(a, w) for a, w in zip(other_round[2:], first_round[2:]))
         assert all(np.array_equal(a, w) for a, w in zip(other_fold, first_fold))
+
+
+# ---- the recoding at its edges: digits a word takes from the word above, and the top of the top word ---------------------
+# k_ec_digits builds the non-adjacent form of one scalar as two 256-bit masks; digit 31 + 32 j of either sign comes out of word
+# j + 1, and mul_digits starts at digit 254.  Each scalar below is asserted (against ipa_ref.naf) to have what its name says,
+# then multiplies generators through ipa_fold_device (d_g alone) and through k_ec_scale; cref.scalar_mul is the reference.
+BOUNDARY = ipa.boundary_scalars()
+BOUNDARY_IDS = [name for name, _, _ in BOUNDARY]
+
+
+def _claimed(x, claims):
+    d = ipa.naf(x)
+    assert sum(v << i for i, v in enumerate(d)) == x and 0 < x < R
+    for i, sign in claims.items():
+        assert ipa.naf_digit(x, i) == sign, i
+
+
+@functools.lru_cache(maxsize=None)
+def _six():
+    """half = 3: rows 0 .. 2 lo, 3 .. 5 hi, hi[1] the identity (read-only)"""
+    g = np.array(_pool()[0][100:106], np.uint64)
+    g[4] = 0
+    g.setflags(write=False)
+    return g
+
+
+@pytest.mark.parametrize("name,x,claims", BOUNDARY, ids=BOUNDARY_IDS)
+def test_boundary_digit_challenges(ctx, name, x, claims):
+    _claimed(x, claims)
+    g = _six()
+    got = _fold(ctx, None, None, g, 3, x)[2]
+    assert np.array_equal(got[:3], ipa.fold_generators(g, 3, x))
+    assert np.array_equal(got[1], g[1]) and np.array_equal(got[3:], g[3:])
+
+
+@functools.lru_cache(maxsize=None)
+def _eight():
+    pts = np.array(_pool()[0][200:208], np.uint64)
+    pts[6] = 0
+    w = api.omega_pow(28 - 3)
+    out = ref.ecfft(pts, ref.fr_int(w), 3)
+    pts.setflags(write=False); out.setflags(write=False)
+    return pts, w, out
+
+
+@pytest.mark.parametrize("name,x,claims", BOUNDARY, ids=BOUNDARY_IDS)
+def test_boundary_digit_scales(ctx, name, x, claims):
+    _claimed(x, claims)
+    pts, w, unscaled = _eight()
+    got = ctx.ecfft(pts, 3, w, _raw(x))
+    assert np.array_equal(got, np.array([ref.mul(x, p) if p.any() else p for p in unscaled], np.uint64))
+
+
+def test_boundary_digit_scale_at_logn_8(ctx):
+    name, x, claims = BOUNDARY[BOUNDARY_IDS.index("both_signs_across_127")]
+    _claimed(x, claims)
+    pts = np.array(_pool()[0][300:556], np.uint64)
+    w = api.omega_pow(28 - 8)
+    want = ref.ecfft(pts, ref.fr_int(w), 8)
+    got = ctx.ecfft(pts, 8, w, _raw(x))
+    assert np.array_equal(got, np.array([ref.mul(x, p) if p.any() else p for p in want], np.uint64))

@@ -1,8 +1,12 @@
-"""The four lemsm_*_last records (regfn eval, logderiv, rhs witness / fraction sums, column a / poly RLC) of one context:
-each call sets its own family's record -- ms > 0, bytes and field products what the family's plan function prices for the
-same request, by the relations include/lemsm.h documents -- and leaves the other three as they were; an empty call sets
-its own ms to 0.0.  Tiny shapes on a context of this module's own; the expected figures come from the plan functions, the
-results that are looked at from tests/rhs_ref.py and tests/column_ref.py."""
+"""The six lemsm_*_last records (regfn eval, logderiv, rhs witness / fraction sums, column a / poly RLC, the transform over
+G1 / g_to_lagrange, the inner-product argument's rounds) of one context: each call sets its own family's record -- ms > 0,
+the figures what the family's plan function prices for the same request, by the relations include/lemsm.h, lemsm_srs.h,
+lemsm_ipa.h and lemsm_ipa_tail.h document -- and leaves the other five as they were; an empty call sets its own ms to 0.0; a
+refused ecfft or IPA call leaves all six as they were (the two headers say so: the record is that of the last call that
+ran).  Tiny shapes on a context of this module's own; the expected figures come from the plan functions, the results that
+are looked at from tests/rhs_ref.py, tests/column_ref.py, tests/ecfft_ref.py and tests/ipa_ref.py."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -11,6 +15,8 @@ from helpers import jacobian_with_random_z
 from oracle import cref, pyref
 
 import column_ref
+import ecfft_ref
+import ipa_ref
 import rhs_ref
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +26,7 @@ P = G.fp
 R = 1 << 256
 RI = pow(R, -1, P)
 HALVES = [(3, 2), (1, 0)]
-LASTS = ("regfn_eval_last", "regfn_logderiv_last", "rhs_last", "column_last")
+LASTS = ("regfn_eval_last", "regfn_logderiv_last", "rhs_last", "column_last", "ecfft_last", "ipa_last")
 
 
 @pytest.fixture(scope="module")
@@ -58,12 +64,17 @@ def _records(ctx):
 
 
 def _only(ctx, before, own, bytes_, mults, empty=False):
-    """`own` is (ms, bytes_, mults) with ms > 0 (0.0 for an empty call); the other three records are as `before`"""
+    """`own` is (ms, bytes_, mults) with ms > 0 (0.0 for an empty call); the other five records are as `before`"""
+    _only_figures(ctx, before, own, (bytes_, mults), empty)
+
+
+def _only_figures(ctx, before, own, figures, empty=False):
+    """`own` is (ms, *figures) with ms > 0 (0.0 for an empty call); the other five records are as `before`"""
     after = _records(ctx)
-    ms, by, fm = after[own]
-    print(own, after[own], "expected bytes, products:", bytes_, mults)
+    ms = after[own][0]
+    print(own, after[own], "expected figures:", figures)
     assert (ms == 0.0) if empty else (ms > 0)
-    assert (by, fm) == (bytes_, mults)
+    assert tuple(after[own][1:]) == tuple(figures)
     for name in LASTS:
         if name != own:
             assert after[name] == before[name], (own, name)
@@ -159,3 +170,143 @@ def test_column_records(rctx):
     cells0 = rctx.poly_rlc(G.cid, np.zeros((0, 4), np.uint64), T, 0, 2, _fe(0x1234567), _lib.LEMSM_FORM_CANONICAL)
     assert cells0.size == 0
     _only(rctx, before, "column_last", 0, 0, empty=True)
+
+
+# ---- the transform over G1 and the inner-product argument ---------------------------------------------------------------
+FR = ecfft_ref.R_ORDER
+BAD_ARG = _lib.LEMSM_ERR_BAD_ARG
+
+
+def _plan_figures(logn, scaled):
+    plan = api.ecfft_plan(logn, scaled)
+    return plan["point_muls"], plan["point_adds"], plan["group_ops"]
+
+
+def test_ecfft_records(rctx):
+    logn, n = 4, 16
+    pts = ecfft_ref.random_points(61, 2 * n)
+    w = api.omega_pow(28 - logn)
+    before = _records(rctx)
+    rctx.ecfft(pts[:n], logn, w)                                              # the host entry, unscaled
+    _only_figures(rctx, before, "ecfft_last", _plan_figures(logn, False))
+    d_in, d_out = rctx.to_device(pts), rctx.alloc(n * 64)
+    before = _records(rctx)
+    rctx.ecfft_device(d_in, logn, w, api.half_pow(logn), d_out)
+    _only_figures(rctx, before, "ecfft_last", _plan_figures(logn, True))
+    before = _records(rctx)
+    rctx.srs_to_lagrange_device(d_in, 2 * n, logn - 1, d_out)                 # g_to_lagrange: the inverse transform with 1 / n
+    _only_figures(rctx, before, "ecfft_last", _plan_figures(logn - 1, True))
+    d_in.free(); d_out.free()
+
+
+def test_ipa_records(rctx):
+    half = 5
+    rng = pyref.SplitMix64(62)
+    p = [rng.next256() % FR for _ in range(2 * half)]
+    b = [rng.next256() % FR for _ in range(2 * half)]
+    u = 1 + rng.next256() % (FR - 1)
+    u_raw, ui_raw = ecfft_ref.fr_raw(u), ecfft_ref.fr_raw(pow(u, -1, FR))
+    g = ecfft_ref.random_points(63, 2 * half)
+    d_p, d_b, d_g = rctx.to_device(ipa_ref.raw_vec(p)), rctx.to_device(ipa_ref.raw_vec(b)), rctx.to_device(g)
+    before = _records(rctx)
+    L, Rr, vl, vr = rctx.ipa_round_device(d_p, d_b, d_g, half)
+    _only_figures(rctx, before, "ipa_last", (0, 2 * half, 2 * half))
+    wL, wR, wvl, wvr = ipa_ref.round_(p, b, g, half)
+    assert cref.jac_eq(0, L, wL) and cref.jac_eq(0, Rr, wR) and ecfft_ref.fr_int(vl) == wvl and ecfft_ref.fr_int(vr) == wvr
+    before = _records(rctx)
+    rctx.ipa_round_device(d_p, None, d_g, half)
+    _only_figures(rctx, before, "ipa_last", (0, 2 * half, 0))
+    q = 1                                                                     # the same rows read as (half, q) = (2, 1) and one left over
+    u_prev = ipa_ref.raw_vec([u])
+    before = _records(rctx)
+    rctx.ipa_round_unfolded_device(d_p, d_b, d_g, 2, u_prev, q)
+    _only_figures(rctx, before, "ipa_last", (0, 8, 8 + 4))
+    before = _records(rctx)
+    rctx.ipa_round_unfolded_device(d_p, None, d_g, 2, u_prev, q)
+    _only_figures(rctx, before, "ipa_last", (0, 8, 8))
+    before = _records(rctx)
+    rctx.ipa_final_generator_device(d_g, u_prev, q)
+    _only_figures(rctx, before, "ipa_last", (0, 2, 0))
+    for given in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0)):      # the folds last: they write
+        before = _records(rctx)
+        rctx.ipa_fold_device(d_p if given[0] else None, d_b if given[1] else None, d_g if given[2] else None, half, u_raw, ui_raw)
+        _only_figures(rctx, before, "ipa_last", (half * given[2], 0, half * (given[0] + given[1])))
+    d_s = rctx.alloc(32 << 3)
+    before = _records(rctx)
+    rctx.ipa_s_device(ipa_ref.raw_vec([u, u, u]), 3, u_raw, d_s)
+    _only_figures(rctx, before, "ipa_last", (0, 0, 0))
+    before = _records(rctx)
+    rctx.ipa_powers_device(u_raw, 8, d_s)
+    _only_figures(rctx, before, "ipa_last", (0, 0, 0))
+    before = _records(rctx)
+    rctx.ipa_powers_device(u_raw, 0, d_s)                                     # nothing to write: ms 0.0
+    _only_figures(rctx, before, "ipa_last", (0, 0, 0), empty=True)
+    for d in (d_p, d_b, d_g, d_s):
+        d.free()
+
+
+def test_refused_calls_leave_every_record(rctx):
+    logn, n, half = 3, 8, 4
+    pts = ecfft_ref.random_points(64, n)
+    off = np.array(pts, np.uint64)
+    off[5, 0] ^= np.uint64(1)                                                 # x of point 5: off the curve
+    off2 = np.array(pts, np.uint64)
+    off2[2, 0] ^= np.uint64(1)                                                # ... and of point 2 in a second copy
+    w, sc = api.omega_pow(28 - logn), api.half_pow(logn)
+    u = ecfft_ref.fr_raw(7)
+    ui = ecfft_ref.fr_raw(pow(7, -1, FR))
+    u3 = ipa_ref.raw_vec([7, 7, 7])                                           # three challenges for q = 3
+    d_in, d_off, d_off2, d_out = rctx.to_device(pts), rctx.to_device(off), rctx.to_device(off2), rctx.alloc(n * 64)
+    d_p = rctx.to_device(ipa_ref.raw_vec(list(range(1, n + 1))))
+    rctx.ecfft_device(d_in, logn, w, sc, d_out)                               # both records non-trivial first
+    rctx.ipa_round_device(d_p, d_p, d_in, half)
+    before = _records(rctx)
+    assert before["ecfft_last"][0] > 0 and before["ipa_last"][0] > 0
+    lib, h = rctx.lib, rctx.h
+    host = [np.zeros(12, np.uint64), np.zeros(12, np.uint64), np.zeros(4, np.uint64), np.zeros(4, np.uint64)]
+    outs = [a.ctypes.data for a in host]
+    zero = ecfft_ref.fr_raw(0)
+    bad = ctypes.c_size_t(0)
+
+    def ec(omega, src, dst, logn_=logn):
+        return lib.lemsm_ecfft_device(h, _lib.BN254_G1, src, logn_, omega.ctypes.data, sc.ctypes.data, dst, ctypes.byref(bad))
+
+    refusals = [
+        lambda: ec(api.omega_pow(28 - logn - 1), d_in.ptr, d_out.ptr),        # an omega of the wrong order
+        lambda: ec(w, d_in.ptr, d_in.ptr + 64),                               # partial overlap
+        lambda: ec(w, d_in.ptr, d_out.ptr, 25),
+        lambda: lib.lemsm_srs_to_lagrange_device(h, _lib.BN254_G1, d_in.ptr, n - 1, logn, d_out.ptr),
+        lambda: lib.lemsm_ipa_round_device(h, _lib.BN254_G1, d_p.ptr, None, d_in.ptr, half, *outs),   # value outputs without b
+        lambda: lib.lemsm_ipa_round_device(h, _lib.BN254_G1, d_p.ptr, d_p.ptr, d_in.ptr, 0, *outs),
+        lambda: lib.lemsm_ipa_fold_device(h, _lib.BN254_G1, d_p.ptr, None, None, half, u.ctypes.data, u.ctypes.data),     # u u_inv != 1
+        lambda: lib.lemsm_ipa_fold_device(h, _lib.BN254_G1, d_p.ptr, None, None, half, zero.ctypes.data, zero.ctypes.data),
+        lambda: lib.lemsm_ipa_round_unfolded_device(h, _lib.BN254_G1, d_p.ptr, d_p.ptr, d_in.ptr, 2, zero.ctypes.data, 1, *outs),   # a zero challenge
+        lambda: lib.lemsm_ipa_final_generator_device(h, _lib.BN254_G1, d_in.ptr, zero.ctypes.data, 1, host[0].ctypes.data),
+        lambda: lib.lemsm_ipa_s_device(h, u.ctypes.data, 25, u.ctypes.data, _lib.LEMSM_FORM_MONTGOMERY, d_out.ptr),
+        lambda: lib.lemsm_ipa_powers_device(h, u.ctypes.data, (1 << 24) + 1, d_out.ptr),
+    ]
+    for i, call in enumerate(refusals):
+        assert call() == BAD_ARG, i
+        assert _records(rctx) == before, i
+    rctx.set_option("validate_points", 1)
+    try:
+        # the spoilt row alternates between 5 and 2, so every refusal has to report its own index, and each must come from the
+        # validation itself (its message), not from a check before it
+        off_curve = [
+            (5, lambda: ec(w, d_off.ptr, d_out.ptr)),
+            (2, lambda: lib.lemsm_ipa_round_device(h, _lib.BN254_G1, d_p.ptr, d_p.ptr, d_off2.ptr, half, *outs)),
+            (5, lambda: lib.lemsm_ipa_fold_device(h, _lib.BN254_G1, None, None, d_off.ptr, half, u.ctypes.data, ui.ctypes.data)),
+            (2, lambda: lib.lemsm_ipa_round_unfolded_device(h, _lib.BN254_G1, d_p.ptr, d_p.ptr, d_off2.ptr, 2, u.ctypes.data, 1, *outs)),
+            (5, lambda: lib.lemsm_ipa_final_generator_device(h, _lib.BN254_G1, d_off.ptr, u3.ctypes.data, 3, host[0].ctypes.data)),
+        ]
+        for i, (row, call) in enumerate(off_curve):
+            assert call() == BAD_ARG and lib.lemsm_last_bad_index(h) == row, i
+            assert "validate_points" in lib.lemsm_last_error(h).decode(), (i, lib.lemsm_last_error(h).decode())
+            assert _records(rctx) == before, i
+        rctx.ipa_round_device(d_p, d_p, d_in, half)                           # the good call behind them sets its record again
+        assert rctx.ipa_last()[1:] == (0, 2 * half, 2 * half) and rctx.ipa_last()[0] > 0
+    finally:
+        rctx.set_option("validate_points", 0)
+    assert np.array_equal(d_off.download(np.uint64, off.nbytes).reshape(-1, 8), off)
+    for d in (d_in, d_off, d_off2, d_out, d_p):
+        d.free()

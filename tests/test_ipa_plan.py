@@ -173,3 +173,30 @@ def test_compute_s_against_the_product_formula():
                     want = want * u[j] % R
             assert s[i] == want, (k, i)
     assert ipa.compute_s([5, 7], 1) == [1, 7, 5, 35]                        # the first round's challenge on the top bit
+
+
+# ---- the non-adjacent form the device recoding is held against -----------------------------------------------------------
+def test_naf_is_the_non_adjacent_form():
+    rng = random.Random(25)
+    xs = [0, 1, 2, 3, R - 1] + [rng.randrange(R) for _ in range(300)] + [rng.randrange(1 << rng.randrange(1, 255)) for _ in range(300)]
+    for x in xs:
+        d = ipa.naf(x)
+        assert all(v in (-1, 0, 1) for v in d) and (not d or d[-1] == 1)
+        assert sum(v << i for i, v in enumerate(d)) == x
+        assert all(not (d[i] and d[i + 1]) for i in range(len(d) - 1))
+        assert len(d) <= ipa.TOP_DIGIT + 1                                   # mul_digits starts at digit 254
+    assert ipa.naf(7) == [-1, 0, 0, 1] and ipa.naf(0) == []
+
+
+def test_boundary_scalars_are_what_they_claim():
+    cases = ipa.boundary_scalars()
+    names = [name for name, _, _ in cases]
+    assert len(set(names)) == len(names)
+    for name, x, claims in cases:
+        assert 0 < x < R, name
+        for i, sign in claims.items():
+            assert ipa.naf_digit(x, i) == sign, (name, i)
+    for i in ipa.BOUNDARIES:                              # a digit of either sign at every word boundary
+        assert any(c.get(i) == 1 for _, _, c in cases) and any(c.get(i) == -1 for _, _, c in cases), i
+    first = dict((n, x) for n, x, _ in cases)["first_top_digit"]
+    assert ipa.naf_digit(first - 1, ipa.TOP_DIGIT) == 0 and first == (1 << 255) // 3 + 1
