@@ -113,6 +113,14 @@ __global__ __launch_bounds__(BS) void k_pip_digits(const uint4* __restrict__ sca
     }
   }
   __syncthreads();
+  if (pl.tile1) {
+    // k_scatter_tile counts and claims per tile itself: only the bin totals (k_binscan) leave this kernel
+    for (u32 i = tid; i < pl.nbins; i += BS) {
+      const u32 cnt = hist[i];
+      if (cnt) atomicAdd(&bin_total[i], cnt);
+    }
+    return;
+  }
   for (u32 i = tid; i < pl.nbins; i += BS) {
     u32 cnt = hist[i];
     u32 wl = i / pl.BW, bin = i - wl * pl.BW;
@@ -618,6 +626,101 @@ __global__ __launch_bounds__(1024) void k_binsort(GroupPlan pl, const u32* __res
   }
   __syncthreads();
   for (u32 q = tid; q < cnt; q += 1024) sorted[off + q] = stage[q];
+}
+
+// pass 1 in k_binsort's shape, for the Pippenger decoder (u16 digit columns, sign bitmap at c = 17): ONE 1024-thread block
+// per CU takes one window x one tile of TILE1 consecutive scalars, 32 consecutive digits per thread in registers (four
+// 16-byte loads and one sign word).  The LDS histogram atomic ranks every entry inside (tile, bin); one scan of the BW
+// counts gives the staging offsets; thread b claims the tile's run in bin b with ONE global atomic on bin_cursor (zeroed with
+// the other counters) -- no per-(range, bin) counts or claims from HBM, k_pip_digits writes none on this path; the tile is
+// staged bin-sorted in LDS and streamed out with consecutive lanes on consecutive positions.  Runs are 4 x as long as
+// k_scatter1's (64 entries per (tile, bin) at 2^24 points and 512 bins).  The order of a bin's runs is the order of the
+// claims, as before.
+static const u32 TILE1 = 32768;      // staged word: jl:15 | local:7 | sign:1 | bin:9 -- 32 bits, hence the tile
+__global__ __launch_bounds__(1024) void k_scatter_tile(PipDec dec, GroupPlan pl, const u32* __restrict__ bin_start,
+                                                       u32* __restrict__ bin_cursor, u32* __restrict__ entries,
+                                                       u32 xcd_windows /* 1-D grid, one XCD per window: see k_scatter1 */) {
+  static_assert(BW_MAX == 512 && MAX_LB == 7 && TILE1 == 1u << 15, "fields of the staged word");
+  __shared__ u32 stage[TILE1];
+  __shared__ u32 hist[BW_MAX];       // entries of the tile per bin
+  __shared__ u32 lstart[BW_MAX];     // where a bin's run starts in the staging buffer
+  __shared__ u32 delta[BW_MAX];      // global position of a bin's run minus its position in the staging buffer
+  __shared__ u32 wsum[16];
+  const u32 tid = threadIdx.x;
+  const u32 ntile = (pl.n + TILE1 - 1) / TILE1;
+  u32 wl, r;
+  if (xcd_windows) {
+    const u32 wpx = (pl.w1 - pl.w0 + 7u) >> 3, slot = blockIdx.x >> 3;
+    wl = (blockIdx.x & 7u) + 8u * (slot % wpx); r = slot / wpx;
+    if (wl >= pl.w1 - pl.w0) return;
+  } else { wl = blockIdx.x; r = blockIdx.y; }
+  if (r >= ntile) return;
+  const u32 w = pl.w0 + wl;
+  const u32 lmask = (1u << pl.LB) - 1u;
+  const u32 j0 = r * TILE1, j1 = min(j0 + TILE1, pl.n);
+  constexpr int PER = TILE1 / 1024;
+  static_assert(PER == 32, "one sign word per thread");
+  u32 bk[PER];   // bucket | sign << 31   (0 = no entry)
+  u32 rk[PER];   // rank inside (tile, bin)
+  if (tid < BW_MAX) hist[tid] = 0;
+  {
+    const u32 jb = j0 + tid * PER;
+    uint4 dv[PER / 8];
+    u32 sbits = 0;
+    if (jb < j1) {     // (columns are 16-byte aligned and padded to pl.dstride, the bitmap to whole 64-bit words)
+      const uint4* p = (const uint4*)(dec.dig16 + (size_t)wl * pl.dstride + jb);
+#pragma unroll
+      for (int v = 0; v < PER / 8; v++) dv[v] = p[v];
+      if (dec.signbm) sbits = ((const u32*)(dec.signbm + (size_t)wl * ((pl.n + 63) / 64)))[jb >> 5];
+    } else {
+#pragma unroll
+      for (int v = 0; v < PER / 8; v++) dv[v] = make_uint4(0, 0, 0, 0);
+    }
+    const u32 half = 1u << (pl.c - 1);
+    const bool top = !(w + 1 < pl.W);
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      const uint4 q4 = dv[k / 8];
+      const u32 word = ((k / 2) % 4 == 0) ? q4.x : ((k / 2) % 4 == 1) ? q4.y : ((k / 2) % 4 == 2) ? q4.z : q4.w;
+      const u32 raw = (k & 1) ? (word >> 16) : (word & 0xffffu);
+      u32 bucket, sign;
+      if (dec.signbm) { sign = (sbits >> k) & 1u; bucket = raw + sign; }                       // c = 17 encoding, see k_pip_digits<2>
+      else if (top) { sign = 0; bucket = raw; }
+      else { sign = raw < half ? 1u : 0u; bucket = sign ? half - raw : raw - half; }
+      bk[k] = (jb + (u32)k < j1 && bucket) ? (bucket | (sign << 31)) : 0u;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PER; k++)
+    rk[k] = bk[k] ? atomicAdd(&hist[((bk[k] & 0x7fffffffu) - 1u) >> pl.LB], 1u) : 0u;
+  __syncthreads();
+  const u32 cnt = tid < pl.BW ? hist[tid] : 0u;
+  u32 total;
+  const u32 off = block_excl_scan_1024(cnt, &total, wsum);
+  if (tid < pl.BW) {
+    lstart[tid] = off;
+    // the claim: where this tile's run starts inside the bin
+    const u32 g = wl * pl.BW + tid;
+    delta[tid] = cnt ? bin_start[g] + atomicAdd(&bin_cursor[g], cnt) - off : 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    if (bk[k]) {
+      const u32 kk = (bk[k] & 0x7fffffffu) - 1u, b = kk >> pl.LB;
+      stage[lstart[b] + rk[k]] = (tid * PER + (u32)k) | ((kk & lmask) << 15) | ((bk[k] >> 31) << 22) | (b << 23);
+    }
+  }
+  __syncthreads();
+#pragma unroll 8
+  for (int k = 0; k < PER; k++) {
+    const u32 q = tid + 1024u * (u32)k;
+    if (q < total) {
+      const u32 v = stage[q];
+      entries[delta[v >> 23] + q] = (j0 + (v & 0x7fffu)) | (((v >> 15) & 127u) << 24) | (((v >> 22) & 1u) << 31);
+    }
+  }
 }
 
 // copy single points (task results that are already final, e.g. U_{L-1} = A^{L-1}[1])

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lemsm.h"
@@ -80,7 +81,7 @@ struct Grumpkin {
 struct Options {
   long host_threads = 0, window_bits = 0, chunk = 0, tile = 0, field = 0, accum_waves = 0, groups = 0, host_slab_bits = 0, slab_bits = 0,
        abi_points = 0, stage2x = 0, xcd_windows = 0, entry_ring = 0, validate_points = 0, pyr_fuse = 0, pyr_first2 = 0, pyr_quad = 0,
-       ws_canary = 0, binsort = 0, merge_slice = 0, merge_wave_th = 0, slab_tail = 0, scatter_lean = 0, ntt_tiled = 0, dw_wrap = 0,
+       ws_canary = 0, binsort = 0, merge_slice = 0, merge_wave_th = 0, slab_tail = 0, scatter_lean = 0, scatter_tile = 0, ntt_tiled = 0, dw_wrap = 0,
        dw_fuse = 0, dw_kb = 0, dw_reuse = 0, dw_pw_lazy = 0, dw_halves = 0, dw_ntt_lazy = 0, open_group = 0;
 };
 
@@ -203,6 +204,7 @@ struct lemsm_ctx {
   std::string last_error;
   Options opt;                                    // lemsm_set_option
   u32 plan_slab_n = 0;                            // choose_lb: points of a FULL slab of the running call (every slab of a call, the ragged last one too, uses the same bin geometry)
+  bool plan_tile_ok = false;                      // make_group_plan: the digits come from PipProvider (k_scatter_tile reads its columns; no other provider may take the tile path)
   bool plan_ring = false;                         // make_group_plan: round the accumulate chunk to the entry ring's 16-entry blocks
   const struct HostStage* host_stage = nullptr;   // set by the host-pointer entries for the duration of one call
   double t_total_ms = 0, t_accum_ms = 0; int n_accum = 0;
@@ -538,7 +540,7 @@ GroupWs carve(char* base, const GroupPlan& pl, const ArenaLayout& ar, const MqLa
   w.zero_bytes_counters = o_arena - z0;
   size_t o_bin_start = take((MAX_BINS + 1) * 4), o_tile_prefix = take((MAX_BINS + 1) * 4), o_meta = take(64);
   size_t o_bstart = take(((size_t)NBpad + 1) * 4);
-  size_t o_blockc = take((size_t)pl.nblk1 * pl.nbins * 8);   // per (window, range, bin): counts, then the offsets claimed inside the bin
+  size_t o_blockc = pl.tile1 ? 0 : take((size_t)pl.nblk1 * pl.nbins * 8);   // per (window, range, bin): counts, then the offsets claimed inside the bin (k_scatter_tile claims in-kernel: not carved, no guard)
   size_t o_dig = take(pl.c ? (size_t)pl.dstride * (pl.w1 - pl.w0) * 2 + 64 : 16);
   size_t o_tinfo = take((size_t)pl.max_tiles * 16 + 16);
   size_t o_sbm = take(pl.c == 17 ? (size_t)(pl.w1 - pl.w0) * ((pl.n + 63) / 64) * 8 + 16 : 16);
@@ -554,7 +556,7 @@ GroupWs carve(char* base, const GroupPlan& pl, const ArenaLayout& ar, const MqLa
     w.bucket_count = (u32*)(base + o_bcount); w.bucket_cursor = (u32*)(base + o_bcursor);
     w.arena = base + o_arena;
     w.bin_start = (u32*)(base + o_bin_start); w.tile_prefix = (u32*)(base + o_tile_prefix); w.meta = (u32*)(base + o_meta);
-    w.bucket_start = (u32*)(base + o_bstart); w.block_counts = (u32*)(base + o_blockc); w.dig16 = (uint16_t*)(base + o_dig); w.tile_info = (uint4*)(base + o_tinfo); w.signbm = (unsigned long long*)(base + o_sbm);
+    w.bucket_start = (u32*)(base + o_bstart); w.block_counts = pl.tile1 ? nullptr : (u32*)(base + o_blockc); w.dig16 = (uint16_t*)(base + o_dig); w.tile_info = (uint4*)(base + o_tinfo); w.signbm = (unsigned long long*)(base + o_sbm);
     w.entries = (u32*)(base + o_entries); w.sorted = (u32*)(base + o_sorted);
     w.rec_key = (u32*)(base + o_rk); w.rec_pt = base + o_rp;
     w.mq_cnt = (u32*)(base + o_mqcnt); w.mq_items = (uint4*)(base + o_mqi); w.mq_partial = base + o_mqp;
@@ -581,6 +583,7 @@ u32 choose_lb(const lemsm_ctx* ctx, const WinGeom& wg, u32 n) {
   return LB;
 }
 
+const u32 TILE1_MIN_BLOCKS_PER_CU = 8;   // auto: the tile path from this many (window, tile) blocks per CU (2^22 points: 16 windows x 128 tiles = 8 x 256)
 GroupPlan make_group_plan(const lemsm_ctx* ctx, const WinGeom& wg, u32 n, u32 w0, u32 w1) {
   const u32 nb = wg.nb, d = wg.d;
   GroupPlan g; memset(&g, 0, sizeof g);
@@ -597,6 +600,16 @@ GroupPlan make_group_plan(const lemsm_ctx* ctx, const WinGeom& wg, u32 n, u32 w0
   if (n >= (1u << 16)) spb = STAGE;     // long (block, bin) runs -> full-line writes
   if (n >= (1u << 16) && d == 0 && ctx->opt.stage2x == 4) spb = 4 * STAGE;   // 1024-thread pass-1 blocks staging 16384 entries: 128-byte runs at 512 bins per window
   if (n >= (1u << 16) && d == 0 && ctx->opt.stage2x == 2) spb = 2 * STAGE;   // A/B knob: 64-byte runs at 512 bins per window; measured slower (fewer resident blocks), profiles/r01/y_scatter1_staging_ab.txt
+  // Pass 1 in whole tiles (k_scatter_tile) for the Pippenger provider's digit columns, where a window's bins fit its tables
+  // and the grid of (window, tile) blocks -- ONE 1024-thread block per CU at a time -- still fills the chip several times over:
+  // at 2^20 points there are 512 tiles for 256 CUs, measured no faster than k_scatter1 (profiles/scatter_tile/NOTES.md).
+  // Option scatter_tile: 1 = whenever the decoder allows it (any n: tests), 2 = never.
+  if (ctx->plan_tile_ok && d == 0 && wg.c && LB <= MAX_LB && g.BW <= BW_MAX && ctx->opt.scatter_tile != 2) {
+    const u64 tiles = (u64)(w1 - w0) * ((n + TILE1 - 1) / TILE1);
+    g.tile1 = (ctx->opt.scatter_tile == 1 || tiles >= (u64)TILE1_MIN_BLOCKS_PER_CU * std::max(ctx->num_cus, 1u)) ? 1u : 0u;
+  }
+  // (spb stays the digit kernel's range, the unit of its LDS histogram, on the tile path too: ranges of 8192 to 32768 scalars --
+  // fewer atomics on bin_total -- measured no faster, 274 us at 4096 against 295 at 32768: profiles/scatter_tile/NOTES.md)
   g.spb = spb;
   g.dstride = (n + 63u) / 64u * 64u;
   g.nblk1 = (n + spb - 1) / spb;
@@ -745,8 +758,13 @@ int run_group(lemsm_ctx* ctx, const Prov& prov, const WinGeom& wg, const GroupPl
   hipLaunchKernelGGL(k_binscan, dim3(1), dim3(1024), 0, st, pl, w.bin_total, w.bin_start, w.tile_prefix, w.meta);
   // >= 8 windows: 1-D grid, one XCD per window (see the kernel); else (windows, ranges)
   const u32 xw = (gw >= 8 && ctx->opt.xcd_windows != 1) ? 1u : 0u;
-  dim3 g1 = xw ? dim3(8u * ((gw + 7) / 8) * pl.nblk1) : dim3(gw, pl.nblk1);
-  if (pl.spb > 2 * STAGE)
+  const u32 nr1 = pl.tile1 ? (pl.n + TILE1 - 1) / TILE1 : pl.nblk1;   // pass-1 blocks per window: tiles or ranges
+  dim3 g1 = xw ? dim3(8u * ((gw + 7) / 8) * nr1) : dim3(gw, nr1);
+  if (pl.tile1) {   // whole tiles that claim their runs themselves (make_group_plan chooses it for PipProvider only: the digit kernel wrote no block_counts)
+    if constexpr (std::is_same<Prov, PipProvider>::value)
+      hipLaunchKernelGGL(k_scatter_tile, g1, dim3(1024), 0, st, dec, pl, w.bin_start, w.bin_cursor, w.entries, xw);
+    else return fail(ctx, LEMSM_ERR_HIP, "internal: tile path planned for another digit provider");
+  } else if (pl.spb > 2 * STAGE)
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, 4 * STAGE, 1024>), g1, dim3(1024), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
   else if (pl.spb > STAGE)
     hipLaunchKernelGGL((k_scatter1<typename Prov::Dec, 2 * STAGE>), g1, dim3(256), 0, st, dec, pl, w.block_counts, w.bin_start, w.entries, xw);
@@ -958,6 +976,7 @@ int run_windows_enqueue(lemsm_ctx* ctx, MakeSrc make_src, size_t n, const WinGeo
   const size_t SLAB = wr.SLAB, nslabs = wr.nslabs, nrec = wr.nrec, ptb = wr.ptb;
   const size_t out_slab = wr.out_slab, err_stride = wr.err_stride, err_bytes = wr.err_cap;
   ctx->plan_ring = false;
+  ctx->plan_tile_ok = std::is_same<decltype(make_src((size_t)0, (u32)0)), PipProvider>::value;
   const HostStage* hs = ctx->host_stage;
   const bool shared = nrec < nslabs;     // the slabs share one tail (shared_tail())
   const u32 nba = shared ? (u32)nslabs : 1u;
@@ -1928,6 +1947,7 @@ static const struct OptionRow { const char* name; long Options::*field; long lo,
   {"xcd_windows", &Options::xcd_windows, 0, 1, false},
   {"ws_canary", &Options::ws_canary, 0, 1, false},
   {"scatter_lean", &Options::scatter_lean, 0, 1, false},      // 1: k_scatter1 with two adjacent bins per thread (A/B knob: measured no faster)
+  {"scatter_tile", &Options::scatter_tile, 0, 2, false},      // pass 1 in whole 32768-scalar tiles (k_scatter_tile): 0 = auto (make_group_plan), 1 = wherever the decoder allows it, 2 = never
   {"validate_points", &Options::validate_points, 0, 1, false},
   {"entry_ring", &Options::entry_ring, 0, 1, false},
   {"dw_pw_lazy", &Options::dw_pw_lazy, 0, 1, false},

@@ -27,6 +27,7 @@ struct GroupPlan {
   uint32_t nbins;    // (w1-w0)*BW <= MAX_BINS
   uint32_t spb;      // scalars per pass-1 block (<= STAGE)
   uint32_t nblk1;    // pass-1 blocks = ceil(n / spb)
+  uint32_t tile1;    // 1: pass 1 runs in whole tiles of TILE1 scalars that claim their runs themselves (k_scatter_tile); no per-(range, bin) counts
   uint32_t T2;       // entries per pass-2 tile
   uint32_t max_tiles;// upper bound on pass-2 tiles
   uint32_t bin_cap;  // pass 2: bins of at most this many entries are sorted whole by ONE block (k_binsort); 0 = every bin goes through the tiled path
